@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|5] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, settle the GPU (untimed windows, see ntt_headline), W warmup steps, K timed
+steps, the outputs of the last step if --dump-outputs is given, and the JSON line.  --full adds everything else the benchmark measures
+or checks: the word-for-word parity against the CPU oracle, the cpu_baseline legs, the shader-clock and device-copy probes, the
+Merkle / coset-evaluation / config-5 / commit-pipeline / side legs below and, with more than one rank, the C-ABI self-test.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (rank 0's shard), as DIR/<name>.npy: for each array of
+u64 words, <name>.npy holds the words as float64 (rounded to 53 bits) and <name>_bytes.npy their eight little-endian bytes as float32
+(exact, shape (words, 8)).  The inputs are seeded, and the headline's buffer is re-seeded right before the timed region, so the same
+arguments give the same inputs in every run.
 
 N > 1 may be launched either by the driver (python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...) or simply as `python bench.py --gpus N`: with no
@@ -12,13 +22,15 @@ GPU, device-resident in and out, in place (math/ntt.rs:67-82 semantics, bit-exac
 path over the whole batch = one tf_ntt_bfe_dev call.  Independent transforms shard across ranks with no data-path
 collective, so N ranks run N x 256 transforms: weak scaling.
 
-Prints ONE JSON line (rank 0).  `value` = (N * 256 * 2^20 * K elements) / (max-over-ranks time of the K steps).
+Prints ONE JSON line (rank 0).  `value` = N * 256 * 2^20 elements / (median over the K timed steps of one step's time, max over
+ranks); `ms_per_step` is that median step time.
   roofline    : dominant kernel ntt_pass_kernel; achieved = algorithmic bytes per launch / average launch duration from
                 HIP events over the timed region.  A 2^20 transform is 2 launches of that kernel (one per pass), and
                 SURVEY.md 8(d) prices a transform at 16 B/element, so one launch carries 8 B/element x (elements it touches).
-  cpu_baseline: the CPU oracle (C restatement of the reference algorithm, kind "port") timed on this box's host cores on
-                the same 256 x 2^20 workload, one transform per thread (what a rayon caller of the single-threaded ntt()
+  cpu_baseline: (--full) the CPU oracle (C restatement of the reference algorithm, kind "port") timed on this box's host cores
+                on the same 256 x 2^20 workload, one transform per thread (what a rayon caller of the single-threaded ntt()
                 does).  Rank 0, N = 1 only.
+The legs below run with --full only:
   merkle      : the second half of BASELINE.json's metric -- Tip5 Merkle leaves/s on configs[2] (one 2^24-leaf tree per
                 GPU, full node array, root all-gathered over RCCL when N > 1), with its own integer-VALU roofline and the
                 oracle's par_new restatement (util_types/merkle_tree.rs:165-212) timed on the host cores in the same run;
@@ -188,6 +200,49 @@ def profile_matches(profile, ident):
     return bool(lib) and lib.get("source_hash") == ident["source_hash"] and lib.get("tf_version") == ident["tf_version"]
 
 
+def oracle_checks(args):
+    """Parity against the CPU oracle and the cpu_baseline legs: part of a --full run unless --no-cpu-baseline says otherwise."""
+    return args.full and not args.no_cpu_baseline
+
+
+def not_checked(args):
+    return "not checked (--no-cpu-baseline)" if args.full else "not checked (plain run: --full compares with the oracle)"
+
+
+DUMP_HEAD_WORDS = 1 << 20    # --dump-outputs: the first 2^20 words of an output, whole ...
+DUMP_SAMPLE_WORDS = 1 << 18  # ... plus 2^18 words at seeded positions over all of it (<= 50 MiB per output in the two forms)
+
+
+def dump_sample_index(total, seed):
+    """Positions of an output's words that --dump-outputs writes: the head, then a fixed seeded sample of the rest."""
+    import numpy as np
+
+    head = np.arange(min(total, DUMP_HEAD_WORDS), dtype=np.int64)
+    if total <= DUMP_HEAD_WORDS:
+        return head
+    tail = np.sort(np.random.default_rng(seed).integers(DUMP_HEAD_WORDS, total, DUMP_SAMPLE_WORDS, dtype=np.int64))
+    return np.concatenate([head, tail])
+
+
+def dump_words(out_dir, name, words):
+    """u64 words (numpy) -> out_dir/<name>.npy (float64 values) and out_dir/<name>_bytes.npy (float32 little-endian bytes, exact)."""
+    import numpy as np
+
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), words.astype(np.float64))
+    np.save(os.path.join(out_dir, name + "_bytes.npy"), words.astype("<u8").view(np.uint8).reshape(-1, 8).astype(np.float32))
+
+
+def dump_device_words(ctx, name, t, seed):
+    """Rank 0 writes the dump sample of the int64 device tensor `t` (its words in order)."""
+    np, torch = ctx["np"], ctx["torch"]
+    idx = dump_sample_index(t.numel(), seed)
+    got = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy().view(np.uint64)
+    if ctx["rank"] == 0:
+        dump_words(ctx["args"].dump_outputs, name, got)
+
+
 def sharding_all_true(ctx, flag):
     from twenty_first_amd import sharding
 
@@ -242,14 +297,19 @@ def main():
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256, help="transforms per GPU (config 2)")
     ap.add_argument("--no-settle", action="store_true", help="skip the untimed stabilisation passes before the warmup")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the oracle parity checks, the cpu_baseline legs, the clock / copy probes and the "
+                                                         "Merkle / coset-evaluation / config-5 / commit-pipeline / side legs (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64 / float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no oracle parity checks and no cpu_baseline legs")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even for one rank (exercises the N > 1 code path on a 1-GPU box)")
-    ap.add_argument("--no-extra", action="store_true", help="headline NTT leg only (no Merkle / coset-evaluation / config-5 legs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: headline NTT leg only (no Merkle / coset-evaluation / config-5 legs)")
     ap.add_argument("--c5-ntts", type=int, default=4096, help="config 5: transforms of 2^20 points in the whole job")
     ap.add_argument("--c5-trees", type=int, default=256, help="config 5: trees of 2^20 leaves in the whole job")
     ap.add_argument("--c5-log-n", type=int, default=20, help="diagnostic: log2 of config 5's transform length and leaves per tree (BASELINE: 20; the record names the size)")
     ap.add_argument("--merkle-log-leaves", type=int, default=24, help="diagnostic: log2 of the Merkle leg's leaves per tree (BASELINE: 24; the record names the size)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(args))
@@ -302,7 +362,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    if not args.no_cpu_baseline:
+    if oracle_checks(args):
         # The oracle is loaded by every rank (each checks its own shard).  Rank 0 goes first: it rebuilds the portable library if it is
         # stale -- so that no two ranks ever run the compiler on the same file -- and then switches ITSELF to the -O3 -march=native build
         # for the timed CPU legs (which has to be chosen before the oracle is first loaded); the other ranks load the portable one after.
@@ -324,7 +384,7 @@ def main():
     else:
         out = ntt_headline(ctx)
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # the other legs run on every rank (they contain collectives); rank 0 reports
         try:
             out["merkle"] = merkle_leg(ctx)
@@ -351,7 +411,7 @@ def main():
     if use_dist:
         # the first multi-GPU record must be complete on its own: rank 0 runs the C++ host mirror's self-test (every visible device
         # driven through the C ABI from its own host thread, and one tf_*_multi call over all of them) and embeds its evidence lines
-        if rank == 0:
+        if rank == 0 and args.full:
             out["c_abi_selftest"] = c_abi_selftest(tf, np)
         barrier()
         dist.destroy_process_group()
@@ -435,7 +495,7 @@ def ntt_headline(ctx):
     # pass, every pass of a process) -- the shader clock measured here tells such a run from a slow kernel.  Run windows
     # of 25 passes until two consecutive windows agree within 2 % (at least 4 windows, at most 40), then the W warmup steps.
     settle = 0
-    sclk_before = tf.lib().tf_debug_sclk_mhz()
+    sclk_before = tf.lib().tf_debug_sclk_mhz() if args.full else None
 
     def copy_gbs():
         """Platform sanity reference: a plain 2 GiB device copy (read + write), GB/s."""
@@ -450,7 +510,7 @@ def ntt_headline(ctx):
         torch.cuda.synchronize()
         return 3 * 2 * x.numel() * 8 / (c0.elapsed_time(c1) * 1e-3) / 1e9
 
-    copy_before = copy_gbs()
+    copy_before = copy_gbs() if args.full else None
     if not args.no_settle:
         prev, best = None, None
         for w in range(40):
@@ -469,34 +529,31 @@ def ntt_headline(ctx):
             prev = cur
     for _ in range(args.warmup):
         tf.device.ntt_(x, n, batch=batch)
+    # the settle loop runs a varying number of in-place passes: re-seed, so that the input of every timed step (and the output that
+    # --dump-outputs writes) depends on the arguments alone
+    tf.device.fill_random(x, SEED_C2, first_index=rank * batch * n)
     barrier()
 
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    # The K timed steps, an event after every step: `value` is priced on the median of these K per-step intervals (max over ranks;
+    # "median of >= 10 runs"), the wall-clock mean of the same K steps is reported beside it.
+    k2 = args.steps
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(k2 + 1)]
     barrier()
     t0 = time.perf_counter()
-    ev0.record()
-    for _ in range(args.steps):
-        tf.device.ntt_(x, n, batch=batch)
-    ev1.record()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    elapsed = t1 - t0
-    ev_ms = ev0.elapsed_time(ev1)
-    # "median of >= 10 runs".  A SECOND pass of the same K steps, an event after every step (an event per step costs
-    # ~2 % when it sits inside the timed region, so the single interval above stays free of them): `value` is priced on the median of
-    # these K per-step intervals (max over ranks), the single-interval mean of the first pass is reported beside it.
-    k2 = max(args.steps, 10)
-    barrier()
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(k2 + 1)]
     evs[0].record()
     for i in range(k2):
         tf.device.ntt_(x, n, batch=batch)
         evs[i + 1].record()
     torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    elapsed = t1 - t0
+    ev_ms = evs[0].elapsed_time(evs[k2])
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(k2))
     median_ms = 0.5 * (step_ms[(k2 - 1) // 2] + step_ms[k2 // 2])
-    sclk_after = tf.lib().tf_debug_sclk_mhz()
-    copy_after = copy_gbs()
+    if args.dump_outputs:
+        dump_device_words(ctx, "ntt_out", x, SEED_C2)  # x after the last timed step: NTT^K of the seeded input
+    sclk_after = tf.lib().tf_debug_sclk_mhz() if args.full else None
+    copy_after = copy_gbs() if args.full else None
     barrier()
     elapsed = ctx["max_over_ranks"](elapsed)
     median_ms = ctx["max_over_ranks"](median_ms * 1e-3) * 1e3
@@ -582,23 +639,24 @@ def ntt_headline(ctx):
             "inputs": f"SplitMix64, seed 0x{SEED_C2:X} (SURVEY.md 8(d)), generated on the device",
         },
         "roofline": roofline,
-        "timing": {"value_from": f"median of {k2} per-step event intervals (second pass of the same steps), max over ranks",
+        "timing": {"value_from": f"median of the {k2} per-step event intervals of the timed steps, max over ranks",
                    "per_step_ms": {"min": round(step_ms[0], 4), "median": round(median_ms, 4), "max": round(step_ms[-1], 4), "n": k2},
                    "single_interval": {"ms_per_step": round(mean_ms_per_step, 4), "value": round(mean_value, 3),
-                                       "note": f"the contract's region: {args.steps} steps between two barriers + synchronisations, wall clock, max over ranks"}},
+                                       "note": f"the same {args.steps} timed steps between two barriers + synchronisations, wall clock, max over ranks"}},
         "settle_steps": settle,
-        "sclk_mhz": {"before_settle": round(sclk_before, 0), "after_timed_region": round(sclk_after, 0),
-                     "note": "one-wave idle probe; the clock under load is in roofline.valu_bound (from GRBM_GUI_ACTIVE)"},
-        "device_copy_gbs": {"before_settle": round(copy_before, 0), "after_timed_region": round(copy_after, 0),
-                            "note": "torch copy of the 2 GiB workload buffer, read + write: a platform reference (normally ~4500-5000)"},
     }
+    if args.full:
+        out["sclk_mhz"] = {"before_settle": round(sclk_before, 0), "after_timed_region": round(sclk_after, 0),
+                           "note": "one-wave idle probe; the clock under load is in roofline.valu_bound (from GRBM_GUI_ACTIVE)"}
+        out["device_copy_gbs"] = {"before_settle": round(copy_before, 0), "after_timed_region": round(copy_after, 0),
+                                  "note": "torch copy of the 2 GiB workload buffer, read + write: a platform reference (normally ~4500-5000)"}
     del x
     # ---- parity (every rank, every world size): whole transforms of THIS rank's shard against the oracle, word for word, on a
     # fresh run after the timed region.  One rank: the first 32 and the last transform of the batch; several ranks: the first
     # and the last transform of every rank's shard (rank r holds transforms [r batch, (r + 1) batch) of the job's sequence).
     cores = os.cpu_count() or 1
-    if args.no_cpu_baseline:
-        out["parity"] = "not checked (--no-cpu-baseline)"
+    if not oracle_checks(args):
+        out["parity"] = not_checked(args)
         out["cpu_baseline"] = None
         return out
     first, last = rank * batch, rank * batch + batch - 1
@@ -920,6 +978,10 @@ def config5_leg(ctx, steps, warmup, headline):
         res["roofline"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
                            "traffic": None, "note": "this rank's NTT phase: 16 B/element over the max-over-ranks time; the kernels are the headline's "
                                                     "(its roofline block says which resource bounds them)"}
+        if args.dump_outputs:
+            # the transforms after warmup + steps in-place passes (rank 0's shard), and every root of the job
+            dump_device_words(ctx, "c5_ntt_out", x[: max(nt, 1) * n], SEED_C5)
+            dump_device_words(ctx, "c5_roots", roots, SEED_C5)
     del x, leaves, nodes
     # ---- one digest for the whole job (every world size must print the same one): Tip5 hash_varlen of the gathered roots, by the
     # HIP path; every rank checks it against the oracle's hash_varlen of the same roots and against every other rank's digest
@@ -936,8 +998,8 @@ def config5_leg(ctx, steps, warmup, headline):
     if not same:
         raise SystemExit(f"rank {rank}: the gathered roots / their digest differ between the ranks")
     res["roots_identical_on_all_ranks"] = True
-    if args.no_cpu_baseline:
-        res["parity"] = "not checked (--no-cpu-baseline)"
+    if not oracle_checks(args):
+        res["parity"] = not_checked(args)
         res["cpu_baseline"] = None
         return res
     # ---- parity, every rank: the first and the last transform and the first and the last tree (every node) of THIS rank's shard

@@ -25,7 +25,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out_path):
+def _worker(rank, world, port, out_path, full=True, dump_dir=None):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -114,14 +114,15 @@ def _worker(rank, world, port, out_path):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    args = argparse.Namespace(gpus=world, steps=2, warmup=1, config=2, log_n=10, batch=6, no_settle=True, no_cpu_baseline=False, force_dist=True,
-                              no_extra=False, c5_ntts=5, c5_trees=3, c5_log_n=8, merkle_log_leaves=8)
+    args = argparse.Namespace(gpus=world, steps=2 if full else 3, warmup=1, config=2, log_n=10, batch=6, no_settle=True, no_cpu_baseline=False, force_dist=True,
+                              no_extra=False, c5_ntts=5, c5_trees=3, c5_log_n=8, merkle_log_leaves=8, full=full, dump_outputs=dump_dir)
     tfs = Tf()
     ctx = dict(tf=tfs, torch=TorchShim(), dist=dist, np=np, dev=dev, world=world, rank=rank, use_dist=use_dist, barrier=barrier,
                max_over_ranks=max_over_ranks, args=args, ident=bench.library_identity(tfs), cpu_cache={})
     head = bench.ntt_headline(ctx)
-    head["merkle"] = bench.merkle_leg(ctx)
-    head["config5"] = bench.config5_leg(ctx, steps=2, warmup=1, headline=True)
+    if full:
+        head["merkle"] = bench.merkle_leg(ctx)
+        head["config5"] = bench.config5_leg(ctx, steps=2, warmup=1, headline=True)
     if rank == 0:
         json.dump(head, open(out_path, "w"))
     dist.barrier()
@@ -158,3 +159,29 @@ def test_bench_legs_at_world_sizes_1_and_2_over_gloo(tmp_path):
     # one 2^8-leaf tree over two ranks by the reference's subtree split has the root of the same tree built on one rank
     sharded = recs[2]["merkle"]["single_tree_sharded"]
     assert "error" not in sharded and sharded["root"] == recs[1]["merkle"]["root"]
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_k_steps_and_dumps_the_last_output(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, checks nothing against the oracle, and --dump-outputs writes the words of
+    the last timed step: NTT^K of the seeded input, identical in two runs, as float64 values and exact float32 bytes."""
+    import torch.multiprocessing as mp
+
+    from oracle import tfo
+
+    dumps = []
+    for run in range(2):
+        out, dump = str(tmp_path / f"plain{run}.json"), str(tmp_path / f"dump{run}")
+        mp.spawn(_worker, args=(1, _free_port(), out, False, dump), nprocs=1, join=True)
+        r = json.load(open(out))
+        assert r["steps"] == 3 and r["timing"]["per_step_ms"]["n"] == 3 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert r["parity"].startswith("not checked") and r["cpu_baseline"] is None and "sclk_mhz" not in r and "merkle" not in r
+        assert sorted(os.listdir(dump)) == ["ntt_out.npy", "ntt_out_bytes.npy"]
+        dumps.append((np.load(os.path.join(dump, "ntt_out.npy")), np.load(os.path.join(dump, "ntt_out_bytes.npy"))))
+    vals, raw = dumps[0]
+    assert vals.dtype == np.float64 and raw.dtype == np.float32 and raw.shape == (6 << 10, 8)
+    assert np.array_equal(vals, dumps[1][0]) and np.array_equal(raw, dumps[1][1])
+    want = tfo.fill_random(6 << 10, 0x7F210002)
+    for _ in range(3):
+        want = tfo.ntt(want, batch=6)
+    assert np.array_equal(raw.astype(np.uint8).reshape(-1).view("<u8"), want) and np.array_equal(vals, want.astype(np.float64))

@@ -12,7 +12,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for spec in "$@"; do
     name=${spec%%|*}; rest=${spec#*|}; envs=${rest%%|*}; lib=${rest#*|}
     libenv=""; [ -n "$lib" ] && libenv="TF_HIP_LIBRARY=$REPO/$lib"
-    env $envs $libenv timeout 600 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extra > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err"
+    env $envs $libenv timeout 600 python bench.py --steps 40 --warmup 5 --full --no-cpu-baseline --no-extra > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err"
     python - "$OUT/${name}_$r.json" "$name" <<'PY'
 import json, sys
 try:

@@ -22,7 +22,7 @@ for k, v in per.items():
     g = max(x[0] for x in v)
     full = sorted([x for x in v if x[0] == g], key=lambda x: x[1])
     d = [x[2] - x[1] for x in full]
-    last = d[-60:]  # the timed region (50 steps) and the 10 steps after it: the last 60 full-size dispatches
+    last = d[-60:]  # the timed region (50 steps) and the 10 untimed steps before it: the last 60 full-size dispatches
     res[k] = {"full_size_dispatches": len(d), "avg_us_all": sum(d) / len(d) / 1e3, "avg_us_last_60": sum(last) / len(last) / 1e3,
               "median_us_last_60": statistics.median(last) / 1e3}
 summary = {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra",

@@ -8,13 +8,13 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+CMD="python $REPO/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/extras" -o all -- $CMD > "$OUT/extras.log" 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, json, os, statistics, sys
 out = sys.argv[1]
 g = glob.glob(os.path.join(out, "extras/**/*kernel_trace.csv"), recursive=True)
-summary = {"command": "bench.py --steps 10 --warmup 3 --no-cpu-baseline (headline + extra workloads)"}
+summary = {"command": "bench.py --steps 10 --warmup 3 --full --no-cpu-baseline (headline + extra workloads)"}
 if g:
     per = {}
     for r in csv.DictReader(open(g[0])):

@@ -4,6 +4,7 @@
 set -u
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd "$REPO"
+B=${BENCH_OUT:-bench_outputs}; mkdir -p "$B"  # the bench records of this session
 {
   echo "== product library: python -m pytest tests -m gpu"
   python -m pytest tests -m gpu -q 2>&1 | tail -n 2
@@ -14,7 +15,7 @@ cd "$REPO"
   echo "== C++ host mirror"
   twenty-first_amd/host/selftest 2>&1 | tail -n 6
 } > gpurun_out/r04_final_suites.txt 2>&1
-python bench.py > gpurun_out/r04_bench_final.json 2> gpurun_out/r04_bench_final.err
+python bench.py --full > "$B/r04_bench_final.json" 2> "$B/r04_bench_final.err"
 echo "bench rc=$?" >> gpurun_out/r04_final_suites.txt
 bash tools/profile_bench.sh r04 > gpurun_out/r04_profile_bench.log 2>&1
 bash tools/prof_r02.sh r04p > gpurun_out/r04p_prof.log 2>&1

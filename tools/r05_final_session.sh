@@ -7,6 +7,7 @@
 set -u
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd "$REPO"
+B=${BENCH_OUT:-bench_outputs}; mkdir -p "$B"  # the bench records of this session
 mkdir -p gpurun_out
 timeout 1500 bash tools/prof_r02.sh r05p > gpurun_out/r05p_prof.log 2>&1
 python tools/make_profile_records.py gpurun_out/prof_r05p r05p > gpurun_out/r05p_records.log 2>&1
@@ -23,10 +24,10 @@ cp gpurun_out/prof_r05p/summary.txt gpurun_out/r05p_rocprof_summary.txt 2>/dev/n
   echo "== smoke"
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 1
 } > gpurun_out/r05_final_suites.txt 2>&1
-python bench.py > gpurun_out/r05_bench_final.json 2> gpurun_out/r05_bench_final.err
+python bench.py --full > "$B/r05_bench_final.json" 2> "$B/r05_bench_final.err"
 echo "bench rc=$?" >> gpurun_out/r05_final_suites.txt
-python bench.py --force-dist --config 5 2> /dev/null | tail -1 > gpurun_out/r05_c5_forcedist.json
-python bench.py --force-dist --no-extra 2> /dev/null | tail -1 > gpurun_out/r05_c2_forcedist.json
+python bench.py --full --force-dist --config 5 2> /dev/null | tail -1 > "$B/r05_c5_forcedist.json"
+python bench.py --full --force-dist --no-extra 2> /dev/null | tail -1 > "$B/r05_c2_forcedist.json"
 timeout 900 bash tools/profile_bench.sh r05 > gpurun_out/r05_profile_bench.log 2>&1
 python tools/reference_bench_shapes.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r05_reference_bench_shapes.txt
 python tools/tip5_times.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r05_tip5_times.txt

@@ -8,6 +8,7 @@
 set -u
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd "$REPO"
+B=${BENCH_OUT:-bench_outputs}; mkdir -p "$B"  # the bench records of this session
 mkdir -p gpurun_out
 T=r06
 PART=${1:-ab}
@@ -29,10 +30,10 @@ cp gpurun_out/prof_${T}pipe/summary.json gpurun_out/${T}pipe_rocprof_summary.jso
   echo "== smoke"
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 1
 } > gpurun_out/${T}_final_suites.txt 2>&1
-python bench.py > gpurun_out/${T}_bench_final.json 2> gpurun_out/${T}_bench_final.err
+python bench.py --full > "$B/${T}_bench_final.json" 2> "$B/${T}_bench_final.err"
 echo "bench rc=$?" >> gpurun_out/${T}_final_suites.txt
-python bench.py --force-dist --config 5 2> /dev/null | tail -1 > gpurun_out/${T}_c5_forcedist.json
-python bench.py --force-dist --no-extra 2> /dev/null | tail -1 > gpurun_out/${T}_c2_forcedist.json
+python bench.py --full --force-dist --config 5 2> /dev/null | tail -1 > "$B/${T}_c5_forcedist.json"
+python bench.py --full --force-dist --no-extra 2> /dev/null | tail -1 > "$B/${T}_c2_forcedist.json"
 timeout 900 bash tools/profile_bench.sh ${T} > gpurun_out/${T}_profile_bench.log 2>&1
 cat gpurun_out/${T}_final_suites.txt
 fi
