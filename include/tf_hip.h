@@ -24,7 +24,7 @@
  *
  * There is NO CPU fallback: without a usable HIP device every call returns TF_ERR_NO_DEVICE.
  *
- * Return value: 0 on success, otherwise one of the codes below.  Codes 1-3 are the reference's
+ * Return value: 0 on success, otherwise one of the codes below.  Codes 1-3, 11 and 19-21 are the reference's
  * MerkleTreeError variants (util_types/merkle_tree.rs:933-965); codes 4-6 replace panics.
  * No C++ exception leaves the library: every status-returning entry point catches what its host-side C++ (tables, caches,
  * worker threads) may throw and returns TF_ERR_OUT_OF_MEMORY (a failed host allocation) or TF_ERR_INTERNAL, with the
@@ -59,7 +59,10 @@ enum tf_status {
     TF_ERR_DIVISION_BY_ZERO = 15,          /* naive_divide panic: "divisor should be non-zero"  math/polynomial.rs:556-559 */
     TF_ERR_DIVISION_NOT_CLEAN = 16,        /* clean_divide panic: the quotient does not come back to the base field  math/polynomial.rs:2374, :2410 */
     TF_ERR_INVALID_ARGUMENT = 17,          /* an index / count argument of a host-logic helper (tf_shard_range, tf_merkle_subtree_layer_range) is out of range */
-    TF_ERR_INTERNAL = 18                   /* a C++ exception other than an allocation failure was caught at the ABI (csrc/tf_guard.h); see tf_last_error() */
+    TF_ERR_INTERNAL = 18,                  /* a C++ exception other than an allocation failure was caught at the ABI (csrc/tf_guard.h); see tf_last_error() */
+    TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH = 19,  /* MerkleTreeError::AuthenticationStructureLengthMismatch  merkle_tree.rs:933-965 (raised :910-912) */
+    TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH = 20,   /* MerkleTreeError::RepeatedLeafDigestMismatch  merkle_tree.rs:933-965 (raised :921-923) */
+    TF_ERR_ROOT_MISMATCH = 21                    /* MerkleTreeError::RootMismatch  merkle_tree.rs:933-965 (raised :740-742) */
 };
 
 /* Human-readable name of a status code. */
@@ -396,6 +399,38 @@ int tf_merkle_from_rows_dev(const uint64_t *d_rows, size_t row_len, size_t n_row
 int tf_merkle_auth_structure_indices(size_t num_leafs, const uint64_t *leaf_indices, size_t k, uint64_t *out_indices, size_t capacity, size_t *out_count);
 int tf_merkle_authentication_structure_dev(const uint64_t *d_nodes, size_t num_leafs, const uint64_t *leaf_indices, size_t k,
                                            uint64_t *out_digests, size_t capacity_digests, size_t *out_count, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Inclusion proofs, batched.   replaces  MerkleTreeInclusionProof::try_verify / verify   util_types/merkle_tree.rs:727-748
+ *                                        MerkleTreeInclusionProof::into_authentication_paths :773-777 (PartialMerkleTree :779-931)
+ * A proof is (tree_height, indexed_leafs, authentication_structure), in CSR layout over n_proofs proofs:
+ *   proof p owns the leafs leaf_offsets[p] .. leaf_offsets[p + 1] - 1 (leaf_indices: one word each; leaf_digests: 5 words each, at
+ *   5 * index) and the structure digests auth_offsets[p] .. auth_offsets[p + 1] - 1 (auth_digests: 5 words each); both offset arrays
+ *   have n_proofs + 1 entries and never decrease.  expected_roots: 5 words per proof.
+ * statuses[p] receives the reference's verdict for proof p: TF_OK, TF_ERR_TREE_TOO_HIGH (height >= 64), TF_ERR_LEAF_INDEX_INVALID,
+ * TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH, TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH or (verify only) TF_ERR_ROOT_MISMATCH, decided in the
+ * reference's order.  A proof with neither leafs nor structure verifies whatever its height and root (:737-739); the paths call has
+ * no such shortcut (:773-777).
+ * paths_out: proof after proof, each k_p x h_p digests, leaf-major in the order of indexed_leafs, duplicates included (entry e, level
+ * l = the sibling of leaf e's ancestor at height l, bottom first); proof p starts at digest sum_(q < p, h_q < 64) k_q * h_q.  The
+ * slot of a proof whose status is not TF_OK holds unspecified words.
+ * The return value concerns the call alone: TF_ERR_NULL_POINTER, TF_ERR_INVALID_ARGUMENT (decreasing offsets), TF_ERR_NO_DEVICE,
+ * TF_ERR_OUT_OF_MEMORY (device work space: proofs of more than 256 leafs keep their levels in device memory, about 200 bytes per leaf).
+ * _dev: tree_heights and the offsets are HOST arrays (the host reads them, O(n_proofs) work); leaf indices, digests, roots, paths and
+ * statuses are device memory.  Nothing is copied back and `stream` is not synchronised: d_statuses is valid once the stream has
+ * reached the call. */
+int tf_merkle_verify_proofs(const uint32_t *tree_heights, size_t n_proofs, const uint64_t *leaf_offsets, const uint64_t *leaf_indices,
+                            const uint64_t *leaf_digests, const uint64_t *auth_offsets, const uint64_t *auth_digests,
+                            const uint64_t *expected_roots, int *statuses);
+int tf_merkle_verify_proofs_dev(const uint32_t *tree_heights, size_t n_proofs, const uint64_t *leaf_offsets, const uint64_t *d_leaf_indices,
+                                const uint64_t *d_leaf_digests, const uint64_t *auth_offsets, const uint64_t *d_auth_digests,
+                                const uint64_t *d_expected_roots, int *d_statuses, void *stream);
+int tf_merkle_authentication_paths(const uint32_t *tree_heights, size_t n_proofs, const uint64_t *leaf_offsets, const uint64_t *leaf_indices,
+                                   const uint64_t *leaf_digests, const uint64_t *auth_offsets, const uint64_t *auth_digests,
+                                   uint64_t *paths_out, int *statuses);
+int tf_merkle_authentication_paths_dev(const uint32_t *tree_heights, size_t n_proofs, const uint64_t *leaf_offsets,
+                                       const uint64_t *d_leaf_indices, const uint64_t *d_leaf_digests, const uint64_t *auth_offsets,
+                                       const uint64_t *d_auth_digests, uint64_t *d_paths_out, int *d_statuses, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the

@@ -27,7 +27,7 @@ from . import _lib
 
 __all__ = [
     "P", "BFieldElement", "ntt", "intt", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
-    "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "set_device", "get_device", "shard_range",
+    "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "set_device", "get_device", "shard_range",
 ]
 
 P = 0xFFFFFFFF00000001  # BFieldElement::P, math/b_field_element.rs:225
@@ -58,7 +58,8 @@ class NttPanic(TwentyFirstError):
 class MerkleTreeError(TwentyFirstError):
     """util_types/merkle_tree.rs:933-965; .variant is the Rust variant name."""
 
-    VARIANTS = {1: "TooFewLeafs", 2: "IncorrectNumberOfLeafs", 3: "TreeTooHigh", 11: "LeafIndexInvalid"}
+    VARIANTS = {1: "TooFewLeafs", 2: "IncorrectNumberOfLeafs", 3: "TreeTooHigh", 11: "LeafIndexInvalid",
+                19: "AuthenticationStructureLengthMismatch", 20: "RepeatedLeafDigestMismatch", 21: "RootMismatch"}
 
     def __init__(self, code: int, where: str = ""):
         super().__init__(code, where)
@@ -68,7 +69,7 @@ class MerkleTreeError(TwentyFirstError):
 def _check(rc: int, where: str):
     if rc == 0:
         return
-    if rc in (1, 2, 3, 11):
+    if rc in (1, 2, 3, 11, 19, 20, 21):
         raise MerkleTreeError(rc, where)
     if rc in (4, 5, 6, 12, 14, 15, 16):
         raise NttPanic(rc, where)
@@ -758,6 +759,100 @@ class MerkleTree:
     def leaf(self, i: int):  # :654-661
         n = self.num_leafs()
         return self.nodes[n + i] if 0 <= i < n else None
+
+    def indexed_leafs(self, indices) -> list:  # :665-674
+        """[(leaf index, digest)] for the given indices; an index outside the tree raises LeafIndexInvalid."""
+        out = []
+        for i in np.asarray(indices, dtype=np.uint64).reshape(-1).tolist():
+            leaf = self.leaf(int(i))
+            if leaf is None:
+                raise MerkleTreeError(11, "MerkleTree::indexed_leafs")
+            out.append((int(i), leaf.copy()))
+        return out
+
+    def inclusion_proof_for_leaf_indices(self, indices) -> "MerkleTreeInclusionProof":  # :684-709
+        indexed = self.indexed_leafs(indices)
+        return MerkleTreeInclusionProof(
+            self.height(),
+            [i for i, _ in indexed],
+            np.array([d for _, d in indexed], dtype=np.uint64).reshape(-1, 5),
+            self.authentication_structure(indices),
+        )
+
+
+class MerkleTreeInclusionProof:
+    """util_types/merkle_tree.rs:90-113, :712-777: (tree_height, indexed_leafs, authentication_structure), verified on the GPU.
+
+    leaf_indices: (k,) uint64; leaf_digests: (k, 5) raw words, the digest of leaf_indices[i] in row i (duplicates allowed);
+    authentication_structure: (a, 5) raw words.  Batches of proofs go to the device in one call (verify_batch / try_verify_batch)."""
+
+    def __init__(self, tree_height: int, leaf_indices, leaf_digests, authentication_structure):
+        if not 0 <= int(tree_height) < (1 << 32):
+            raise ValueError("tree_height is a u32")
+        self.tree_height = int(tree_height)
+        self.leaf_indices = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+        self.leaf_digests = np.ascontiguousarray(leaf_digests, dtype=np.uint64).reshape(-1, 5)
+        self.authentication_structure = np.ascontiguousarray(authentication_structure, dtype=np.uint64).reshape(-1, 5)
+        if self.leaf_digests.shape[0] != self.leaf_indices.size:
+            raise ValueError("one digest per leaf index")
+
+    @staticmethod
+    def _pack(proofs):
+        heights = np.array([p.tree_height for p in proofs], dtype=np.uint32)
+        leaf_off = np.zeros(len(proofs) + 1, dtype=np.uint64)
+        auth_off = np.zeros(len(proofs) + 1, dtype=np.uint64)
+        leaf_off[1:] = np.cumsum([p.leaf_indices.size for p in proofs])
+        auth_off[1:] = np.cumsum([p.authentication_structure.shape[0] for p in proofs])
+        cat = lambda xs: np.ascontiguousarray(np.concatenate(xs).reshape(-1) if xs else np.empty(0), dtype=np.uint64)  # noqa: E731
+        return (heights, leaf_off, cat([p.leaf_indices for p in proofs]), cat([p.leaf_digests for p in proofs]), auth_off,
+                cat([p.authentication_structure for p in proofs]))
+
+    @staticmethod
+    def try_verify_batch(proofs, roots) -> np.ndarray:
+        """Status of try_verify for every proof (int32; 0 = Ok, else a MerkleTreeError code: MerkleTreeError.VARIANTS)."""
+        proofs = list(proofs)
+        roots = np.ascontiguousarray(roots, dtype=np.uint64).reshape(-1)
+        if roots.size != 5 * len(proofs):
+            raise ValueError("one root (5 words) per proof")
+        h, lo, li, ld, ao, ad = MerkleTreeInclusionProof._pack(proofs)
+        st = np.zeros(max(len(proofs), 1), dtype=np.int32)
+        _check(lib().tf_merkle_verify_proofs(_ptr(h), len(proofs), _ptr(lo), _ptr(li), _ptr(ld), _ptr(ao), _ptr(ad), _ptr(roots), _ptr(st)),
+               "MerkleTreeInclusionProof::verify")
+        return st[: len(proofs)]
+
+    @staticmethod
+    def verify_batch(proofs, roots) -> np.ndarray:
+        return MerkleTreeInclusionProof.try_verify_batch(proofs, roots) == 0
+
+    def try_verify(self, root) -> None:  # :736-748
+        st = int(self.try_verify_batch([self], root)[0])
+        if st:
+            raise MerkleTreeError(st, "MerkleTreeInclusionProof::try_verify")
+
+    def verify(self, root) -> bool:  # :727-729
+        return bool(self.verify_batch([self], root)[0])
+
+    @staticmethod
+    def authentication_paths_batch(proofs):
+        """(paths, statuses): paths[p] = the (k_p, h_p, 5) authentication paths of proof p (None where statuses[p] != 0)."""
+        proofs = list(proofs)
+        h, lo, li, ld, ao, ad = MerkleTreeInclusionProof._pack(proofs)
+        sizes = [p.leaf_indices.size * p.tree_height if p.tree_height < 64 else 0 for p in proofs]
+        out = np.empty(max(5 * sum(sizes), 1), dtype=np.uint64)
+        st = np.zeros(max(len(proofs), 1), dtype=np.int32)
+        _check(lib().tf_merkle_authentication_paths(_ptr(h), len(proofs), _ptr(lo), _ptr(li), _ptr(ld), _ptr(ao), _ptr(ad), _ptr(out), _ptr(st)),
+               "MerkleTreeInclusionProof::into_authentication_paths")
+        paths, off = [], 0
+        for p, n, s in zip(proofs, sizes, st.tolist()):
+            paths.append(out[5 * off: 5 * (off + n)].reshape(p.leaf_indices.size, p.tree_height, 5).copy() if s == 0 else None)
+            off += n
+        return paths, st[: len(proofs)]
+
+    def into_authentication_paths(self) -> np.ndarray:  # :773-777
+        paths, st = self.authentication_paths_batch([self])
+        if st[0]:
+            raise MerkleTreeError(int(st[0]), "MerkleTreeInclusionProof::into_authentication_paths")
+        return paths[0]
 
 
 from . import device  # noqa: E402  (torch device-pointer API)

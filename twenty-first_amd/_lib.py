@@ -127,6 +127,10 @@ SIGNATURES = {
     "tf_merkle_from_rows_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp]),
     "tf_merkle_auth_structure_indices": (C.c_int, [_sz, _vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "tf_merkle_authentication_structure_dev": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(C.c_size_t), _vp]),
+    "tf_merkle_verify_proofs": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tf_merkle_verify_proofs_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tf_merkle_authentication_paths": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tf_merkle_authentication_paths_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_ntt_launch_count": (C.c_int, [_sz, _sz, C.c_int]),
     "tf_ntt_plan": (C.c_int, [_sz, C.c_int, C.POINTER(C.c_int)]),
     "tf_batch_eval_plan": (C.c_int, [_sz, _sz, _sz, C.c_int]),

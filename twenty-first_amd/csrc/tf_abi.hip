@@ -113,6 +113,40 @@ int host_roundtrip(const uint64_t* in1, size_t w1, const uint64_t* in2, size_t w
     return sync(s);
 }
 
+// Host flavour of the inclusion-proof calls (tf_proof.hip): uploads the ranges the offsets use, runs the batch, copies the verdicts
+// (and the paths) back.
+int merkle_proofs_host(const uint32_t* heights, size_t n, const uint64_t* loff, const uint64_t* idx, const uint64_t* dig, const uint64_t* aoff,
+                       const uint64_t* auth, const uint64_t* roots, int* statuses, uint64_t* paths_out, bool paths) {
+    if (n == 0) return TF_OK;
+    if (!heights || !loff || !aoff || !statuses) return TF_ERR_NULL_POINTER;
+    size_t path_words = 0;
+    for (size_t p = 0; p < n; ++p) {
+        if (loff[p + 1] < loff[p] || aoff[p + 1] < aoff[p]) return TF_ERR_INVALID_ARGUMENT;
+        if (heights[p] < 64) path_words += (loff[p + 1] - loff[p]) * heights[p];
+    }
+    const size_t nk = loff[n] - loff[0], na = aoff[n] - aoff[0];
+    if ((nk && (!idx || !dig)) || (na && !auth) || (!paths && !roots) || (paths && path_words && !paths_out)) return TF_ERR_NULL_POINTER;
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    hipStream_t s = host_stream();
+    DevBuf di(s), dd(s), da(s), dr(s), dst(s), dp(s);
+    TRY(di.alloc(nk));
+    TRY(dd.alloc(5 * nk));
+    TRY(da.alloc(5 * na));
+    TRY(dr.alloc(paths ? 0 : 5 * n));
+    TRY(dst.alloc((n + 1) / 2));
+    TRY(dp.alloc(paths ? 5 * path_words : 0));
+    if (nk) {
+        TRY(h2d(di.p, idx + loff[0], nk, s));
+        TRY(h2d(dd.p, dig + 5 * loff[0], 5 * nk, s));
+    }
+    if (na) TRY(h2d(da.p, auth + 5 * aoff[0], 5 * na, s));
+    if (!paths) TRY(h2d(dr.p, roots, 5 * n, s));
+    TRY(merkle_proofs_dev(heights, n, loff, di.p, dd.p, aoff, da.p, dr.p, reinterpret_cast<int*>(dst.p), dp.p, paths, loff[0], aoff[0], s));
+    HIPCHK(hipMemcpyAsync(statuses, dst.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (paths) TRY(d2h(paths_out, dp.p, 5 * path_words, s));
+    return sync(s);
+}
 
 }  // namespace tfi
 
@@ -143,12 +177,15 @@ const char* tf_status_string(int status) {
         case TF_ERR_DIVISION_NOT_CLEAN: return "TF_ERR_DIVISION_NOT_CLEAN";
         case TF_ERR_INVALID_ARGUMENT: return "TF_ERR_INVALID_ARGUMENT";
         case TF_ERR_INTERNAL: return "TF_ERR_INTERNAL";
+        case TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH: return "TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH";
+        case TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH: return "TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH";
+        case TF_ERR_ROOT_MISMATCH: return "TF_ERR_ROOT_MISMATCH";
         default: return "TF_ERR_UNKNOWN";
     }
 }
 
 const char* tf_last_error(void) { return t_last_error.c_str(); }
-int tf_version(void) { return 1001; }
+int tf_version(void) { return 1002; }
 #ifndef TF_SOURCE_HASH
 #define TF_SOURCE_HASH "unknown"
 #endif
@@ -893,6 +930,31 @@ int tf_merkle_authentication_structure_dev(const uint64_t* d_nodes, size_t num_l
     TRY(gather_digests_dev(d_nodes, reinterpret_cast<const unsigned long long*>(didx.p), idx.size(), dout.p, s));
     TRY(d2h(out_digests, dout.p, idx.size() * 5, s));
     return sync(s);
+} TF_ABI_CATCH
+
+int tf_merkle_verify_proofs(const uint32_t* tree_heights, size_t n_proofs, const uint64_t* leaf_offsets, const uint64_t* leaf_indices,
+                            const uint64_t* leaf_digests, const uint64_t* auth_offsets, const uint64_t* auth_digests,
+                            const uint64_t* expected_roots, int* statuses) try {
+    return merkle_proofs_host(tree_heights, n_proofs, leaf_offsets, leaf_indices, leaf_digests, auth_offsets, auth_digests, expected_roots,
+                              statuses, nullptr, false);
+} TF_ABI_CATCH
+int tf_merkle_verify_proofs_dev(const uint32_t* tree_heights, size_t n_proofs, const uint64_t* leaf_offsets, const uint64_t* d_leaf_indices,
+                                const uint64_t* d_leaf_digests, const uint64_t* auth_offsets, const uint64_t* d_auth_digests,
+                                const uint64_t* d_expected_roots, int* d_statuses, void* stream) try {
+    return merkle_proofs_dev(tree_heights, n_proofs, leaf_offsets, d_leaf_indices, d_leaf_digests, auth_offsets, d_auth_digests, d_expected_roots,
+                             d_statuses, nullptr, false, 0, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_merkle_authentication_paths(const uint32_t* tree_heights, size_t n_proofs, const uint64_t* leaf_offsets, const uint64_t* leaf_indices,
+                                   const uint64_t* leaf_digests, const uint64_t* auth_offsets, const uint64_t* auth_digests,
+                                   uint64_t* paths_out, int* statuses) try {
+    return merkle_proofs_host(tree_heights, n_proofs, leaf_offsets, leaf_indices, leaf_digests, auth_offsets, auth_digests, nullptr, statuses,
+                              paths_out, true);
+} TF_ABI_CATCH
+int tf_merkle_authentication_paths_dev(const uint32_t* tree_heights, size_t n_proofs, const uint64_t* leaf_offsets,
+                                       const uint64_t* d_leaf_indices, const uint64_t* d_leaf_digests, const uint64_t* auth_offsets,
+                                       const uint64_t* d_auth_digests, uint64_t* d_paths_out, int* d_statuses, void* stream) try {
+    return merkle_proofs_dev(tree_heights, n_proofs, leaf_offsets, d_leaf_indices, d_leaf_digests, auth_offsets, d_auth_digests, nullptr,
+                             d_statuses, d_paths_out, true, 0, 0, static_cast<hipStream_t>(stream));
 } TF_ABI_CATCH
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 //   tf_poly.hip   the callers on either side of the path, SURVEY 8(f) (poly_kernels.h)
 //   tf_abi.hip    host-pointer wrappers and the extern "C" entry points
 //   tf_multi.hip  one host-resident batch over several GPUs (tf_*_multi), device selection
+//   tf_proof.hip  batched verification of Merkle inclusion proofs (proof_kernels.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -156,6 +157,14 @@ int merkle_root_dev(const u64* d_leaves, size_t n, u64* d_root, size_t batch, vo
 int merkle_from_rows_dev(const u64* d_rows, size_t row_len, size_t n_rows, u64* d_nodes, size_t batch, void* stream);
 int merkle_from_columns_dev(const u64* d_table, size_t n_rows, size_t n_cols, int width, size_t col_stride, u64* d_nodes, size_t batch, void* stream);
 int gather_digests_dev(const u64* d_nodes, const unsigned long long* d_idx, size_t count, u64* d_out, hipStream_t s);
+extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (canonical values; tf_tip5.hip)
+
+// ------------------------------------------------------------------------------------ tf_proof.hip
+// batched MerkleTreeInclusionProof::try_verify (paths = false) / into_authentication_paths (paths = true); the leaf and structure
+// arrays are indexed from leaf_base / auth_base (the host flavours upload only [offsets[0], offsets[n]))
+int merkle_proofs_dev(const uint32_t* heights, size_t n, const uint64_t* leaf_offsets, const u64* d_leaf_indices, const u64* d_leaf_digests,
+                      const uint64_t* auth_offsets, const u64* d_auth, const u64* d_roots, int* d_statuses, u64* d_paths, bool paths,
+                      uint64_t leaf_base, uint64_t auth_base, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ tf_poly.hip
 extern std::atomic<int> g_batch_eval_route;

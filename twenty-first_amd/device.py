@@ -120,6 +120,72 @@ def merkle_root(leaves, n_leaves: int, root_out, batch: int = 1, stream=None) ->
     _chk(_lib.lib().tf_merkle_root_dev(_p(leaves), n_leaves, _p(root_out), batch, _stream(stream)), "MerkleTree::par_frugal_root")
 
 
+def _proof_layout(tree_heights, leaf_offsets, auth_offsets):
+    """Host arrays of a batch of inclusion proofs (include/tf_hip.h, "Inclusion proofs"): heights as u32, CSR offsets as u64."""
+    import numpy as np
+
+    h = np.ascontiguousarray(tree_heights, dtype=np.uint32).reshape(-1)
+    lo = np.ascontiguousarray(leaf_offsets, dtype=np.uint64).reshape(-1)
+    ao = np.ascontiguousarray(auth_offsets, dtype=np.uint64).reshape(-1)
+    _need(lo.size == h.size + 1 and ao.size == h.size + 1, "leaf_offsets and auth_offsets need n_proofs + 1 entries")
+    return h, lo, ao
+
+
+def _host(a):
+    return C.c_void_p(a.ctypes.data) if a.size else C.c_void_p(0)
+
+
+def _status_tensor(statuses, n: int):
+    import torch
+
+    _need(isinstance(statuses, torch.Tensor) and statuses.is_cuda and statuses.is_contiguous() and statuses.dtype == torch.int32
+          and statuses.numel() >= n, "statuses must be a contiguous CUDA int32 tensor of n_proofs entries")
+    return statuses
+
+
+def verify_inclusion_proofs(tree_heights, leaf_offsets, leaf_indices, leaf_digests, auth_offsets, auth_digests, expected_roots, statuses,
+                            stream=None) -> None:
+    """MerkleTreeInclusionProof::try_verify of a batch (util_types/merkle_tree.rs:736-748): statuses[p] (device int32) receives proof p's
+    verdict (0 = Ok, else a MerkleTreeError code).  tree_heights and the offsets are host arrays; leaf_indices (k words),
+    leaf_digests (5 k), auth_digests (5 a) and expected_roots (5 n) are device tensors.  Nothing is synchronised."""
+    h, lo, ao = _proof_layout(tree_heights, leaf_offsets, auth_offsets)
+    n = h.size
+    leaf_indices, leaf_digests = _t(leaf_indices, "leaf_indices"), _t(leaf_digests, "leaf_digests")
+    auth_digests, expected_roots = _t(auth_digests, "auth_digests"), _t(expected_roots, "expected_roots")
+    statuses = _status_tensor(statuses, n)
+    k, a = int(lo[-1]) if n else 0, int(ao[-1]) if n else 0
+    _need(leaf_indices.numel() >= k and leaf_digests.numel() >= 5 * k and auth_digests.numel() >= 5 * a and expected_roots.numel() >= 5 * n,
+          "buffer sizes do not match the offsets")
+    _chk(_lib.lib().tf_merkle_verify_proofs_dev(_host(h), n, _host(lo), _p(leaf_indices), _p(leaf_digests), _host(ao), _p(auth_digests),
+                                                _p(expected_roots), _p(statuses), _stream(stream)), "MerkleTreeInclusionProof::verify")
+
+
+def authentication_path_words(tree_heights, leaf_offsets) -> int:
+    """Words of paths_out for a batch: 5 k_p h_p per proof of height < 64."""
+    import numpy as np
+
+    h = np.asarray(tree_heights, dtype=np.uint64).reshape(-1)
+    k = np.diff(np.asarray(leaf_offsets, dtype=np.uint64).reshape(-1))
+    return 5 * int(np.sum(np.where(h < 64, k * h, 0)))
+
+
+def authentication_paths(tree_heights, leaf_offsets, leaf_indices, leaf_digests, auth_offsets, auth_digests, paths_out, statuses,
+                         stream=None) -> None:
+    """MerkleTreeInclusionProof::into_authentication_paths of a batch (:773-777): paths_out (device, authentication_path_words words)
+    receives proof after proof k_p x h_p digests, leaf-major; statuses as verify_inclusion_proofs.  Nothing is synchronised."""
+    h, lo, ao = _proof_layout(tree_heights, leaf_offsets, auth_offsets)
+    n = h.size
+    leaf_indices, leaf_digests = _t(leaf_indices, "leaf_indices"), _t(leaf_digests, "leaf_digests")
+    auth_digests, paths_out = _t(auth_digests, "auth_digests"), _t(paths_out, "paths_out")
+    statuses = _status_tensor(statuses, n)
+    k, a = int(lo[-1]) if n else 0, int(ao[-1]) if n else 0
+    _need(leaf_indices.numel() >= k and leaf_digests.numel() >= 5 * k and auth_digests.numel() >= 5 * a
+          and paths_out.numel() >= authentication_path_words(h, lo), "buffer sizes do not match the offsets")
+    _chk(_lib.lib().tf_merkle_authentication_paths_dev(_host(h), n, _host(lo), _p(leaf_indices), _p(leaf_digests), _host(ao), _p(auth_digests),
+                                                       _p(paths_out), _p(statuses), _stream(stream)),
+         "MerkleTreeInclusionProof::into_authentication_paths")
+
+
 # ---- SURVEY 8(f1)-(f3): the callers on either side of the path, kept in HBM --------------------------------
 
 def coset_interpolate(values, n: int, offset_raw: int, out, batch: int = 1, width: int = 1, stream=None) -> None:

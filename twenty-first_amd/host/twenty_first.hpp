@@ -90,13 +90,22 @@ struct NttPanic : BackendError {
 };
 // util_types/merkle_tree.rs:933-965
 struct MerkleTreeError : BackendError {
-    enum Variant { TooFewLeafs = 1, IncorrectNumberOfLeafs = 2, TreeTooHigh = 3, LeafIndexInvalid = 11 } variant;
+    enum Variant {
+        TooFewLeafs = 1,
+        IncorrectNumberOfLeafs = 2,
+        TreeTooHigh = 3,
+        LeafIndexInvalid = 11,
+        AuthenticationStructureLengthMismatch = 19,
+        RepeatedLeafDigestMismatch = 20,
+        RootMismatch = 21
+    } variant;
     MerkleTreeError(int c, const std::string& where) : BackendError(c, where), variant((Variant)c) {}
 };
 
 inline void check(int rc, const char* where) {
     if (rc == TF_OK) return;
-    if ((rc >= 1 && rc <= 3) || rc == TF_ERR_LEAF_INDEX_INVALID) throw MerkleTreeError(rc, where);  // merkle_tree.rs:933-965
+    if ((rc >= 1 && rc <= 3) || rc == TF_ERR_LEAF_INDEX_INVALID || (rc >= TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH && rc <= TF_ERR_ROOT_MISMATCH))
+        throw MerkleTreeError(rc, where);  // merkle_tree.rs:933-965
     if ((rc >= 4 && rc <= 6) || rc == TF_ERR_INVERSE_OF_ZERO || (rc >= TF_ERR_EMPTY_DOMAIN && rc <= TF_ERR_DIVISION_NOT_CLEAN)) throw NttPanic(rc, where);  // the reference panics here
     throw BackendError(rc, where);
 }
@@ -423,6 +432,92 @@ struct MerkleTree {
     unsigned height() const { unsigned h = 0; for (size_t n = num_leafs(); n > 1; n >>= 1) ++h; return h; }  // :633-636
     const Digest* node(size_t i) const { return i < nodes.size() ? &nodes[i] : nullptr; }  // :638-645
     const Digest* leaf(size_t i) const { return i < num_leafs() ? &nodes[num_leafs() + i] : nullptr; }  // :654-661
+    std::vector<std::pair<size_t, Digest>> indexed_leafs(const std::vector<size_t>& indices) const {  // :665-674
+        std::vector<std::pair<size_t, Digest>> out;
+        for (size_t i : indices) {
+            const Digest* d = leaf(i);
+            if (!d) throw MerkleTreeError(TF_ERR_LEAF_INDEX_INVALID, "MerkleTree::indexed_leafs");
+            out.emplace_back(i, *d);
+        }
+        return out;
+    }
+    struct MerkleTreeInclusionProof inclusion_proof_for_leaf_indices(const std::vector<size_t>& indices) const;  // :684-709
 };
+
+// ---- MerkleTreeInclusionProof (util_types/merkle_tree.rs:90-113, :712-777), verified on the GPU in batches ----------------------
+struct MerkleTreeInclusionProof {
+    uint32_t tree_height = 0;
+    std::vector<std::pair<size_t, Digest>> indexed_leafs;
+    std::vector<Digest> authentication_structure;
+
+    // statuses of try_verify for every proof, one device call (0 = Ok, else a MerkleTreeError code)
+    static std::vector<int> try_verify_statuses(const std::vector<MerkleTreeInclusionProof>& proofs, const std::vector<Digest>& roots) {
+        if (roots.size() != proofs.size()) throw std::invalid_argument("one root per proof");
+        Packed p(proofs);
+        std::vector<int> st(proofs.size());
+        check(tf_merkle_verify_proofs(p.heights.data(), proofs.size(), p.leaf_off.data(), p.idx.data(), p.dig(), p.auth_off.data(), p.auth(),
+                                      reinterpret_cast<const uint64_t*>(roots.data()), st.data()),
+              "MerkleTreeInclusionProof::verify");
+        return st;
+    }
+    static std::vector<bool> verify_batch(const std::vector<MerkleTreeInclusionProof>& proofs, const std::vector<Digest>& roots) {
+        std::vector<int> st = try_verify_statuses(proofs, roots);
+        return flip_ok(st);
+    }
+    void try_verify(const Digest& root) const {  // :736-748
+        const int st = try_verify_statuses({*this}, {root})[0];
+        if (st) throw MerkleTreeError(st, "MerkleTreeInclusionProof::try_verify");
+    }
+    bool verify(const Digest& root) const { return try_verify_statuses({*this}, {root})[0] == TF_OK; }  // :727-729
+    // :773-777: for every entry of indexed_leafs (duplicates included) its tree_height siblings, bottom first
+    std::vector<std::vector<Digest>> into_authentication_paths() const {
+        Packed p({*this});
+        const size_t h = tree_height < 64 ? tree_height : 0, k = indexed_leafs.size();
+        std::vector<Digest> out(k * h + 1);
+        int st = 0;
+        check(tf_merkle_authentication_paths(p.heights.data(), 1, p.leaf_off.data(), p.idx.data(), p.dig(), p.auth_off.data(), p.auth(),
+                                             reinterpret_cast<uint64_t*>(out.data()), &st),
+              "MerkleTreeInclusionProof::into_authentication_paths");
+        if (st) throw MerkleTreeError(st, "MerkleTreeInclusionProof::into_authentication_paths");
+        std::vector<std::vector<Digest>> paths(k);
+        for (size_t e = 0; e < k; ++e) paths[e].assign(out.begin() + (long)(e * h), out.begin() + (long)((e + 1) * h));
+        return paths;
+    }
+
+  private:
+    static std::vector<bool> flip_ok(const std::vector<int>& st) {
+        std::vector<bool> ok(st.size());
+        for (size_t i = 0; i < st.size(); ++i) ok[i] = st[i] == TF_OK;
+        return ok;
+    }
+    // the CSR layout of include/tf_hip.h ("Inclusion proofs")
+    struct Packed {
+        std::vector<uint32_t> heights;
+        std::vector<uint64_t> leaf_off{0}, auth_off{0}, idx;
+        std::vector<Digest> digs, auths;
+        explicit Packed(const std::vector<MerkleTreeInclusionProof>& proofs) {
+            for (const auto& q : proofs) {
+                heights.push_back(q.tree_height);
+                for (const auto& [i, d] : q.indexed_leafs) {
+                    idx.push_back(i);
+                    digs.push_back(d);
+                }
+                auths.insert(auths.end(), q.authentication_structure.begin(), q.authentication_structure.end());
+                leaf_off.push_back(idx.size());
+                auth_off.push_back(auths.size());
+            }
+        }
+        const uint64_t* dig() const { return reinterpret_cast<const uint64_t*>(digs.data()); }
+        const uint64_t* auth() const { return reinterpret_cast<const uint64_t*>(auths.data()); }
+    };
+};
+
+inline MerkleTreeInclusionProof MerkleTree::inclusion_proof_for_leaf_indices(const std::vector<size_t>& indices) const {
+    MerkleTreeInclusionProof p;
+    p.tree_height = height();
+    p.indexed_leafs = indexed_leafs(indices);
+    p.authentication_structure = authentication_structure(indices);
+    return p;
+}
 
 }  // namespace twenty_first
