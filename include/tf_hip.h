@@ -58,7 +58,8 @@ enum tf_status {
     TF_ERR_EMPTY_DOMAIN = 14,              /* interpolate panic: "interpolation must happen through more than zero points"  math/polynomial.rs:1503-1506 */
     TF_ERR_DIVISION_BY_ZERO = 15,          /* naive_divide panic: "divisor should be non-zero"  math/polynomial.rs:556-559 */
     TF_ERR_DIVISION_NOT_CLEAN = 16,        /* clean_divide panic: the quotient does not come back to the base field  math/polynomial.rs:2374, :2410 */
-    TF_ERR_INVALID_ARGUMENT = 17,          /* an index / count argument of a host-logic helper (tf_shard_range, tf_merkle_subtree_layer_range) is out of range */
+    TF_ERR_INVALID_ARGUMENT = 17,          /* an index / count argument of a host-logic helper (tf_shard_range, tf_merkle_subtree_layer_range) is out of range;
+                                            * a divisor / power series whose last coefficient is zero (tf_poly_divide_*, tf_poly_fps_inverse_newton_*) */
     TF_ERR_INTERNAL = 18,                  /* a C++ exception other than an allocation failure was caught at the ABI (csrc/tf_guard.h); see tf_last_error() */
     TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH = 19,  /* MerkleTreeError::AuthenticationStructureLengthMismatch  merkle_tree.rs:933-965 (raised :910-912) */
     TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH = 20,   /* MerkleTreeError::RepeatedLeafDigestMismatch  merkle_tree.rs:933-965 (raised :921-923) */
@@ -326,6 +327,45 @@ int tf_poly_clean_divide_bfe_dev(const uint64_t *d_a, size_t na, const uint64_t 
  * out: batch x (na - nb + 1) coefficients.  Any unclean row fails the call.  At most 65 535 dividends per call. */
 int tf_poly_clean_divide_many_bfe(const uint64_t *a, size_t na, size_t batch, const uint64_t *b, size_t nb, uint64_t *out);
 int tf_poly_clean_divide_many_bfe_dev(const uint64_t *d_a, size_t na, size_t batch, const uint64_t *d_b, size_t nb, uint64_t *d_out, void *stream);
+/* Polynomial::divide / naive_divide (math/polynomial.rs:539-600), Div / Rem (:2502-2524), reduce / fast_reduce (:989-1048).
+ * batch dividends of na coefficients each (packed; shorter ones zero padded) over ONE divisor of nb coefficients.
+ * Words: raw Montgomery words as everywhere; an XFieldElement is 3 words per coefficient.
+ * Divisor: normalised, b[nb-1] != 0 (clean_divide's contract).  nb == 0 -> TF_ERR_DIVISION_BY_ZERO (the reference's panic,
+ *   :556-559); b[nb-1] == 0 -> TF_ERR_INVALID_ARGUMENT (the host form returns it, the _dev form writes it to *d_status).
+ * Dividends need not be normalised: quotient and remainder are unique, trailing zeros only give zero coefficients at the top.
+ * Outputs, fixed length and zero padded at the top (the reference's Polynomial trims those zeros; its equality ignores them):
+ *   q: batch x max(na - nb + 1, 0) coefficients;  r: batch x (nb - 1) coefficients.
+ *   na < nb: the quotient is empty and r is the dividend, zero padded (the reference's (zero, self), :560-563).
+ *   nb == 1: q = a * lc^-1 and r is empty.
+ *   q or r may be NULL and is then not written (r alone is `reduce`); both NULL -> TF_ERR_NULL_POINTER.
+ * Limits: batch <= 65 535, na <= 2^30, nb <= 2^30; above them TF_ERR_LEN_TOO_LARGE.  Device work space: at most
+ *   (batch + 6) x next_power_of_two(2k - 1) elements, k = na - nb + 1 (na = 2^24 over BFieldElement or 2^23 over XFieldElement:
+ *   about 2 GiB / 5 GiB in one call); a failed allocation is TF_ERR_OUT_OF_MEMORY.
+ * Construction (csrc/divide_kernels.h): h = rev(b)^-1 mod x^k by Newton doublings, every doubling with
+ *   transforms of order <= 2^12 (BFieldElement) / 2^9 (XFieldElement: the order whose three limb lines run without register
+ *   spills) in ONE launch, the larger ones on the library's transforms; rev(q) = (rev(a) mod x^k) h mod x^k with h's transform
+ *   shared by the batch; the remainder as (a - q b) mod (x^N - 1), N = next_power_of_two(nb - 1), one cyclic product of order N.
+ * _dev forms: device pointers; they never synchronise `stream`.  The data-dependent panic case (b[nb-1] == 0) goes to d_status
+ *   (one int of device memory, first non-zero code wins, as the _dev_async calls below); d_status == NULL -> TF_ERR_NULL_POINTER.
+ *   Everything checkable on the host (null pointers, nb == 0, sizes) is the return value, returned before any HIP call. */
+int tf_poly_divide_bfe(const uint64_t *a, size_t na, size_t batch, const uint64_t *b, size_t nb, uint64_t *q, uint64_t *r);
+int tf_poly_divide_xfe(const uint64_t *a, size_t na, size_t batch, const uint64_t *b, size_t nb, uint64_t *q, uint64_t *r);
+int tf_poly_divide_bfe_dev(const uint64_t *d_a, size_t na, size_t batch, const uint64_t *d_b, size_t nb,
+                           uint64_t *d_q, uint64_t *d_r, void *stream, int *d_status);
+int tf_poly_divide_xfe_dev(const uint64_t *d_a, size_t na, size_t batch, const uint64_t *d_b, size_t nb,
+                           uint64_t *d_q, uint64_t *d_r, void *stream, int *d_status);
+/* Polynomial::formal_power_series_inverse_newton (math/polynomial.rs:1281-1366): exactly the reference's return value, the R-th
+ * Newton iterate f_(i+1) = 2 f_i - f_i^2 g from f_0 = g(0)^-1, R = ilog2(next_power_of_two(precision)) (precision 0 counts as 1).
+ * The iterate is NOT truncated to x^precision (neither is the reference's): out receives (2^R - 1) d + 1 coefficients, d = nf - 1,
+ * or exactly one when d == 0 -- tf_poly_fps_inverse_newton_len(nf, precision) returns that count, or 0 when it exceeds 2^30 (or
+ * nf == 0).  Errors: nf == 0 or f[0] == 0 -> TF_ERR_INVERSE_OF_ZERO (the reference panics by index or in inverse());
+ * f[nf-1] == 0 -> TF_ERR_INVALID_ARGUMENT; a count above 2^30 -> TF_ERR_LEN_TOO_LARGE.  The _dev forms report the two
+ * data-dependent cases through d_status as tf_poly_divide_*_dev does and never synchronise. */
+int tf_poly_fps_inverse_newton_bfe(const uint64_t *f, size_t nf, size_t precision, uint64_t *out);
+int tf_poly_fps_inverse_newton_xfe(const uint64_t *f, size_t nf, size_t precision, uint64_t *out);
+int tf_poly_fps_inverse_newton_bfe_dev(const uint64_t *d_f, size_t nf, size_t precision, uint64_t *d_out, void *stream, int *d_status);
+int tf_poly_fps_inverse_newton_xfe_dev(const uint64_t *d_f, size_t nf, size_t precision, uint64_t *d_out, void *stream, int *d_status);
+size_t tf_poly_fps_inverse_newton_len(size_t nf, size_t precision);
 /* ZerofierTree  math/zerofier_tree.rs (new_from_domain :66-87, zerofier :93-99) with Polynomial::divide_and_conquer_batch_evaluate
  * math/polynomial.rs:1882-1894: the tree of a domain built ONCE and kept in HBM (levels, the cached level transforms, the root,
  * the domain, and after the first interpolation the inverse weights), for callers that evaluate or interpolate on the same

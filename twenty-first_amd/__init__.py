@@ -269,6 +269,27 @@ def fast_square(a: np.ndarray, width: int = 1, batch: int = 1) -> np.ndarray:
     return out
 
 
+def poly_divide(dividends: np.ndarray, divisor: np.ndarray, width: int = 1, batch: int = 1, quotient: bool = True, remainder: bool = True):
+    """Polynomial::divide (math/polynomial.rs:539-600) of `batch` dividends (packed, na coefficients each) by ONE divisor: returns
+    (q, r) as batch x max(na - nb + 1, 0) and batch x (nb - 1) coefficients, zero padded at the top (None for an output not
+    asked for).  The divisor's leading zero coefficients are dropped first; a zero divisor panics (NttPanic code 15)."""
+    a = _words(np.ascontiguousarray(dividends, dtype=np.uint64).reshape(-1), "dividends")
+    b = _words(np.ascontiguousarray(divisor, dtype=np.uint64).reshape(-1), "divisor")
+    if width not in (1, 3) or a.size % (width * max(batch, 1)) or b.size % width:
+        raise ValueError("dividends / divisor must hold whole elements of `width` words, batch dividends of equal length")
+    nb = b.size // width
+    while nb and not b[(nb - 1) * width:nb * width].any():
+        nb -= 1
+    na = a.size // (width * batch) if batch else 0
+    q = np.zeros(batch * max(na - nb + 1, 0) * width, dtype=np.uint64) if quotient else None
+    r = np.zeros(batch * max(nb - 1, 0) * width, dtype=np.uint64) if remainder else None
+    fn = lib().tf_poly_divide_bfe if width == 1 else lib().tf_poly_divide_xfe
+    pad = np.zeros(width, dtype=np.uint64)  # stands for an empty operand (never read) or an empty output (never written)
+    out = lambda x: None if x is None else _ptr(x if x.size else pad)  # noqa: E731
+    _check(fn(_ptr(a if a.size else pad), na, batch, _ptr(b if b.size else pad), nb, out(q), out(r)), "divide")
+    return q, r
+
+
 class Polynomial:
     """Coefficients low -> high degree (math/polynomial.rs:78-84); only the hot-path members."""
 
@@ -325,6 +346,38 @@ class Polynomial:
         out = np.zeros(max(na - nb + 1, 0), dtype=np.uint64)
         _check(lib().tf_poly_clean_divide_bfe(_ptr(self.coefficients), na, _ptr(divisor.coefficients), nb, _ptr(out)), "clean_divide")
         return Polynomial(out)
+
+    def divide(self, divisor: "Polynomial"):
+        """Polynomial::divide / naive_divide (math/polynomial.rs:539-600): (quotient, remainder).  A zero divisor panics (NttPanic
+        code 15, "divisor should be non-zero")."""
+        if self.width != divisor.width:
+            raise TypeError("dividend and divisor must be over the same field")
+        q, r = poly_divide(self.coefficients, divisor.coefficients, width=self.width)
+        return Polynomial(q, width=self.width), Polynomial(r, width=self.width)
+
+    def reduce(self, modulus: "Polynomial") -> "Polynomial":
+        """Polynomial::reduce / fast_reduce (math/polynomial.rs:989-1048): the remainder only (the quotient is not written)."""
+        if self.width != modulus.width:
+            raise TypeError("dividend and modulus must be over the same field")
+        _, r = poly_divide(self.coefficients, modulus.coefficients, width=self.width, quotient=False)
+        return Polynomial(r, width=self.width)
+
+    def __truediv__(self, other: "Polynomial") -> "Polynomial":  # Div (:2502-2512): the quotient
+        return self.divide(other)[0]
+
+    def __mod__(self, other: "Polynomial") -> "Polynomial":  # Rem (:2514-2524): the remainder
+        return self.reduce(other)
+
+    def formal_power_series_inverse_newton(self, precision: int) -> "Polynomial":
+        """math/polynomial.rs:1281-1366: the reference's return value, the untruncated Newton iterate ((2^R - 1) deg + 1
+        coefficients, R = ilog2(next_power_of_two(precision))).  A zero constant term panics (NttPanic code 12)."""
+        nf = self.coefficients.size // self.width
+        n = int(lib().tf_poly_fps_inverse_newton_len(nf, precision)) if nf else 0
+        out = np.zeros(max(n, 1) * self.width, dtype=np.uint64)
+        fn = lib().tf_poly_fps_inverse_newton_bfe if self.width == 1 else lib().tf_poly_fps_inverse_newton_xfe
+        c = self.coefficients if nf else np.zeros(self.width, dtype=np.uint64)
+        _check(fn(_ptr(c), nf, precision, _ptr(out)), "formal_power_series_inverse_newton")
+        return Polynomial(out[: n * self.width], width=self.width)
 
     @classmethod
     def zerofier(cls, roots: np.ndarray, width: int = 1) -> "Polynomial":

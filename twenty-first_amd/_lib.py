@@ -94,6 +94,15 @@ SIGNATURES = {
     "tf_poly_clean_divide_many_bfe": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp]),
     "tf_poly_clean_divide_many_bfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
     "tf_poly_clean_divide_bfe_dev": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _vp]),
+    "tf_poly_divide_bfe": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "tf_poly_divide_xfe": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "tf_poly_divide_bfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "tf_poly_divide_xfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "tf_poly_fps_inverse_newton_bfe": (C.c_int, [_vp, _sz, _sz, _vp]),
+    "tf_poly_fps_inverse_newton_xfe": (C.c_int, [_vp, _sz, _sz, _vp]),
+    "tf_poly_fps_inverse_newton_bfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp]),
+    "tf_poly_fps_inverse_newton_xfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp]),
+    "tf_poly_fps_inverse_newton_len": (_sz, [_sz, _sz]),
     "tf_zerofier_tree_new_bfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_xfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_bfe_dev": (C.c_int, [_vp, _sz, _vp, C.POINTER(C.c_void_p)]),

@@ -856,6 +856,38 @@ int tf_poly_clean_divide_bfe(const uint64_t* a, size_t na, const uint64_t* b, si
     if (!a || !b || !out) return TF_ERR_NULL_POINTER;
     return host_roundtrip(a, na, b, nb, out, na - nb + 1, [&](u64* da, u64* db, u64* o, hipStream_t s) { return clean_divide_dev(da, na, db, nb, o, s); });
 } TF_ABI_CATCH
+// Polynomial::divide / reduce / Div / Rem and formal_power_series_inverse_newton (tf_divide.hip)
+int tf_poly_divide_bfe(const uint64_t* a, size_t na, size_t batch, const uint64_t* b, size_t nb, uint64_t* q, uint64_t* r) try {
+    return divide_host(a, na, batch, b, nb, q, r, 1);
+} TF_ABI_CATCH
+int tf_poly_divide_xfe(const uint64_t* a, size_t na, size_t batch, const uint64_t* b, size_t nb, uint64_t* q, uint64_t* r) try {
+    return divide_host(a, na, batch, b, nb, q, r, 3);
+} TF_ABI_CATCH
+int tf_poly_divide_bfe_dev(const uint64_t* d_a, size_t na, size_t batch, const uint64_t* d_b, size_t nb, uint64_t* d_q, uint64_t* d_r, void* stream,
+                           int* d_status) try {
+    if (!d_status) return TF_ERR_NULL_POINTER;
+    return divide_dev(d_a, na, batch, d_b, nb, d_q, d_r, stream, d_status, 1);
+} TF_ABI_CATCH
+int tf_poly_divide_xfe_dev(const uint64_t* d_a, size_t na, size_t batch, const uint64_t* d_b, size_t nb, uint64_t* d_q, uint64_t* d_r, void* stream,
+                           int* d_status) try {
+    if (!d_status) return TF_ERR_NULL_POINTER;
+    return divide_dev(d_a, na, batch, d_b, nb, d_q, d_r, stream, d_status, 3);
+} TF_ABI_CATCH
+size_t tf_poly_fps_inverse_newton_len(size_t nf, size_t precision) { return fps_len(nf, precision); }
+int tf_poly_fps_inverse_newton_bfe(const uint64_t* f, size_t nf, size_t precision, uint64_t* out) try {
+    return fps_host(f, nf, precision, out, 1);
+} TF_ABI_CATCH
+int tf_poly_fps_inverse_newton_xfe(const uint64_t* f, size_t nf, size_t precision, uint64_t* out) try {
+    return fps_host(f, nf, precision, out, 3);
+} TF_ABI_CATCH
+int tf_poly_fps_inverse_newton_bfe_dev(const uint64_t* d_f, size_t nf, size_t precision, uint64_t* d_out, void* stream, int* d_status) try {
+    if (!d_status) return TF_ERR_NULL_POINTER;
+    return fps_dev(d_f, nf, precision, d_out, stream, d_status, 1);
+} TF_ABI_CATCH
+int tf_poly_fps_inverse_newton_xfe_dev(const uint64_t* d_f, size_t nf, size_t precision, uint64_t* d_out, void* stream, int* d_status) try {
+    if (!d_status) return TF_ERR_NULL_POINTER;
+    return fps_dev(d_f, nf, precision, d_out, stream, d_status, 3);
+} TF_ABI_CATCH
 static int coset_extrapolate_host(uint64_t offset, const uint64_t* cw, size_t n, size_t batch, const uint64_t* pts, size_t np,
                                   uint64_t* out, int L) {
     if (n == 0) return TF_ERR_LEN_NOT_POWER_OF_TWO;

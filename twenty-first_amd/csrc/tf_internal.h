@@ -7,6 +7,7 @@
 //   tf_abi.hip    host-pointer wrappers and the extern "C" entry points
 //   tf_multi.hip  one host-resident batch over several GPUs (tf_*_multi), device selection
 //   tf_proof.hip  batched verification of Merkle inclusion proofs (proof_kernels.h)
+//   tf_divide.hip division with remainder and the power-series inverse (divide_kernels.h), with their entry points
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,6 +139,7 @@ int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long l
 int launch_lat(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
                long long n_coeffs, const u64* in2, hipStream_t stream, const tfk::NttLatArgs* mods = nullptr, const u64* pre_scale = nullptr,
                const u64* post_scale = nullptr);
+int get_lat_table(DeviceCtx* ctx, int log_n, bool inverse, const u64** out, int scale_log);  // (scale_log < 0: log_n)
 bool tree_level_wanted(long long order, long long lines, int L = 1, bool up = false);
 template <bool UP>
 int launch_tree_level(DeviceCtx* ctx, int log_n, tfk::TreeLevelArgs a, hipStream_t s, int L = 1);
@@ -165,6 +167,22 @@ extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (c
 int merkle_proofs_dev(const uint32_t* heights, size_t n, const uint64_t* leaf_offsets, const u64* d_leaf_indices, const u64* d_leaf_digests,
                       const uint64_t* auth_offsets, const u64* d_auth, const u64* d_roots, int* d_statuses, u64* d_paths, bool paths,
                       uint64_t leaf_base, uint64_t auth_base, hipStream_t s);
+
+// ------------------------------------------------------------------------------------ tf_abi.hip
+// the host-pointer entry points' plumbing: h2d waits for its upload (pageable host memory), d2h and sync do not / do
+hipStream_t host_stream();
+int h2d(u64* d, const u64* h, size_t words, hipStream_t s);
+int d2h(u64* h, const u64* d, size_t words, hipStream_t s);
+int sync(hipStream_t s);
+
+// ------------------------------------------------------------------------------------ tf_divide.hip
+// division with remainder of `batch` dividends over one divisor, and the power-series inverse (include/tf_hip.h has the contract);
+// the _dev flavours take device pointers and a status word (may be null), the _host flavours host pointers
+int divide_dev(const u64* a, size_t na, size_t batch, const u64* b, size_t nb, u64* q, u64* r, void* stream, int* status, int L);
+int divide_host(const u64* a, size_t na, size_t batch, const u64* b, size_t nb, u64* q, u64* r, int L);
+size_t fps_len(size_t nf, size_t precision);
+int fps_dev(const u64* f, size_t nf, size_t precision, u64* out, void* stream, int* status, int L);
+int fps_host(const u64* f, size_t nf, size_t precision, u64* out, int L);
 
 // ------------------------------------------------------------------------------------ tf_poly.hip
 extern std::atomic<int> g_batch_eval_route;

@@ -308,6 +308,56 @@ def clean_divide_many(a, na: int, b, out, batch: int, stream=None, status=None) 
     _chk(_lib.lib().tf_poly_clean_divide_many_bfe_dev(_p(a), na, batch, _p(b), b.numel(), _p(out), _stream(stream)), "clean_divide")
 
 
+def divide(a, na: int, b, q, r, batch: int = 1, width: int = 1, stream=None, status=None) -> None:
+    """Polynomial::divide (math/polynomial.rs:539-600) of `batch` dividends of na coefficients each over ONE divisor b
+    (tf_poly_divide_*_dev): q = batch x max(na - nb + 1, 0), r = batch x (nb - 1) coefficients; either may be None (not written).
+    b must be normalised (b[nb-1] != 0, else 17 in status).  status: a one-element int32 CUDA tensor (first non-zero code wins);
+    without one a scratch word is used and checked after a synchronisation.  Never synchronises otherwise."""
+    import torch
+
+    width = _width(width)
+    a, b = _t(a, "a"), _t(b, "b")
+    _need(b.numel() % width == 0 and a.numel() == batch * na * width, "a = batch * na elements, b whole elements")
+    nb = b.numel() // width
+    _need(nb > 0, "the divisor must have a coefficient")  # (the C ABI's nb == 0 is TF_ERR_DIVISION_BY_ZERO)
+    k, m = max(na - nb + 1, 0), nb - 1
+    if q is not None:
+        q = _t(q, "q")
+        _need(q.numel() == batch * k * width, "q must hold batch * max(na - nb + 1, 0) elements")
+    if r is not None:
+        r = _t(r, "r")
+        _need(r.numel() == batch * m * width, "r must hold batch * (nb - 1) elements")
+    own = status is None
+    st = torch.zeros(1, dtype=torch.int32, device=a.device) if own else status
+    fn = _lib.lib().tf_poly_divide_bfe_dev if width == 1 else _lib.lib().tf_poly_divide_xfe_dev
+    _chk(fn(_p(a), na, batch, _p(b), nb, _p(q) if q is not None else None, _p(r) if r is not None else None, _stream(stream), _status(st)),
+         "divide")
+    if own:
+        (stream or torch.cuda.current_stream()).synchronize()
+        _chk(int(st.item()), "divide")
+
+
+def fps_inverse_newton(f, precision: int, out, width: int = 1, stream=None, status=None) -> None:
+    """Polynomial::formal_power_series_inverse_newton (math/polynomial.rs:1281-1366) on device buffers: out receives
+    tf_poly_fps_inverse_newton_len(nf, precision) coefficients.  status: as in divide."""
+    import torch
+
+    width = _width(width)
+    f = _t(f, "f")
+    _need(f.numel() % width == 0 and f.numel() > 0, "f must hold at least one whole element")
+    nf = f.numel() // width
+    n = int(_lib.lib().tf_poly_fps_inverse_newton_len(nf, precision))
+    out = _t(out, "out")
+    _need(n > 0 and out.numel() == n * width, "out must hold tf_poly_fps_inverse_newton_len(nf, precision) elements")
+    own = status is None
+    st = torch.zeros(1, dtype=torch.int32, device=f.device) if own else status
+    fn = _lib.lib().tf_poly_fps_inverse_newton_bfe_dev if width == 1 else _lib.lib().tf_poly_fps_inverse_newton_xfe_dev
+    _chk(fn(_p(f), nf, precision, _p(out), _stream(stream), _status(st)), "formal_power_series_inverse_newton")
+    if own:
+        (stream or torch.cuda.current_stream()).synchronize()
+        _chk(int(st.item()), "formal_power_series_inverse_newton")
+
+
 def zerofier(roots, out, width: int = 1, stream=None) -> None:
     """Polynomial::zerofier (math/polynomial.rs:1435-1441) on device buffers: out = the n + 1 coefficients of prod (x - roots[i])."""
     roots, out = _t(roots, "roots"), _t(out, "out")

@@ -14,6 +14,7 @@
 #pragma once
 
 #include <array>
+#include <utility>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -134,6 +135,22 @@ inline void ntt_batch_multi(XFieldElement* x, size_t n, size_t batch, const std:
 template <class FF>
 struct Polynomial {
     std::vector<FF> coefficients;  // low -> high degree
+  private:
+    std::pair<Polynomial, Polynomial> divide_impl(const Polynomial& divisor, bool want_q) const {
+        const size_t na = coefficients.size(), nb = divisor.coefficients.size();
+        std::vector<FF> q(want_q && na >= nb ? na - nb + 1 : 0), r(nb ? nb - 1 : 0);
+        const uint64_t* a = reinterpret_cast<const uint64_t*>(coefficients.data());
+        const uint64_t* b = reinterpret_cast<const uint64_t*>(divisor.coefficients.data());
+        uint64_t dummy[3] = {0, 0, 0};  // stands for an empty output (never written) and an empty dividend (never read)
+        uint64_t* qp = want_q ? (q.empty() ? dummy : reinterpret_cast<uint64_t*>(q.data())) : nullptr;
+        uint64_t* rp = r.empty() ? dummy : reinterpret_cast<uint64_t*>(r.data());
+        if (!na) a = dummy;
+        if constexpr (sizeof(FF) == 8) check(tf_poly_divide_bfe(a, na, 1, b, nb, qp, rp), "divide");
+        else check(tf_poly_divide_xfe(a, na, 1, b, nb, qp, rp), "divide");
+        return {Polynomial(std::move(q)), Polynomial(std::move(r))};
+    }
+
+  public:
     explicit Polynomial(std::vector<FF> c) : coefficients(std::move(c)) {
         while (!coefficients.empty() && coefficients.back() == FF{}) coefficients.pop_back();  // Polynomial::new normalises
     }
@@ -197,6 +214,25 @@ struct Polynomial {
                                        reinterpret_cast<const uint64_t*>(divisor.coefficients.data()), nb, reinterpret_cast<uint64_t*>(out.data())),
               "clean_divide");
         if (na < nb) out.clear();
+        return Polynomial(std::move(out));
+    }
+    // divide / naive_divide (polynomial.rs:539-600): (quotient, remainder); a zero divisor panics (NttPanic, code 15)
+    std::pair<Polynomial, Polynomial> divide(const Polynomial& divisor) const {
+        return divide_impl(divisor, true);
+    }
+    Polynomial operator/(const Polynomial& divisor) const { return divide(divisor).first; }   // Div (:2502-2512)
+    Polynomial operator%(const Polynomial& divisor) const { return reduce(divisor); }         // Rem (:2514-2524)
+    // reduce / fast_reduce (polynomial.rs:989-1048): the remainder only
+    Polynomial reduce(const Polynomial& modulus) const { return divide_impl(modulus, false).second; }
+    // formal_power_series_inverse_newton (polynomial.rs:1281-1366): the untruncated Newton iterate the reference returns
+    Polynomial formal_power_series_inverse_newton(size_t precision) const {
+        const size_t nf = coefficients.size();
+        std::vector<FF> out(nf ? tf_poly_fps_inverse_newton_len(nf, precision) : 0);
+        const uint64_t* f = reinterpret_cast<const uint64_t*>(coefficients.data());
+        uint64_t dummy[3] = {0, 0, 0};  // an empty output (the zero polynomial, or a length above the limit): never written
+        uint64_t* o = out.empty() ? dummy : reinterpret_cast<uint64_t*>(out.data());
+        if constexpr (sizeof(FF) == 8) check(tf_poly_fps_inverse_newton_bfe(f, nf, precision, o), "formal_power_series_inverse_newton");
+        else check(tf_poly_fps_inverse_newton_xfe(f, nf, precision, o), "formal_power_series_inverse_newton");
         return Polynomial(std::move(out));
     }
     // zerofier (polynomial.rs:1435-1441, par_zerofier :1444-1459): the monic polynomial with exactly these roots
