@@ -63,7 +63,12 @@ enum tf_status {
     TF_ERR_INTERNAL = 18,                  /* a C++ exception other than an allocation failure was caught at the ABI (csrc/tf_guard.h); see tf_last_error() */
     TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH = 19,  /* MerkleTreeError::AuthenticationStructureLengthMismatch  merkle_tree.rs:933-965 (raised :910-912) */
     TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH = 20,   /* MerkleTreeError::RepeatedLeafDigestMismatch  merkle_tree.rs:933-965 (raised :921-923) */
-    TF_ERR_ROOT_MISMATCH = 21                    /* MerkleTreeError::RootMismatch  merkle_tree.rs:933-965 (raised :740-742) */
+    TF_ERR_ROOT_MISMATCH = 21,                   /* MerkleTreeError::RootMismatch  merkle_tree.rs:933-965 (raised :740-742) */
+    /* the reasons MmrMembershipProof::verify returns false, in its order (mmr/mmr_membership_proof.rs:36-77) */
+    TF_ERR_MMR_LEAF_INDEX_OUT_OF_RANGE = 22,     /* leaf_index >= num_leafs  :43-46 */
+    TF_ERR_MMR_PEAK_COUNT_MISMATCH = 23,         /* peaks.len() != num_leafs.count_ones()  :50-54 */
+    TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH = 24,   /* authentication path length != height of the leaf's peak  :56-60 */
+    TF_ERR_MMR_PEAK_MISMATCH = 25                /* the path does not hash to the leaf's peak  :76 */
 };
 
 /* Human-readable name of a status code. */
@@ -471,6 +476,55 @@ int tf_merkle_authentication_paths(const uint32_t *tree_heights, size_t n_proofs
 int tf_merkle_authentication_paths_dev(const uint32_t *tree_heights, size_t n_proofs, const uint64_t *leaf_offsets,
                                        const uint64_t *d_leaf_indices, const uint64_t *d_leaf_digests, const uint64_t *auth_offsets,
                                        const uint64_t *d_auth_digests, uint64_t *d_paths_out, int *d_statuses, void *stream);
+
+/* ---- Merkle Mountain Range accumulators (util_types/mmr/; mmr.rs, mmr_accumulator.rs, mmr_membership_proof.rs, shared_basic.rs)
+ * A digest is 5 raw Montgomery words; a list of peaks runs from the highest to the lowest, popcount(leaf_count) digests.  Every
+ * call returns TF_ERR_INVALID_ARGUMENT for a leaf count above 2^63 (the limit of mmr.rs:12-13), before the device is touched; so
+ * do the other argument errors named below.  The host forms take host pointers and return when the results are in place; the
+ * _dev forms take device pointers for the digests (and statuses / flags), enqueue on `stream`, never synchronise and copy nothing
+ * back.  Counts, leaf indices of a mutation and every offset array stay on the host: the planner reads them.
+ *
+ * tf_mmr_append: k successive MmrAccumulator::append calls (mmr_accumulator.rs:149-159, calculate_new_peaks_from_append
+ *   shared_basic.rs:75-105) on the accumulator (leaf_count, old_peaks): new_peaks receives the popcount(leaf_count + k) peaks (it
+ *   must not overlap old_peaks); proofs, if not NULL, the membership proof each append returns, concatenated: proof i has
+ *   trailing_ones(leaf_count + i) digests.  leaf_count = 0 is MmrAccumulator::new_from_leafs (:29-115).
+ *   Errors: leaf_count + k > 2^63 -> TF_ERR_INVALID_ARGUMENT; NULL new_peaks / new_leafs (k > 0) / old_peaks (leaf_count > 0)
+ *   -> TF_ERR_NULL_POINTER. */
+int tf_mmr_append(uint64_t leaf_count, const uint64_t *old_peaks, const uint64_t *new_leafs, size_t k, uint64_t *new_peaks, uint64_t *proofs);
+int tf_mmr_append_dev(uint64_t leaf_count, const uint64_t *d_old_peaks, const uint64_t *d_new_leafs, size_t k, uint64_t *d_new_peaks,
+                      uint64_t *d_proofs, void *stream);
+/* tf_mmr_bag_peaks: bag_peaks (mmr_accumulator.rs:379-391) of n_acc accumulators: accumulator a has leaf_counts[a] leafs and its
+ *   popcount(leaf_counts[a]) peaks follow those of accumulator a - 1 in peaks; out receives one digest per accumulator. */
+int tf_mmr_bag_peaks(const uint64_t *leaf_counts, size_t n_acc, const uint64_t *peaks, uint64_t *out);
+int tf_mmr_bag_peaks_dev(const uint64_t *leaf_counts, size_t n_acc, const uint64_t *d_peaks, uint64_t *d_out, void *stream);
+/* tf_mmr_verify_membership_proofs: MmrMembershipProof::verify (mmr_membership_proof.rs:36-77) of n_proofs proofs against one
+ *   accumulator (leaf_count, the n_peaks digests of peaks).  Proof p: leaf index leaf_indices[p], leaf digest leaf_digests + 5 p,
+ *   path digests [path_offsets[p], path_offsets[p + 1]) of paths.  statuses[p] = 0 where verify returns true, else the first reason
+ *   it returns false: TF_ERR_MMR_LEAF_INDEX_OUT_OF_RANGE / _PEAK_COUNT_MISMATCH / _AUTH_PATH_LENGTH_MISMATCH / _PEAK_MISMATCH.
+ *   Errors: decreasing path_offsets -> TF_ERR_INVALID_ARGUMENT. */
+int tf_mmr_verify_membership_proofs(uint64_t leaf_count, const uint64_t *peaks, size_t n_peaks, size_t n_proofs, const uint64_t *leaf_indices,
+                                    const uint64_t *leaf_digests, const uint64_t *path_offsets, const uint64_t *paths, int *statuses);
+int tf_mmr_verify_membership_proofs_dev(uint64_t leaf_count, const uint64_t *d_peaks, size_t n_peaks, size_t n_proofs,
+                                        const uint64_t *d_leaf_indices, const uint64_t *d_leaf_digests, const uint64_t *path_offsets,
+                                        const uint64_t *d_paths, int *d_statuses, void *stream);
+/* tf_mmr_batch_mutate_leafs: MmrAccumulator::batch_mutate_leaf_and_update_mps (mmr_accumulator.rs:180-302).  Mutation m sets leaf
+ *   mut_indices[m] to new_leafs + 5 m, with the path [mut_offsets[m], mut_offsets[m + 1]) of mut_paths.  Own proof p (leaf
+ *   own_indices[p], path [own_offsets[p], own_offsets[p + 1]) of own_paths) is updated in place and modified[p] = 1 where a digest
+ *   was replaced, else 0.  peaks (popcount(leaf_count) digests) is updated in place; with peaks = NULL the call is
+ *   MmrMembershipProof::batch_update_from_batch_leaf_mutation (mmr_membership_proof.rs:523-626).  The result is the reference's for
+ *   every input it does not panic on, consistent or not.
+ *   Errors: a repeated mutation index -> TF_ERR_INVALID_ARGUMENT (the reference panics); decreasing offsets ->
+ *   TF_ERR_INVALID_ARGUMENT.  Two divergences from the reference: (1) a mutation or own index >= leaf_count ->
+ *   TF_ERR_LEAF_INDEX_INVALID also with peaks = NULL, where the reference checks no index, so pass the MMR's leaf count in both
+ *   modes; (2) a mutation path of more than 63 digests -> TF_ERR_INVALID_ARGUMENT in both modes (no node of an MMR of at most 2^63
+ *   leafs is that high; the reference's u64 node index arithmetic overflows there, and batch_update_from_batch_leaf_mutation, which
+ *   skips the last step, would otherwise accept a path of 64). */
+int tf_mmr_batch_mutate_leafs(uint64_t leaf_count, uint64_t *peaks, size_t n_mut, const uint64_t *mut_indices, const uint64_t *new_leafs,
+                              const uint64_t *mut_offsets, const uint64_t *mut_paths, size_t n_own, const uint64_t *own_indices,
+                              const uint64_t *own_offsets, uint64_t *own_paths, int *modified);
+int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t *d_peaks, size_t n_mut, const uint64_t *mut_indices, const uint64_t *d_new_leafs,
+                                  const uint64_t *mut_offsets, const uint64_t *d_mut_paths, size_t n_own, const uint64_t *own_indices,
+                                  const uint64_t *own_offsets, uint64_t *d_own_paths, int *d_modified, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the

@@ -908,4 +908,163 @@ class MerkleTreeInclusionProof:
         return paths[0]
 
 
+# ----------------------------------------------------------------------------- Merkle Mountain Range (util_types/mmr/)
+from . import mmr_index  # noqa: E402
+
+
+def _digests(x, name):
+    a = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 5)
+    return a
+
+
+class MmrMembershipProof:
+    """mmr_membership_proof.rs:23-34: the authentication path, (h, 5) raw words from the leaf upwards."""
+
+    def __init__(self, authentication_path):
+        self.authentication_path = _digests(authentication_path, "authentication_path")
+
+    def __eq__(self, other):
+        return isinstance(other, MmrMembershipProof) and np.array_equal(self.authentication_path, other.authentication_path)
+
+    @staticmethod
+    def _pack(proofs):
+        off = np.zeros(len(proofs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([p.authentication_path.shape[0] for p in proofs])
+        paths = np.ascontiguousarray(np.concatenate([p.authentication_path for p in proofs]).reshape(-1) if proofs else np.empty(0),
+                                     dtype=np.uint64)
+        return off, paths
+
+    @staticmethod
+    def verify_status_batch(proofs, leaf_indices, leaf_digests, peaks, num_leafs: int) -> np.ndarray:
+        """Status of verify (:36-77) for every proof: 0 = true, else the first reason it is false (22..25, include/tf_hip.h)."""
+        proofs = list(proofs)
+        idx = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+        dig = np.ascontiguousarray(leaf_digests, dtype=np.uint64).reshape(-1)
+        pk = np.ascontiguousarray(peaks, dtype=np.uint64).reshape(-1)
+        if idx.size != len(proofs) or dig.size != 5 * len(proofs) or pk.size % 5:
+            raise ValueError("one leaf index and one leaf digest per proof, whole peak digests")
+        off, paths = MmrMembershipProof._pack(proofs)
+        st = np.zeros(max(len(proofs), 1), dtype=np.int32)
+        _check(lib().tf_mmr_verify_membership_proofs(C.c_uint64(num_leafs), _ptr(pk), pk.size // 5, len(proofs), _ptr(idx), _ptr(dig), _ptr(off),
+                                                     _ptr(paths), _ptr(st)), "MmrMembershipProof::verify")
+        return st[: len(proofs)]
+
+    @staticmethod
+    def verify_batch(proofs, leaf_indices, leaf_digests, peaks, num_leafs: int) -> np.ndarray:
+        return MmrMembershipProof.verify_status_batch(proofs, leaf_indices, leaf_digests, peaks, num_leafs) == 0
+
+    def verify(self, leaf_index: int, leaf_hash, peaks, num_leafs: int) -> bool:
+        return bool(self.verify_batch([self], [leaf_index], leaf_hash, peaks, num_leafs)[0])
+
+    @staticmethod
+    def batch_update_from_batch_leaf_mutation(membership_proofs, membership_proof_leaf_indices, leaf_mutations, num_leafs: int):
+        """:523-626 on the GPU; the proofs are updated in place, the indices of the changed ones are returned.  num_leafs is the MMR's
+        leaf count: this call checks every index against it, where the reference checks none (include/tf_hip.h)."""
+        return _mmr_mutate(None, num_leafs, membership_proofs, membership_proof_leaf_indices, leaf_mutations)[1]
+
+
+class LeafMutation:
+    """mmr_trait.rs: the leaf at leaf_index becomes new_leaf; membership_proof is its proof before the mutation."""
+
+    def __init__(self, leaf_index: int, new_leaf, membership_proof: MmrMembershipProof):
+        self.leaf_index = int(leaf_index)
+        self.new_leaf = np.ascontiguousarray(new_leaf, dtype=np.uint64).reshape(5)
+        self.membership_proof = membership_proof
+
+
+def _mmr_mutate(peaks, leaf_count, proofs, proof_indices, mutations):
+    proofs, mutations = list(proofs), list(mutations)
+    pidx = np.ascontiguousarray(proof_indices, dtype=np.uint64).reshape(-1)
+    if pidx.size != len(proofs):
+        raise ValueError(f"Lists must have same length. Got: {len(proofs)} and {pidx.size}")
+    midx = np.array([m.leaf_index for m in mutations], dtype=np.uint64)
+    leafs = np.ascontiguousarray(np.concatenate([m.new_leaf for m in mutations]) if mutations else np.empty(0), dtype=np.uint64)
+    moff, mpaths = MmrMembershipProof._pack([m.membership_proof for m in mutations])
+    poff, ppaths = MmrMembershipProof._pack(proofs)
+    mod = np.zeros(max(len(proofs), 1), dtype=np.int32)
+    pk = None if peaks is None else np.ascontiguousarray(peaks, dtype=np.uint64).reshape(-1)
+    _check(lib().tf_mmr_batch_mutate_leafs(C.c_uint64(leaf_count), None if pk is None else _ptr(pk), len(mutations), _ptr(midx), _ptr(leafs),
+                                           _ptr(moff), _ptr(mpaths), len(proofs), _ptr(pidx), _ptr(poff), _ptr(ppaths), _ptr(mod)),
+           "batch_mutate_leaf_and_update_mps")
+    for p, a, b in zip(proofs, poff[:-1].tolist(), poff[1:].tolist()):
+        p.authentication_path = ppaths[5 * a: 5 * b].reshape(-1, 5).copy()
+    return pk, [i for i in range(len(proofs)) if mod[i]]
+
+
+class MmrAccumulator:
+    """mmr_accumulator.rs: leaf count and peaks (highest first, (popcount, 5) raw words), every operation on the GPU."""
+
+    def __init__(self, leaf_count: int = 0, peaks=None):
+        self.init(peaks if peaks is not None else np.empty((0, 5), dtype=np.uint64), leaf_count)
+
+    def init(self, peaks, leaf_count: int):  # :118-124
+        leaf_count = int(leaf_count)
+        if not 0 <= leaf_count <= mmr_index.MAX_LEAFS:
+            raise ValueError("at most 2^63 leafs (mmr.rs:12-13)")
+        peaks = _digests(peaks, "peaks").copy()
+        if peaks.shape[0] != bin(leaf_count).count("1"):
+            raise ValueError(f"an accumulator of {leaf_count} leafs has {bin(leaf_count).count('1')} peaks, got {peaks.shape[0]}")
+        self._peaks, self.leaf_count = peaks, leaf_count
+        return self
+
+    @classmethod
+    def new_from_leafs(cls, leafs):  # :29-115
+        acc = cls()
+        acc.append_many(leafs, proofs=False)
+        return acc
+
+    def peaks(self) -> np.ndarray:
+        return self._peaks.copy()
+
+    def num_leafs(self) -> int:
+        return self.leaf_count
+
+    def bag_peaks(self) -> np.ndarray:  # :379-391
+        return bag_peaks_batch([self.leaf_count], self._peaks)[0]
+
+    def append(self, new_leaf) -> MmrMembershipProof:  # :149-159
+        return self.append_many(np.asarray(new_leaf, dtype=np.uint64).reshape(1, 5))[0]
+
+    def append_many(self, leafs, proofs: bool = True):
+        """k successive appends in one call; returns their membership proofs (or None with proofs=False)."""
+        leafs = _digests(leafs, "leafs")
+        k, n = leafs.shape[0], self.leaf_count
+        if n + k > mmr_index.MAX_LEAFS:
+            raise ValueError("at most 2^63 leafs (mmr.rs:12-13)")
+        if k == 0:
+            return [] if proofs else None
+        lens = [mmr_index.trailing_ones(n + i) for i in range(k)]
+        new = np.empty(5 * bin(n + k).count("1"), dtype=np.uint64)
+        out = np.empty(max(5 * sum(lens), 1), dtype=np.uint64) if proofs else None
+        old = np.ascontiguousarray(self._peaks.reshape(-1))
+        _check(lib().tf_mmr_append(C.c_uint64(n), _ptr(old), _ptr(np.ascontiguousarray(leafs.reshape(-1))), k, _ptr(new),
+                                   _ptr(out) if proofs else None), "MmrAccumulator::append")
+        self._peaks, self.leaf_count = new.reshape(-1, 5), n + k
+        if not proofs:
+            return None
+        res, off = [], 0
+        for L in lens:
+            res.append(MmrMembershipProof(out[5 * off: 5 * (off + L)].reshape(-1, 5).copy()))
+            off += L
+        return res
+
+    def mutate_leaf(self, leaf_mutation: LeafMutation) -> None:  # :164-175
+        self.batch_mutate_leaf_and_update_mps([], [], [leaf_mutation])
+
+    def batch_mutate_leaf_and_update_mps(self, membership_proofs, membership_proof_leaf_indices, mutation_data):  # :180-302
+        """The proofs are updated in place; returns the indices of those that changed."""
+        peaks, modified = _mmr_mutate(self._peaks, self.leaf_count, membership_proofs, membership_proof_leaf_indices, mutation_data)
+        self._peaks = peaks.reshape(-1, 5)
+        return modified
+
+
+def bag_peaks_batch(leaf_counts, peaks) -> np.ndarray:
+    """bag_peaks of many accumulators at once: peaks = every accumulator's peaks, one after the other; returns (n, 5)."""
+    lc = np.ascontiguousarray(leaf_counts, dtype=np.uint64).reshape(-1)
+    pk = np.ascontiguousarray(peaks, dtype=np.uint64).reshape(-1)
+    out = np.empty(max(5 * lc.size, 1), dtype=np.uint64)
+    _check(lib().tf_mmr_bag_peaks(_ptr(lc), lc.size, _ptr(pk), _ptr(out)), "bag_peaks")
+    return out[: 5 * lc.size].reshape(-1, 5)
+
+
 from . import device  # noqa: E402  (torch device-pointer API)

@@ -136,6 +136,14 @@ SIGNATURES = {
     "tf_merkle_from_rows_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp]),
     "tf_merkle_auth_structure_indices": (C.c_int, [_sz, _vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "tf_merkle_authentication_structure_dev": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(C.c_size_t), _vp]),
+    "tf_mmr_append": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _vp, _vp]),
+    "tf_mmr_append_dev": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "tf_mmr_bag_peaks": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "tf_mmr_bag_peaks_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp]),
+    "tf_mmr_verify_membership_proofs": (C.c_int, [C.c_uint64, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "tf_mmr_verify_membership_proofs_dev": (C.c_int, [C.c_uint64, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tf_mmr_batch_mutate_leafs": (C.c_int, [C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "tf_mmr_batch_mutate_leafs_dev": (C.c_int, [C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "tf_merkle_verify_proofs": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_merkle_verify_proofs_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_merkle_authentication_paths": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

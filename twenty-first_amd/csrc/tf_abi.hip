@@ -180,6 +180,10 @@ const char* tf_status_string(int status) {
         case TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH: return "TF_ERR_AUTH_STRUCTURE_LENGTH_MISMATCH";
         case TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH: return "TF_ERR_REPEATED_LEAF_DIGEST_MISMATCH";
         case TF_ERR_ROOT_MISMATCH: return "TF_ERR_ROOT_MISMATCH";
+        case TF_ERR_MMR_LEAF_INDEX_OUT_OF_RANGE: return "TF_ERR_MMR_LEAF_INDEX_OUT_OF_RANGE";
+        case TF_ERR_MMR_PEAK_COUNT_MISMATCH: return "TF_ERR_MMR_PEAK_COUNT_MISMATCH";
+        case TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH: return "TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH";
+        case TF_ERR_MMR_PEAK_MISMATCH: return "TF_ERR_MMR_PEAK_MISMATCH";
         default: return "TF_ERR_UNKNOWN";
     }
 }
@@ -987,6 +991,43 @@ int tf_merkle_authentication_paths_dev(const uint32_t* tree_heights, size_t n_pr
                                        const uint64_t* d_auth_digests, uint64_t* d_paths_out, int* d_statuses, void* stream) try {
     return merkle_proofs_dev(tree_heights, n_proofs, leaf_offsets, d_leaf_indices, d_leaf_digests, auth_offsets, d_auth_digests, nullptr,
                              d_statuses, d_paths_out, true, 0, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+
+
+int tf_mmr_append(uint64_t leaf_count, const uint64_t* old_peaks, const uint64_t* new_leafs, size_t k, uint64_t* new_peaks, uint64_t* proofs) try {
+    return mmr_append_host(leaf_count, old_peaks, new_leafs, k, new_peaks, proofs);
+} TF_ABI_CATCH
+int tf_mmr_append_dev(uint64_t leaf_count, const uint64_t* d_old_peaks, const uint64_t* d_new_leafs, size_t k, uint64_t* d_new_peaks,
+                      uint64_t* d_proofs, void* stream) try {
+    return mmr_append_dev(leaf_count, d_old_peaks, d_new_leafs, k, d_new_peaks, d_proofs, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_mmr_bag_peaks(const uint64_t* leaf_counts, size_t n_acc, const uint64_t* peaks, uint64_t* out) try {
+    return mmr_bag_peaks_host(leaf_counts, n_acc, peaks, out);
+} TF_ABI_CATCH
+int tf_mmr_bag_peaks_dev(const uint64_t* leaf_counts, size_t n_acc, const uint64_t* d_peaks, uint64_t* d_out, void* stream) try {
+    return mmr_bag_peaks_dev(leaf_counts, n_acc, d_peaks, d_out, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_mmr_verify_membership_proofs(uint64_t leaf_count, const uint64_t* peaks, size_t n_peaks, size_t n_proofs, const uint64_t* leaf_indices,
+                                    const uint64_t* leaf_digests, const uint64_t* path_offsets, const uint64_t* paths, int* statuses) try {
+    return mmr_verify_host(leaf_count, peaks, n_peaks, n_proofs, leaf_indices, leaf_digests, path_offsets, paths, statuses);
+} TF_ABI_CATCH
+int tf_mmr_verify_membership_proofs_dev(uint64_t leaf_count, const uint64_t* d_peaks, size_t n_peaks, size_t n_proofs,
+                                        const uint64_t* d_leaf_indices, const uint64_t* d_leaf_digests, const uint64_t* path_offsets,
+                                        const uint64_t* d_paths, int* d_statuses, void* stream) try {
+    return mmr_verify_dev(leaf_count, d_peaks, n_peaks, n_proofs, d_leaf_indices, d_leaf_digests, path_offsets, d_paths, d_statuses, 0,
+                          static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_mmr_batch_mutate_leafs(uint64_t leaf_count, uint64_t* peaks, size_t n_mut, const uint64_t* mut_indices, const uint64_t* new_leafs,
+                              const uint64_t* mut_offsets, const uint64_t* mut_paths, size_t n_own, const uint64_t* own_indices,
+                              const uint64_t* own_offsets, uint64_t* own_paths, int* modified) try {
+    return mmr_mutate_host(leaf_count, peaks, n_mut, mut_indices, new_leafs, mut_offsets, mut_paths, n_own, own_indices, own_offsets, own_paths,
+                           modified);
+} TF_ABI_CATCH
+int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t* d_peaks, size_t n_mut, const uint64_t* mut_indices, const uint64_t* d_new_leafs,
+                                  const uint64_t* mut_offsets, const uint64_t* d_mut_paths, size_t n_own, const uint64_t* own_indices,
+                                  const uint64_t* own_offsets, uint64_t* d_own_paths, int* d_modified, void* stream) try {
+    return mmr_mutate_dev(leaf_count, d_peaks, n_mut, mut_indices, d_new_leafs, mut_offsets, d_mut_paths, n_own, own_indices, own_offsets,
+                          d_own_paths, d_modified, 0, 0, static_cast<hipStream_t>(stream));
 } TF_ABI_CATCH
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //   tf_abi.hip    host-pointer wrappers and the extern "C" entry points
 //   tf_multi.hip  one host-resident batch over several GPUs (tf_*_multi), device selection
 //   tf_proof.hip  batched verification of Merkle inclusion proofs (proof_kernels.h)
+//   tf_mmr.hip    batched Merkle Mountain Range accumulators and membership proofs (mmr_kernels.h), with their host flavours
 //   tf_divide.hip division with remainder and the power-series inverse (divide_kernels.h), with their entry points
 #pragma once
 #include <hip/hip_runtime.h>
@@ -162,11 +163,35 @@ int gather_digests_dev(const u64* d_nodes, const unsigned long long* d_idx, size
 extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (canonical values; tf_tip5.hip)
 
 // ------------------------------------------------------------------------------------ tf_proof.hip
+// page-locked staging for descriptors built on the host (shared with tf_mmr.hip): stage_acquire hands out a block of at least `bytes`
+// whose last copy has completed; stage_release takes it back once the copy that reads it is enqueued on `s`
+struct Staging {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;
+};
+int stage_acquire(int dev, size_t bytes, Staging* out);
+void stage_release(int dev, Staging st, hipStream_t s);
 // batched MerkleTreeInclusionProof::try_verify (paths = false) / into_authentication_paths (paths = true); the leaf and structure
 // arrays are indexed from leaf_base / auth_base (the host flavours upload only [offsets[0], offsets[n]))
 int merkle_proofs_dev(const uint32_t* heights, size_t n, const uint64_t* leaf_offsets, const u64* d_leaf_indices, const u64* d_leaf_digests,
                       const uint64_t* auth_offsets, const u64* d_auth, const u64* d_roots, int* d_statuses, u64* d_paths, bool paths,
                       uint64_t leaf_base, uint64_t auth_base, hipStream_t s);
+
+// ------------------------------------------------------------------------------------ tf_mmr.hip
+// the MMR calls of include/tf_hip.h: _dev forms (path arrays indexed from mbase / pbase / path_base, as merkle_proofs_dev) and host forms
+int mmr_append_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_peaks, u64* proofs, hipStream_t s);
+int mmr_append_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_peaks, u64* proofs);
+int mmr_bag_peaks_dev(const uint64_t* leaf_counts, size_t n_acc, const u64* peaks, u64* out, hipStream_t s);
+int mmr_bag_peaks_host(const uint64_t* leaf_counts, size_t n_acc, const u64* peaks, u64* out);
+int mmr_verify_dev(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, const u64* idx, const u64* digests, const uint64_t* offsets,
+                   const u64* paths, int* statuses, uint64_t path_base, hipStream_t s);
+int mmr_verify_host(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, const u64* idx, const u64* digests, const uint64_t* offsets,
+                    const u64* paths, int* statuses);
+int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, const u64* leafs, const uint64_t* moff, const u64* mpaths, size_t P,
+                   const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified, uint64_t mbase, uint64_t pbase, hipStream_t s);
+int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, const u64* leafs, const uint64_t* moff, const u64* mpaths, size_t P,
+                    const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified);
 
 // ------------------------------------------------------------------------------------ tf_abi.hip
 // the host-pointer entry points' plumbing: h2d waits for its upload (pageable host memory), d2h and sync do not / do

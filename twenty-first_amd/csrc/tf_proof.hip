@@ -19,13 +19,9 @@ namespace tfi {
 // page-locked blocks kept per device; a block is reused once the copy that last read it has completed (its event), so a call never
 // waits for earlier work on its stream.
 namespace {
-struct Staging {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t done = nullptr;
-};
 std::mutex g_stage_mu[kMaxDevices];
 std::vector<Staging> g_stage[kMaxDevices];
+}  // namespace
 
 int stage_acquire(int dev, size_t bytes, Staging* out) {
     {
@@ -58,6 +54,7 @@ void stage_release(int dev, Staging st, hipStream_t s) {
     g_stage[dev].push_back(st);
 }
 
+namespace {
 std::mutex g_consts_mu;
 bool g_consts_ready[kMaxDevices];
 

@@ -483,3 +483,73 @@ def merkle_from_columns(table, n_rows: int, n_cols: int, nodes_out, width: int =
     _need(table.numel() >= ((batch * n_cols - 1) * cs + n_rows * width if batch * n_cols else 0), "table is smaller than batch * n_cols columns")
     _need(nodes_out.numel() == batch * n_rows * 10, "nodes_out must hold batch x 2 n_rows digests")
     _chk(_lib.lib().tf_merkle_from_columns_dev(_p(table), n_rows, n_cols, width, cs, _p(nodes_out), batch, _stream(stream)), "MerkleTree::par_new")
+
+
+# ----------------------------------------------------------------------------- Merkle Mountain Range (include/tf_hip.h, "Merkle Mountain Range")
+def _u64_host(a):
+    import numpy as np
+
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+
+
+def _opt(t, name):
+    return None if t is None else _p(_t(t, name))
+
+
+def mmr_append(leaf_count: int, old_peaks, new_leafs, new_peaks, proofs=None, stream=None) -> None:
+    """k successive MmrAccumulator::append (mmr_accumulator.rs:149-159): new_peaks receives popcount(leaf_count + k) digests, proofs
+    (if given) the concatenated proofs, trailing_ones(leaf_count + i) digests for append i.  Nothing is synchronised."""
+    new_leafs, new_peaks = _t(new_leafs, "new_leafs"), _t(new_peaks, "new_peaks")
+    _need(new_leafs.numel() % 5 == 0, "new_leafs must hold whole digests")
+    k = new_leafs.numel() // 5
+    _need(new_peaks.numel() >= 5 * bin(leaf_count + k).count("1"), "new_peaks must hold popcount(leaf_count + k) digests")
+    _need(old_peaks is None or old_peaks.numel() >= 5 * bin(leaf_count).count("1"), "old_peaks must hold popcount(leaf_count) digests")
+    if proofs is not None:
+        _need(_t(proofs, "proofs").numel() >= 5 * sum(((leaf_count + i) ^ (leaf_count + i + 1)).bit_length() - 1 for i in range(k)),
+              "proofs must hold sum(trailing_ones(leaf_count + i)) digests")
+    _chk(_lib.lib().tf_mmr_append_dev(C.c_uint64(leaf_count), _opt(old_peaks, "old_peaks"), _p(new_leafs), k, _p(new_peaks),
+                                      _opt(proofs, "proofs"), _stream(stream)), "MmrAccumulator::append")
+
+
+def mmr_bag_peaks(leaf_counts, peaks, out, stream=None) -> None:
+    """bag_peaks (mmr_accumulator.rs:379-391) of len(leaf_counts) accumulators (host counts; device peaks, one accumulator's after the
+    other's): out receives one digest each.  Nothing is synchronised."""
+    lc = _u64_host(leaf_counts)
+    peaks, out = _t(peaks, "peaks"), _t(out, "out")
+    import numpy as np
+
+    n_peaks = int(np.unpackbits(lc.view(np.uint8)).sum())  # the peaks of all accumulators
+    _need(peaks.numel() >= 5 * n_peaks and out.numel() >= 5 * lc.size, "buffer sizes do not match the counts")
+    _chk(_lib.lib().tf_mmr_bag_peaks_dev(_host(lc), lc.size, _p(peaks), _p(out), _stream(stream)), "bag_peaks")
+
+
+def mmr_verify_membership_proofs(leaf_count: int, peaks, leaf_indices, leaf_digests, path_offsets, paths, statuses, stream=None) -> None:
+    """MmrMembershipProof::verify (mmr_membership_proof.rs:36-77) of a batch: statuses[p] (device int32) = 0 or the first reason it is
+    false (22..25).  path_offsets is a host array of n_proofs + 1 entries; everything else is on the device.  Nothing is synchronised."""
+    off = _u64_host(path_offsets)
+    n = off.size - 1
+    peaks, leaf_indices, leaf_digests, paths = _t(peaks, "peaks"), _t(leaf_indices, "leaf_indices"), _t(leaf_digests, "leaf_digests"), _t(paths, "paths")
+    statuses = _status_tensor(statuses, n)
+    _need(n >= 0 and peaks.numel() % 5 == 0 and leaf_indices.numel() >= n and leaf_digests.numel() >= 5 * n
+          and (n == 0 or paths.numel() >= 5 * int(off[-1])), "buffer sizes do not match the offsets")
+    _chk(_lib.lib().tf_mmr_verify_membership_proofs_dev(C.c_uint64(leaf_count), _p(peaks), peaks.numel() // 5, n, _p(leaf_indices),
+                                                        _p(leaf_digests), _host(off), _p(paths), _p(statuses), _stream(stream)),
+         "MmrMembershipProof::verify")
+
+
+def mmr_batch_mutate_leafs(leaf_count: int, peaks, mut_indices, new_leafs, mut_offsets, mut_paths, own_indices, own_offsets, own_paths,
+                           modified, stream=None) -> None:
+    """batch_mutate_leaf_and_update_mps (mmr_accumulator.rs:180-302), or with peaks=None batch_update_from_batch_leaf_mutation
+    (mmr_membership_proof.rs:523-626): peaks and own_paths are updated in place, modified[p] (device int32) = 1 where proof p
+    changed.  Indices and offsets are host arrays.  Nothing is synchronised."""
+    mi, mo, oi, oo = _u64_host(mut_indices), _u64_host(mut_offsets), _u64_host(own_indices), _u64_host(own_offsets)
+    M, P = mi.size, oi.size
+    _need(mo.size == M + 1 and oo.size == P + 1, "offsets need one entry more than indices")
+    new_leafs, mut_paths, own_paths = _t(new_leafs, "new_leafs"), _t(mut_paths, "mut_paths"), _t(own_paths, "own_paths")
+    mod_p = _p(_status_tensor(modified, P)) if P else None
+    _need(new_leafs.numel() >= 5 * M and mut_paths.numel() >= 5 * int(mo[-1]) and own_paths.numel() >= 5 * int(oo[-1]), "buffer sizes do not match")
+    if peaks is not None:
+        _need(_t(peaks, "peaks").numel() >= 5 * bin(leaf_count).count("1"), "peaks must hold popcount(leaf_count) digests")
+    _chk(_lib.lib().tf_mmr_batch_mutate_leafs_dev(C.c_uint64(leaf_count), _opt(peaks, "peaks"), M, _host(mi), _p(new_leafs), _host(mo),
+                                                  _p(mut_paths), P, _host(oi), _host(oo), _p(own_paths), mod_p, _stream(stream)),
+         "batch_mutate_leaf_and_update_mps")

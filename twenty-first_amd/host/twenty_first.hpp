@@ -556,4 +556,118 @@ inline MerkleTreeInclusionProof MerkleTree::inclusion_proof_for_leaf_indices(con
     return p;
 }
 
+// ---- Merkle Mountain Range (util_types/mmr/), every operation on the GPU -----------------------------------------------------------
+struct MmrMembershipProof {  // mmr_membership_proof.rs:23-34
+    std::vector<Digest> authentication_path;
+    bool operator==(const MmrMembershipProof& o) const { return authentication_path == o.authentication_path; }
+
+    // verify (:36-77) of many proofs against one accumulator: 0 = true, else the first reason it is false (TF_ERR_MMR_*)
+    static std::vector<int> verify_statuses(const std::vector<MmrMembershipProof>& proofs, const std::vector<uint64_t>& leaf_indices,
+                                            const std::vector<Digest>& leafs, const std::vector<Digest>& peaks, uint64_t num_leafs) {
+        if (leaf_indices.size() != proofs.size() || leafs.size() != proofs.size()) throw std::invalid_argument("one leaf per proof");
+        std::vector<uint64_t> off;
+        std::vector<Digest> paths;
+        pack(proofs, off, paths);
+        std::vector<int> st(proofs.size());
+        check(tf_mmr_verify_membership_proofs(num_leafs, reinterpret_cast<const uint64_t*>(peaks.data()), peaks.size(), proofs.size(),
+                                              leaf_indices.data(), reinterpret_cast<const uint64_t*>(leafs.data()), off.data(),
+                                              reinterpret_cast<const uint64_t*>(paths.data()), st.data()),
+              "MmrMembershipProof::verify");
+        return st;
+    }
+    bool verify(uint64_t leaf_index, const Digest& leaf, const std::vector<Digest>& peaks, uint64_t num_leafs) const {
+        return verify_statuses({*this}, {leaf_index}, {leaf}, peaks, num_leafs)[0] == TF_OK;
+    }
+    // the CSR layout of include/tf_hip.h (Merkle Mountain Range calls)
+    static void pack(const std::vector<MmrMembershipProof>& proofs, std::vector<uint64_t>& off, std::vector<Digest>& paths) {
+        off.assign(1, 0);
+        for (const auto& p : proofs) {
+            paths.insert(paths.end(), p.authentication_path.begin(), p.authentication_path.end());
+            off.push_back(paths.size());
+        }
+    }
+};
+
+struct LeafMutation {  // mmr_trait.rs
+    uint64_t leaf_index = 0;
+    Digest new_leaf;
+    MmrMembershipProof membership_proof;
+};
+
+// batch_mutate_leaf_and_update_mps, or with peaks == nullptr batch_update_from_batch_leaf_mutation: the proofs are updated in place and
+// the indices of those that changed are returned
+inline std::vector<size_t> mmr_batch_mutate(uint64_t leaf_count, std::vector<Digest>* peaks, std::vector<MmrMembershipProof>& proofs,
+                                            const std::vector<uint64_t>& proof_indices, const std::vector<LeafMutation>& mutations) {
+    if (proof_indices.size() != proofs.size()) throw std::invalid_argument("Lists must have same length");
+    std::vector<uint64_t> midx, moff, poff;
+    std::vector<Digest> leafs, mpaths, ppaths;
+    std::vector<MmrMembershipProof> mp;
+    for (const auto& m : mutations) {
+        midx.push_back(m.leaf_index);
+        leafs.push_back(m.new_leaf);
+        mp.push_back(m.membership_proof);
+    }
+    MmrMembershipProof::pack(mp, moff, mpaths);
+    MmrMembershipProof::pack(proofs, poff, ppaths);
+    std::vector<int> mod(proofs.size() + 1);
+    check(tf_mmr_batch_mutate_leafs(leaf_count, peaks ? reinterpret_cast<uint64_t*>(peaks->data()) : nullptr, mutations.size(), midx.data(),
+                                    reinterpret_cast<const uint64_t*>(leafs.data()), moff.data(), reinterpret_cast<const uint64_t*>(mpaths.data()),
+                                    proofs.size(), proof_indices.data(), poff.data(), reinterpret_cast<uint64_t*>(ppaths.data()), mod.data()),
+          "batch_mutate_leaf_and_update_mps");
+    std::vector<size_t> changed;
+    for (size_t p = 0; p < proofs.size(); ++p) {
+        proofs[p].authentication_path.assign(ppaths.begin() + (long)poff[p], ppaths.begin() + (long)poff[p + 1]);
+        if (mod[p]) changed.push_back(p);
+    }
+    return changed;
+}
+
+struct MmrAccumulator {  // mmr_accumulator.rs
+    uint64_t leaf_count = 0;
+    std::vector<Digest> peaks;  // highest first
+
+    static MmrAccumulator new_from_leafs(const std::vector<Digest>& leafs) {  // :29-115
+        MmrAccumulator a;
+        a.append_many(leafs, false);
+        return a;
+    }
+    uint64_t num_leafs() const { return leaf_count; }
+    Digest bag_peaks() const {  // :379-391
+        Digest out;
+        check(tf_mmr_bag_peaks(&leaf_count, 1, reinterpret_cast<const uint64_t*>(peaks.data()), reinterpret_cast<uint64_t*>(&out)), "bag_peaks");
+        return out;
+    }
+    // k successive appends (:149-159) in one call; their membership proofs if `proofs`
+    std::vector<MmrMembershipProof> append_many(const std::vector<Digest>& leafs, bool proofs = true) {
+        const uint64_t n = leaf_count, k = leafs.size();
+        std::vector<size_t> lens;
+        size_t total = 0;
+        for (uint64_t i = 0; i < k; ++i) total += lens.emplace_back(__builtin_ctzll(~(n + i)));
+        std::vector<Digest> next(__builtin_popcountll(n + k) + 1), flat(total + 1);  // (+ 1: never an empty buffer)
+        check(tf_mmr_append(n, reinterpret_cast<const uint64_t*>(peaks.data()), reinterpret_cast<const uint64_t*>(leafs.data()), k,
+                            reinterpret_cast<uint64_t*>(next.data()), proofs ? reinterpret_cast<uint64_t*>(flat.data()) : nullptr),
+              "MmrAccumulator::append");
+        next.pop_back();
+        peaks = next;
+        leaf_count = n + k;
+        std::vector<MmrMembershipProof> out;
+        if (!proofs) return out;
+        size_t off = 0;
+        for (size_t L : lens) {
+            out.push_back({std::vector<Digest>(flat.begin() + (long)off, flat.begin() + (long)(off + L))});
+            off += L;
+        }
+        return out;
+    }
+    MmrMembershipProof append(const Digest& leaf) { return append_many({leaf})[0]; }
+    void mutate_leaf(const LeafMutation& m) {  // :164-175
+        std::vector<MmrMembershipProof> none;
+        mmr_batch_mutate(leaf_count, &peaks, none, {}, {m});
+    }
+    std::vector<size_t> batch_mutate_leaf_and_update_mps(std::vector<MmrMembershipProof>& proofs, const std::vector<uint64_t>& indices,
+                                                         const std::vector<LeafMutation>& mutations) {  // :180-302
+        return mmr_batch_mutate(leaf_count, &peaks, proofs, indices, mutations);
+    }
+};
+
 }  // namespace twenty_first
