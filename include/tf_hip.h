@@ -527,6 +527,34 @@ int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t *d_peaks, size_t
                                   const uint64_t *own_offsets, uint64_t *d_own_paths, int *d_modified, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batch inversion.   replaces  FiniteField::batch_inversion   math/traits.rs:93-121  (Montgomery's trick over a Vec<Self>)
+ *                               Inverse::inverse_or_zero       math/traits.rs:39-45   (element by element)
+ * `n` counts ELEMENTS: a BFieldElement is 1 word, an XFieldElement 3 words [c0, c1, c2] (x_field_element.rs:217-231); inputs are
+ * raw Montgomery words below p, as everywhere in this ABI.
+ *   out[i] = in[i]^-1, canonical raw words.  The inverse is unique, so the words are BFieldElement::inverse /
+ *            XFieldElement::inverse of each element, and the reference's batch_inversion output (traits.rs:111-118).
+ *   n == 0   TF_OK, nothing touched (the reference returns an empty Vec, :95-97).  A NULL pointer with n > 0: TF_ERR_NULL_POINTER.
+ *   zero     batch_inversion: any zero element -> TF_ERR_INVERSE_OF_ZERO (the reference's assert!, traits.rs:106).  The host form
+ *            and the plain _dev form copy a flag back, so they block once (as tf_poly_interpolate_*_dev); _dev_async follows the
+ *            contract of the asynchronous variants above: it writes 12 to d_status (first non-zero code wins) and never
+ *            synchronises.  The output of a failed call is unspecified.  An XFieldElement is zero only when all three words are:
+ *            (a, 0, 0) and (0, a, 0) with a != 0 are inverted.
+ *            inverse_or_zero: zero -> zero, anything else -> its inverse (traits.rs:39-45); it never fails on values, and its _dev
+ *            form only enqueues.
+ *   in == out is allowed (the reference consumes its Vec and returns it, :113); a partial overlap is not.
+ * Each wave inverts 64 K consecutive elements with one exponentiation (csrc/inverse_kernels.h). */
+int tf_batch_inversion_bfe(const uint64_t *in, size_t n, uint64_t *out);
+int tf_batch_inversion_xfe(const uint64_t *in, size_t n, uint64_t *out);
+int tf_batch_inversion_bfe_dev(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream);
+int tf_batch_inversion_xfe_dev(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream);
+int tf_batch_inversion_bfe_dev_async(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream, int *d_status);
+int tf_batch_inversion_xfe_dev_async(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream, int *d_status);
+int tf_inverse_or_zero_bfe(const uint64_t *in, size_t n, uint64_t *out);
+int tf_inverse_or_zero_xfe(const uint64_t *in, size_t n, uint64_t *out);
+int tf_inverse_or_zero_bfe_dev(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream);
+int tf_inverse_or_zero_xfe_dev(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the
  * first call); every other TF_* switch of DESIGN_HISTORY.md exists in the laboratory build alone (TF_AB_BUILD, below).
  *   TF_NTT_TILE_BYTES : bytes of batch processed between the passes of a multi-pass NTT (scratch size),

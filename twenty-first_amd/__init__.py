@@ -26,7 +26,7 @@ import numpy as np
 from . import _lib
 
 __all__ = [
-    "P", "BFieldElement", "ntt", "intt", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
+    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
     "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "set_device", "get_device", "shard_range",
 ]
 
@@ -288,6 +288,33 @@ def poly_divide(dividends: np.ndarray, divisor: np.ndarray, width: int = 1, batc
     out = lambda x: None if x is None else _ptr(x if x.size else pad)  # noqa: E731
     _check(fn(_ptr(a if a.size else pad), na, batch, _ptr(b if b.size else pad), nb, out(q), out(r)), "divide")
     return q, r
+
+
+def _elements(x, width: int, name: str) -> np.ndarray:
+    x = _words(np.ascontiguousarray(x, dtype=np.uint64).reshape(-1), name)
+    if width not in (1, 3) or x.size % width:
+        raise ValueError(f"{name} must hold whole elements of `width` (1 or 3) words")
+    return x
+
+
+def batch_inversion(x: np.ndarray, width: int = 1) -> np.ndarray:
+    """FiniteField::batch_inversion (math/traits.rs:93-121): the inverses of a vector of BFieldElements (width 1) or
+    XFieldElements (width 3, three raw words each), as a new array.  A zero element panics (NttPanic code 12, the reference's
+    assert! at :106)."""
+    x = _elements(x, width, "x")
+    out = np.empty_like(x)
+    fn = lib().tf_batch_inversion_bfe if width == 1 else lib().tf_batch_inversion_xfe
+    _check(fn(_ptr(x), x.size // width, _ptr(out)), "batch_inversion")
+    return out
+
+
+def inverse_or_zero(x: np.ndarray, width: int = 1) -> np.ndarray:
+    """Inverse::inverse_or_zero (math/traits.rs:39-45) of every element of a vector: zero stays zero."""
+    x = _elements(x, width, "x")
+    out = np.empty_like(x)
+    fn = lib().tf_inverse_or_zero_bfe if width == 1 else lib().tf_inverse_or_zero_xfe
+    _check(fn(_ptr(x), x.size // width, _ptr(out)), "inverse_or_zero")
+    return out
 
 
 class Polynomial:

@@ -103,6 +103,16 @@ SIGNATURES = {
     "tf_poly_fps_inverse_newton_bfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "tf_poly_fps_inverse_newton_xfe_dev": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "tf_poly_fps_inverse_newton_len": (_sz, [_sz, _sz]),
+    "tf_batch_inversion_bfe": (C.c_int, [_vp, _sz, _vp]),
+    "tf_batch_inversion_xfe": (C.c_int, [_vp, _sz, _vp]),
+    "tf_batch_inversion_bfe_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "tf_batch_inversion_xfe_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "tf_batch_inversion_bfe_dev_async": (C.c_int, [_vp, _sz, _vp, _vp, _vp]),
+    "tf_batch_inversion_xfe_dev_async": (C.c_int, [_vp, _sz, _vp, _vp, _vp]),
+    "tf_inverse_or_zero_bfe": (C.c_int, [_vp, _sz, _vp]),
+    "tf_inverse_or_zero_xfe": (C.c_int, [_vp, _sz, _vp]),
+    "tf_inverse_or_zero_bfe_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "tf_inverse_or_zero_xfe_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
     "tf_zerofier_tree_new_bfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_xfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_bfe_dev": (C.c_int, [_vp, _sz, _vp, C.POINTER(C.c_void_p)]),

@@ -892,6 +892,31 @@ int tf_poly_fps_inverse_newton_xfe_dev(const uint64_t* d_f, size_t nf, size_t pr
     if (!d_status) return TF_ERR_NULL_POINTER;
     return fps_dev(d_f, nf, precision, d_out, stream, d_status, 3);
 } TF_ABI_CATCH
+// FiniteField::batch_inversion / Inverse::inverse_or_zero over a vector (tf_inverse.hip)
+int tf_batch_inversion_bfe(const uint64_t* in, size_t n, uint64_t* out) try { return batch_inverse_host(in, n, out, 1, false); } TF_ABI_CATCH
+int tf_batch_inversion_xfe(const uint64_t* in, size_t n, uint64_t* out) try { return batch_inverse_host(in, n, out, 3, false); } TF_ABI_CATCH
+int tf_batch_inversion_bfe_dev(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream) try {
+    return batch_inverse_dev(d_in, n, d_out, 1, false, stream, nullptr);
+} TF_ABI_CATCH
+int tf_batch_inversion_xfe_dev(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream) try {
+    return batch_inverse_dev(d_in, n, d_out, 3, false, stream, nullptr);
+} TF_ABI_CATCH
+int tf_batch_inversion_bfe_dev_async(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream, int* d_status) try {
+    if (n && !d_status) return TF_ERR_NULL_POINTER;
+    return batch_inverse_dev(d_in, n, d_out, 1, false, stream, d_status);
+} TF_ABI_CATCH
+int tf_batch_inversion_xfe_dev_async(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream, int* d_status) try {
+    if (n && !d_status) return TF_ERR_NULL_POINTER;
+    return batch_inverse_dev(d_in, n, d_out, 3, false, stream, d_status);
+} TF_ABI_CATCH
+int tf_inverse_or_zero_bfe(const uint64_t* in, size_t n, uint64_t* out) try { return batch_inverse_host(in, n, out, 1, true); } TF_ABI_CATCH
+int tf_inverse_or_zero_xfe(const uint64_t* in, size_t n, uint64_t* out) try { return batch_inverse_host(in, n, out, 3, true); } TF_ABI_CATCH
+int tf_inverse_or_zero_bfe_dev(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream) try {
+    return batch_inverse_dev(d_in, n, d_out, 1, true, stream, nullptr);
+} TF_ABI_CATCH
+int tf_inverse_or_zero_xfe_dev(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream) try {
+    return batch_inverse_dev(d_in, n, d_out, 3, true, stream, nullptr);
+} TF_ABI_CATCH
 static int coset_extrapolate_host(uint64_t offset, const uint64_t* cw, size_t n, size_t batch, const uint64_t* pts, size_t np,
                                   uint64_t* out, int L) {
     if (n == 0) return TF_ERR_LEN_NOT_POWER_OF_TWO;

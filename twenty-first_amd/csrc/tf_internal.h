@@ -9,6 +9,7 @@
 //   tf_proof.hip  batched verification of Merkle inclusion proofs (proof_kernels.h)
 //   tf_mmr.hip    batched Merkle Mountain Range accumulators and membership proofs (mmr_kernels.h), with their host flavours
 //   tf_divide.hip division with remainder and the power-series inverse (divide_kernels.h), with their entry points
+//   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -208,6 +209,12 @@ int divide_host(const u64* a, size_t na, size_t batch, const u64* b, size_t nb, 
 size_t fps_len(size_t nf, size_t precision);
 int fps_dev(const u64* f, size_t nf, size_t precision, u64* out, void* stream, int* status, int L);
 int fps_host(const u64* f, size_t nf, size_t precision, u64* out, int L);
+
+// ------------------------------------------------------------------------------------ tf_inverse.hip
+// FiniteField::batch_inversion (or_zero = false) / inverse_or_zero (or_zero = true) of n elements of L words (include/tf_hip.h has the
+// contract); _dev: device pointers, d_status as the _dev_async entry points (null: a blocking check of a flag word), _host: host pointers
+int batch_inverse_dev(const u64* in, size_t n, u64* out, int L, bool or_zero, void* stream, int* d_status);
+int batch_inverse_host(const u64* in, size_t n, u64* out, int L, bool or_zero);
 
 // ------------------------------------------------------------------------------------ tf_poly.hip
 extern std::atomic<int> g_batch_eval_route;

@@ -358,6 +358,37 @@ def fps_inverse_newton(f, precision: int, out, width: int = 1, stream=None, stat
         _chk(int(st.item()), "formal_power_series_inverse_newton")
 
 
+def _inversion_args(x, out, width):
+    x, out = _t(x, "x"), _t(out, "out")
+    w = _width(width)
+    _need(x.numel() % w == 0 and out.numel() == x.numel(), "x and out must hold the same number of whole elements")
+    nbytes = x.numel() * 8
+    _need(out.data_ptr() == x.data_ptr() or out.data_ptr() >= x.data_ptr() + nbytes or x.data_ptr() >= out.data_ptr() + nbytes,
+          "out must be x itself or not overlap it")
+    return x, out, x.numel() // w
+
+
+def batch_inversion(x, out, width: int = 1, stream=None, status=None) -> None:
+    """FiniteField::batch_inversion (math/traits.rs:93-121) on device buffers: out[i] = x[i]^-1; out may be x.  Without status a zero
+    element raises NttPanic (code 12) after the call has synchronised once to read its flag; with status (see _status) nothing is
+    synchronised and a zero element writes 12 there."""
+    x, out, n = _inversion_args(x, out, width)
+    if status is not None:
+        fn = _lib.lib().tf_batch_inversion_bfe_dev_async if width == 1 else _lib.lib().tf_batch_inversion_xfe_dev_async
+        _chk(fn(_p(x), n, _p(out), _stream(stream), _status(status)), "batch_inversion")
+        return
+    fn = _lib.lib().tf_batch_inversion_bfe_dev if width == 1 else _lib.lib().tf_batch_inversion_xfe_dev
+    _chk(fn(_p(x), n, _p(out), _stream(stream)), "batch_inversion")
+
+
+def inverse_or_zero(x, out, width: int = 1, stream=None) -> None:
+    """Inverse::inverse_or_zero (math/traits.rs:39-45) of every element on device buffers (zero stays zero); out may be x.  Only
+    enqueues."""
+    x, out, n = _inversion_args(x, out, width)
+    fn = _lib.lib().tf_inverse_or_zero_bfe_dev if width == 1 else _lib.lib().tf_inverse_or_zero_xfe_dev
+    _chk(fn(_p(x), n, _p(out), _stream(stream)), "inverse_or_zero")
+
+
 def zerofier(roots, out, width: int = 1, stream=None) -> None:
     """Polynomial::zerofier (math/polynomial.rs:1435-1441) on device buffers: out = the n + 1 coefficients of prod (x - roots[i])."""
     roots, out = _t(roots, "roots"), _t(out, "out")

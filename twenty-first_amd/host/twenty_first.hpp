@@ -131,6 +131,30 @@ inline void ntt_batch_multi(XFieldElement* x, size_t n, size_t batch, const std:
           inverse ? "intt" : "ntt");
 }
 
+// ---- FiniteField::batch_inversion (math/traits.rs:93-121) / Inverse::inverse_or_zero (:39-45) over a whole vector --------------
+// batch_inversion consumes its input and returns it inverted, as the reference does; a zero element panics (NttPanic, code 12, :106)
+inline std::vector<BFieldElement> batch_inversion(std::vector<BFieldElement> input) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(input.data());
+    check(tf_batch_inversion_bfe(p, input.size(), p), "batch_inversion");
+    return input;
+}
+inline std::vector<XFieldElement> batch_inversion(std::vector<XFieldElement> input) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(input.data());
+    check(tf_batch_inversion_xfe(p, input.size(), p), "batch_inversion");
+    return input;
+}
+// every element's inverse_or_zero: zero stays zero
+inline std::vector<BFieldElement> inverse_or_zero(std::vector<BFieldElement> input) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(input.data());
+    check(tf_inverse_or_zero_bfe(p, input.size(), p), "inverse_or_zero");
+    return input;
+}
+inline std::vector<XFieldElement> inverse_or_zero(std::vector<XFieldElement> input) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(input.data());
+    check(tf_inverse_or_zero_xfe(p, input.size(), p), "inverse_or_zero");
+    return input;
+}
+
 // ---- Polynomial (math/polynomial.rs:78-84): only the hot-path members ------------------------------
 template <class FF>
 struct Polynomial {
