@@ -68,7 +68,8 @@ enum tf_status {
     TF_ERR_MMR_LEAF_INDEX_OUT_OF_RANGE = 22,     /* leaf_index >= num_leafs  :43-46 */
     TF_ERR_MMR_PEAK_COUNT_MISMATCH = 23,         /* peaks.len() != num_leafs.count_ones()  :50-54 */
     TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH = 24,   /* authentication path length != height of the leaf's peak  :56-60 */
-    TF_ERR_MMR_PEAK_MISMATCH = 25                /* the path does not hash to the leaf's peak  :76 */
+    TF_ERR_MMR_PEAK_MISMATCH = 25,               /* the path does not hash to the leaf's peak  :76 */
+    TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO = 26     /* Tip5::sample_indices panic: assert!(upper_bound.is_power_of_two())  tip5/mod.rs:637 */
 };
 
 /* Human-readable name of a status code. */
@@ -525,6 +526,47 @@ int tf_mmr_batch_mutate_leafs(uint64_t leaf_count, uint64_t *peaks, size_t n_mut
 int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t *d_peaks, size_t n_mut, const uint64_t *mut_indices, const uint64_t *d_new_leafs,
                                   const uint64_t *mut_offsets, const uint64_t *d_mut_paths, size_t n_own, const uint64_t *own_indices,
                                   const uint64_t *own_offsets, uint64_t *d_own_paths, int *d_modified, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tip5 sponges.     replaces  Tip5::new(Domain)              tip5/mod.rs:511-526
+ *                             Sponge::absorb / squeeze       :684-698   (overwrite-mode absorb; squeeze = the rate words, THEN the permutation)
+ *                             Sponge::pad_and_absorb_all     util_types/sponge.rs:41-55
+ *                             Tip5::sample_indices / sample_scalars   tip5/mod.rs:636-674
+ * A batch of `count` independent sponges is count x 16 raw Montgomery words (the layout of tf_tip5_permute).  Every call advances all
+ * of them and is ONE kernel launch (plus, for a ragged absorb, the upload of its offsets); every result is word for word that of the
+ * reference function applied to each sponge on its own.  The `_dev` forms take device pointers and enqueue on `stream` without
+ * waiting for it: states, rows and roots that are already in device memory are absorbed where they lie.
+ *   init               all words 0 (fixed_length == 0, Domain::VariableLength) or words 10..15 = ONE (Domain::FixedLength).
+ *   absorb             n_chunks successive absorb calls per sponge; input: count x n_chunks x 10 words.
+ *   pad_and_absorb_all offsets == NULL: sponge i absorbs the `len` words at input + i len.  Otherwise offsets is a HOST array (in the
+ *                      _dev form too) of count + 1 non-decreasing word offsets, sponge i absorbs input[offsets[i] .. offsets[i + 1]) and
+ *                      len is ignored; the offsets reach the device through pinned staging, the stream is not waited for.  A length
+ *                      of 0 is legal (one padding block).
+ *   squeeze            n_squeezes successive squeeze calls per sponge; out: count x n_squeezes x 10 words.
+ *   sample_scalars     ceil(3 num_elements / 10) squeezes; element e is words 3 e .. 3 e + 2 of their concatenation ([c0, c1, c2],
+ *                      XFieldElement::new), the unused tail of the last squeeze is dropped; out: count x num_elements x 3 words.
+ *   sample_indices     squeeze whenever the ten-element buffer is used up; an element equal to BFieldElement::MAX (p - 1) is
+ *                      skipped, any other yields (value() as u32) % upper_bound; stops after num_indices, the rest of the buffer
+ *                      is discarded.  out_u32: count x num_indices uint32_t.  The number of squeezes depends on the data (an
+ *                      element is MAX with probability 2^-64), so sponges of one call may end after different numbers of steps.
+ * count == 0 -> TF_OK.  n_chunks / n_squeezes / num_elements / num_indices == 0 -> TF_OK, states untouched.  A NULL pointer with a
+ * non-zero size -> TF_ERR_NULL_POINTER; decreasing offsets -> TF_ERR_INVALID_ARGUMENT; an upper_bound that is not a power of two (0
+ * included) -> TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO.  All of these are returned before a device is touched.
+ * What is absorbed are words: BFieldCodec encoding is the caller's. */
+int tf_tip5_sponge_init(uint64_t *states, size_t count, int fixed_length);
+int tf_tip5_sponge_init_dev(uint64_t *d_states, size_t count, int fixed_length, void *stream);
+int tf_tip5_sponge_absorb(uint64_t *states, size_t count, const uint64_t *input, size_t n_chunks);
+int tf_tip5_sponge_absorb_dev(uint64_t *d_states, size_t count, const uint64_t *d_input, size_t n_chunks, void *stream);
+int tf_tip5_sponge_pad_and_absorb_all(uint64_t *states, size_t count, const uint64_t *input, size_t len, const uint64_t *offsets);
+int tf_tip5_sponge_pad_and_absorb_all_dev(uint64_t *d_states, size_t count, const uint64_t *d_input, size_t len, const uint64_t *offsets,
+                                          void *stream);
+int tf_tip5_sponge_squeeze(uint64_t *states, size_t count, size_t n_squeezes, uint64_t *out);
+int tf_tip5_sponge_squeeze_dev(uint64_t *d_states, size_t count, size_t n_squeezes, uint64_t *d_out, void *stream);
+int tf_tip5_sponge_sample_scalars(uint64_t *states, size_t count, size_t num_elements, uint64_t *out);
+int tf_tip5_sponge_sample_scalars_dev(uint64_t *d_states, size_t count, size_t num_elements, uint64_t *d_out, void *stream);
+int tf_tip5_sponge_sample_indices(uint64_t *states, size_t count, uint32_t upper_bound, size_t num_indices, uint32_t *out_u32);
+int tf_tip5_sponge_sample_indices_dev(uint64_t *d_states, size_t count, uint32_t upper_bound, size_t num_indices, uint32_t *d_out_u32,
+                                      void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batch inversion.   replaces  FiniteField::batch_inversion   math/traits.rs:93-121  (Montgomery's trick over a Vec<Self>)

@@ -673,8 +673,9 @@ class Tip5:
 
 class Tip5Sponge:
     """`batch` independent Tip5 sponges stepped together (impl Sponge for Tip5, tip5/mod.rs:677-699; trait
-    util_types/sponge.rs:33-55).  The state lives in a (batch, 16) array of raw words; every absorb / squeeze is one
-    batched Tip5::permutation on the device."""
+    util_types/sponge.rs:33-55).  The state lives in a (batch, 16) array of raw words; absorb / squeeze are one batched
+    Tip5::permutation on the device each, pad_and_absorb_all and the *_many / sample_* methods one library call (one kernel launch)
+    for all their permutations (include/tf_hip.h, "Tip5 sponges")."""
 
     RATE = Tip5.RATE
 
@@ -704,17 +705,52 @@ class Tip5Sponge:
         return out
 
     def pad_and_absorb_all(self, inp) -> None:
-        """util_types/sponge.rs:41-55: full chunks, then the remainder padded with 1, 0, 0, ...  (equal lengths per sponge)."""
+        """util_types/sponge.rs:41-55: full chunks, then the remainder padded with 1, 0, 0, ...  One library call (one launch) for
+        the whole batch.  inp: an array of batch x len words (equal lengths), or a list / tuple of `batch` rows of unequal length."""
         b = self.state.shape[0]
+        st = self.state.reshape(-1)
+        if isinstance(inp, (list, tuple)) and len(inp) == b and all(np.ndim(r) == 1 for r in inp):
+            rows = [np.ascontiguousarray(r, dtype=np.uint64) for r in inp]
+            off = np.zeros(b + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([r.size for r in rows], dtype=np.uint64)
+            a = np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint64)
+            _check(lib().tf_tip5_sponge_pad_and_absorb_all(_ptr(st), b, _ptr(a), 0, _ptr(off)), "Sponge::pad_and_absorb_all")
+            return
         a = np.ascontiguousarray(inp, dtype=np.uint64).reshape(b, -1)
-        full = a.shape[1] // Tip5.RATE
-        for c in range(full):
-            self.absorb(a[:, c * Tip5.RATE:(c + 1) * Tip5.RATE])
-        rem = a.shape[1] - full * Tip5.RATE
-        last = np.zeros((b, Tip5.RATE), dtype=np.uint64)
-        last[:, :rem] = a[:, full * Tip5.RATE:]
-        last[:, rem] = BFieldElement.ONE_RAW
-        self.absorb(last)
+        _check(lib().tf_tip5_sponge_pad_and_absorb_all(_ptr(st), b, _ptr(a), a.shape[1], None), "Sponge::pad_and_absorb_all")
+
+    def absorb_many(self, chunks) -> None:
+        """k successive absorb calls per sponge in one library call: chunks holds batch x k x RATE words."""
+        b = self.state.shape[0]
+        a = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(b, -1)
+        if a.shape[1] % Tip5.RATE:
+            raise ValueError("chunks must hold a multiple of RATE words per sponge")
+        _check(lib().tf_tip5_sponge_absorb(_ptr(self.state.reshape(-1)), b, _ptr(a), a.shape[1] // Tip5.RATE), "Sponge::absorb")
+
+    def squeeze_many(self, k: int) -> np.ndarray:
+        """k successive squeeze calls per sponge in one library call -> (batch, k, RATE) raw words."""
+        b = self.state.shape[0]
+        out = np.empty((b, k, Tip5.RATE), dtype=np.uint64)
+        _check(lib().tf_tip5_sponge_squeeze(_ptr(self.state.reshape(-1)), b, k, _ptr(out)), "Sponge::squeeze")
+        return out
+
+    def sample_scalars(self, num_elements: int) -> np.ndarray:
+        """Tip5::sample_scalars (tip5/mod.rs:664-674) per sponge -> (batch, num_elements, 3) raw words, [c0, c1, c2] each."""
+        b = self.state.shape[0]
+        out = np.empty((b, num_elements, 3), dtype=np.uint64)
+        _check(lib().tf_tip5_sponge_sample_scalars(_ptr(self.state.reshape(-1)), b, num_elements, _ptr(out)), "Tip5::sample_scalars")
+        return out
+
+    def sample_indices(self, upper_bound: int, num_indices: int) -> np.ndarray:
+        """Tip5::sample_indices (tip5/mod.rs:636-656) per sponge -> (batch, num_indices) uint32; upper_bound must be a power of
+        two (the reference's assert!: TwentyFirstError with status 26 otherwise)."""
+        if not 0 <= upper_bound < 2 ** 32:
+            raise ValueError("upper_bound is a u32")
+        b = self.state.shape[0]
+        out = np.empty((b, num_indices), dtype=np.uint32)
+        _check(lib().tf_tip5_sponge_sample_indices(_ptr(self.state.reshape(-1)), b, upper_bound, num_indices, _ptr(out)),
+               "Tip5::sample_indices")
+        return out
 
 
 # ----------------------------------------------------------------------------- Merkle tree

@@ -154,6 +154,18 @@ SIGNATURES = {
     "tf_mmr_verify_membership_proofs_dev": (C.c_int, [C.c_uint64, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_mmr_batch_mutate_leafs": (C.c_int, [C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "tf_mmr_batch_mutate_leafs_dev": (C.c_int, [C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "tf_tip5_sponge_init": (C.c_int, [_vp, _sz, C.c_int]),
+    "tf_tip5_sponge_init_dev": (C.c_int, [_vp, _sz, C.c_int, _vp]),
+    "tf_tip5_sponge_absorb": (C.c_int, [_vp, _sz, _vp, _sz]),
+    "tf_tip5_sponge_absorb_dev": (C.c_int, [_vp, _sz, _vp, _sz, _vp]),
+    "tf_tip5_sponge_pad_and_absorb_all": (C.c_int, [_vp, _sz, _vp, _sz, _vp]),
+    "tf_tip5_sponge_pad_and_absorb_all_dev": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _vp]),
+    "tf_tip5_sponge_squeeze": (C.c_int, [_vp, _sz, _sz, _vp]),
+    "tf_tip5_sponge_squeeze_dev": (C.c_int, [_vp, _sz, _sz, _vp, _vp]),
+    "tf_tip5_sponge_sample_scalars": (C.c_int, [_vp, _sz, _sz, _vp]),
+    "tf_tip5_sponge_sample_scalars_dev": (C.c_int, [_vp, _sz, _sz, _vp, _vp]),
+    "tf_tip5_sponge_sample_indices": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp]),
+    "tf_tip5_sponge_sample_indices_dev": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _vp]),
     "tf_merkle_verify_proofs": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_merkle_verify_proofs_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_merkle_authentication_paths": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -184,6 +184,7 @@ const char* tf_status_string(int status) {
         case TF_ERR_MMR_PEAK_COUNT_MISMATCH: return "TF_ERR_MMR_PEAK_COUNT_MISMATCH";
         case TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH: return "TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH";
         case TF_ERR_MMR_PEAK_MISMATCH: return "TF_ERR_MMR_PEAK_MISMATCH";
+        case TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO: return "TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO";
         default: return "TF_ERR_UNKNOWN";
     }
 }
@@ -1053,6 +1054,48 @@ int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t* d_peaks, size_t
                                   const uint64_t* own_offsets, uint64_t* d_own_paths, int* d_modified, void* stream) try {
     return mmr_mutate_dev(leaf_count, d_peaks, n_mut, mut_indices, d_new_leafs, mut_offsets, d_mut_paths, n_own, own_indices, own_offsets,
                           d_own_paths, d_modified, 0, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+
+// ---- device-resident Tip5 sponges (tf_sponge.hip)
+int tf_tip5_sponge_init(uint64_t* states, size_t count, int fixed_length) try {
+    return sponge_init_host(states, count, fixed_length);
+} TF_ABI_CATCH
+int tf_tip5_sponge_init_dev(uint64_t* d_states, size_t count, int fixed_length, void* stream) try {
+    return sponge_init_dev(d_states, count, fixed_length, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_tip5_sponge_absorb(uint64_t* states, size_t count, const uint64_t* input, size_t n_chunks) try {
+    if (n_chunks > (size_t(1) << 56)) return TF_ERR_INVALID_ARGUMENT;
+    return sponge_absorb_host(states, count, input, 10 * n_chunks, nullptr, false);
+} TF_ABI_CATCH
+int tf_tip5_sponge_absorb_dev(uint64_t* d_states, size_t count, const uint64_t* d_input, size_t n_chunks, void* stream) try {
+    if (n_chunks > (size_t(1) << 56)) return TF_ERR_INVALID_ARGUMENT;
+    return sponge_absorb_dev(d_states, count, d_input, 10 * n_chunks, nullptr, false, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_tip5_sponge_pad_and_absorb_all(uint64_t* states, size_t count, const uint64_t* input, size_t len, const uint64_t* offsets) try {
+    return sponge_absorb_host(states, count, input, len, offsets, true);
+} TF_ABI_CATCH
+int tf_tip5_sponge_pad_and_absorb_all_dev(uint64_t* d_states, size_t count, const uint64_t* d_input, size_t len, const uint64_t* offsets,
+                                          void* stream) try {
+    return sponge_absorb_dev(d_states, count, d_input, len, offsets, true, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_tip5_sponge_squeeze(uint64_t* states, size_t count, size_t n_squeezes, uint64_t* out) try {
+    return sponge_squeeze_host(states, count, n_squeezes, 10, out);
+} TF_ABI_CATCH
+int tf_tip5_sponge_squeeze_dev(uint64_t* d_states, size_t count, size_t n_squeezes, uint64_t* d_out, void* stream) try {
+    return sponge_squeeze_dev(d_states, count, n_squeezes, 10, d_out, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_tip5_sponge_sample_scalars(uint64_t* states, size_t count, size_t num_elements, uint64_t* out) try {
+    return sponge_squeeze_host(states, count, num_elements, 3, out);
+} TF_ABI_CATCH
+int tf_tip5_sponge_sample_scalars_dev(uint64_t* d_states, size_t count, size_t num_elements, uint64_t* d_out, void* stream) try {
+    return sponge_squeeze_dev(d_states, count, num_elements, 3, d_out, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_tip5_sponge_sample_indices(uint64_t* states, size_t count, uint32_t upper_bound, size_t num_indices, uint32_t* out_u32) try {
+    return sponge_indices_host(states, count, upper_bound, num_indices, out_u32);
+} TF_ABI_CATCH
+int tf_tip5_sponge_sample_indices_dev(uint64_t* d_states, size_t count, uint32_t upper_bound, size_t num_indices, uint32_t* d_out_u32,
+                                      void* stream) try {
+    return sponge_indices_dev(d_states, count, upper_bound, num_indices, d_out_u32, static_cast<hipStream_t>(stream));
 } TF_ABI_CATCH
 
 }  // extern "C"

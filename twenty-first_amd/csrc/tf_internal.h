@@ -162,6 +162,27 @@ int merkle_from_rows_dev(const u64* d_rows, size_t row_len, size_t n_rows, u64* 
 int merkle_from_columns_dev(const u64* d_table, size_t n_rows, size_t n_cols, int width, size_t col_stride, u64* d_nodes, size_t batch, void* stream);
 int gather_digests_dev(const u64* d_nodes, const unsigned long long* d_idx, size_t count, u64* d_out, hipStream_t s);
 extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (canonical values; tf_tip5.hip)
+// the planner's rules for a launch of `count` permutation chains (tf_tip5.hip has the measurements behind them)
+constexpr long long kCoopMaxCount = 1ll << 13;
+static_assert(kCoopMaxCount >= 64 && (kCoopMaxCount & (kCoopMaxCount - 1)) == 0, "a power of two: the level at which a tree narrows is found by halving");
+
+// Round 6: a launch of at most 8 permutation chains per compute unit leaves half the chip's 16-lane rows idle; it runs every chain on a row
+// PAIR instead (tip5_permutation_coop2: the circulant's sixteen rotation terms split over the two rows; 2.01 -> 1.68 us per permutation,
+// profiles/r06_microbench_coop2.txt).  A workgroup then holds 8 chains, so up to this count every workgroup still has a CU of its own.
+inline bool coop_two_rows(long long chains) {
+    static const bool off = ab_env("TF_TIP5_NO_COOP2") != nullptr;  // A/B switch
+    return !off && chains <= 8ll * device_cus();
+}
+// grid of a matrix-pipe launch: one workgroup (4 waves x 16 permutations) per 64 items, capped at kMxBlocksPerCu per CU -- beyond
+// that the waves walk the items with a grid stride, so the tables are staged once per wave and not once per 16 items (8 workgroups
+// are resident per CU at the kernels' VGPR count; 56 keeps the hardware's dynamic balancing: measured 7 / 14 / 28 / 56 / no cap on
+// the 2^24-leaf tree: 4.87 / 5.00 / 5.06 / 5.07 / 5.06 G leaves/s, profiles/r05_tip5_grid_cap.txt)
+constexpr long long kMxBlocksPerCu = 56;
+inline unsigned mx_blocks(long long count) {
+    const long long cap = (long long)device_cus() * kMxBlocksPerCu;
+    const long long want = (count + 63) / 64;
+    return (unsigned)(want < cap ? want : cap);
+}
 
 // ------------------------------------------------------------------------------------ tf_proof.hip
 // page-locked staging for descriptors built on the host (shared with tf_mmr.hip): stage_acquire hands out a block of at least `bytes`
@@ -193,6 +214,19 @@ int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, c
                    const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified, uint64_t mbase, uint64_t pbase, hipStream_t s);
 int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, const u64* leafs, const uint64_t* moff, const u64* mpaths, size_t P,
                     const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified);
+
+// ------------------------------------------------------------------------------------ tf_sponge.hip
+// the sponge calls of include/tf_hip.h.  absorb: pad = false, len = 10 n_chunks, no offsets; pad_and_absorb_all: pad = true (the _dev
+// form indexes `in` from in_base, as merkle_proofs_dev).  squeeze: per_sponge = n_squeezes, words_each = 10; sample_scalars:
+// per_sponge = num_elements, words_each = 3.
+int sponge_init_dev(u64* states, size_t count, int fixed_length, hipStream_t s);
+int sponge_init_host(u64* states, size_t count, int fixed_length);
+int sponge_absorb_dev(u64* states, size_t count, const u64* in, size_t len, const uint64_t* offsets, bool pad, uint64_t in_base, hipStream_t s);
+int sponge_absorb_host(u64* states, size_t count, const u64* in, size_t len, const uint64_t* offsets, bool pad);
+int sponge_squeeze_dev(u64* states, size_t count, size_t per_sponge, size_t words_each, u64* out, hipStream_t s);
+int sponge_squeeze_host(u64* states, size_t count, size_t per_sponge, size_t words_each, u64* out);
+int sponge_indices_dev(u64* states, size_t count, uint32_t upper_bound, size_t num, uint32_t* out, hipStream_t s);
+int sponge_indices_host(u64* states, size_t count, uint32_t upper_bound, size_t num, uint32_t* out);
 
 // ------------------------------------------------------------------------------------ tf_abi.hip
 // the host-pointer entry points' plumbing: h2d waits for its upload (pageable host memory), d2h and sync do not / do

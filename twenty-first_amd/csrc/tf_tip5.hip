@@ -51,16 +51,7 @@ int ensure_tip5(DeviceCtx* ctx) {
 // than the chip has SIMD slots): 16 lanes per permutation, ~2.5 us per permutation of a chain.  Everything larger runs in the
 // matrix-pipe form (4 lanes per permutation, MDS on v_mfma_i32_16x16x64_i8 since round 6): crossover measured at 2^13 chains with the f64 form
 // (profiles/r05_tip5_small_times.txt: hash_varlen of 33 words, 2^13 rows 24.4 vs 25.6 us, 2^14 rows 34.6 vs 26.3 us).
-constexpr long long kCoopMaxCount = 1ll << 13;
-static_assert(kCoopMaxCount >= 64 && (kCoopMaxCount & (kCoopMaxCount - 1)) == 0, "a power of two: the level at which a tree narrows is found by halving");
-
-// Round 6: a launch of at most 8 permutation chains per compute unit leaves half the chip's 16-lane rows idle; it runs every chain on a row
-// PAIR instead (tip5_permutation_coop2: the circulant's sixteen rotation terms split over the two rows; 2.01 -> 1.68 us per permutation,
-// profiles/r06_microbench_coop2.txt).  A workgroup then holds 8 chains, so up to this count every workgroup still has a CU of its own.
-inline bool coop_two_rows(long long chains) {
-    static const bool off = ab_env("TF_TIP5_NO_COOP2") != nullptr;  // A/B switch
-    return !off && chains <= 8ll * device_cus();
-}
+// (kCoopMaxCount, coop_two_rows and mx_blocks: tf_internal.h -- tf_sponge.hip plans with the same rules)
 // ... and the subtree launches use a row pair per hash_pair at the levels that have the rows to spare, when every workgroup has a CU of its own
 inline int subtree_two_rows(long long workgroups) {
     static const bool off = ab_env("TF_TIP5_NO_COOP2") != nullptr;  // A/B switch
@@ -69,17 +60,6 @@ inline int subtree_two_rows(long long workgroups) {
 
 // per_tree = 2^shift, or -1
 inline int shift_of(long long per_tree) { return (per_tree > 0 && !(per_tree & (per_tree - 1))) ? __builtin_ctzll((unsigned long long)per_tree) : -1; }
-
-// grid of a matrix-pipe launch: one workgroup (4 waves x 16 permutations) per 64 items, capped at kMxBlocksPerCu per CU -- beyond
-// that the waves walk the items with a grid stride, so the tables are staged once per wave and not once per 16 items (8 workgroups
-// are resident per CU at the kernels' VGPR count; 56 keeps the hardware's dynamic balancing: measured 7 / 14 / 28 / 56 / no cap on
-// the 2^24-leaf tree: 4.87 / 5.00 / 5.06 / 5.07 / 5.06 G leaves/s, profiles/r05_tip5_grid_cap.txt)
-constexpr long long kMxBlocksPerCu = 56;
-inline unsigned mx_blocks(long long count) {
-    const long long cap = (long long)device_cus() * kMxBlocksPerCu;
-    const long long want = (count + 63) / 64;
-    return (unsigned)(want < cap ? want : cap);
-}
 
 void launch_permute_mx(u64* d_states, u64* d_trace, long long count, hipStream_t s) {
     hipLaunchKernelGGL(tfk::tip5_permute_mx_kernel<1>, dim3(mx_blocks(count)), dim3(256), 0, s, d_states, d_trace, count);

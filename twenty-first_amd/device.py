@@ -516,6 +516,80 @@ def merkle_from_columns(table, n_rows: int, n_cols: int, nodes_out, width: int =
     _chk(_lib.lib().tf_merkle_from_columns_dev(_p(table), n_rows, n_cols, width, cs, _p(nodes_out), batch, _stream(stream)), "MerkleTree::par_new")
 
 
+# ----------------------------------------------------------------------------- Tip5 sponges (include/tf_hip.h, "Tip5 sponges")
+# A batch of sponges is a tensor of count x 16 raw words; every call below advances all of them in ONE kernel launch on the stream
+# and synchronises nothing.
+def _sponge_states(states) -> int:
+    states = _t(states, "states")
+    _need(states.numel() % 16 == 0, "states must hold 16 words per Tip5 sponge")
+    return states.numel() // 16
+
+
+def _per_sponge(t, count: int, unit: int, what: str) -> int:
+    """t holds n x unit words for each of count sponges: n."""
+    _need(t.numel() % (unit * count) == 0 if count else t.numel() == 0, what)
+    return t.numel() // (unit * count) if count else 0
+
+
+def tip5_sponge_init_(states, fixed_length: bool = False, stream=None) -> None:
+    """Tip5::new(Domain) (tip5/mod.rs:511-526) into every sponge: all zero, or the capacity words ONE (fixed_length)."""
+    count = _sponge_states(states)
+    _chk(_lib.lib().tf_tip5_sponge_init_dev(_p(states), count, 1 if fixed_length else 0, _stream(stream)), "Tip5::new")
+
+
+def tip5_sponge_absorb_(states, inp, stream=None) -> None:
+    """n_chunks successive Sponge::absorb calls (tip5/mod.rs:684-691) per sponge: inp holds count x n_chunks x 10 words."""
+    count, inp = _sponge_states(states), _t(inp, "input")
+    n_chunks = _per_sponge(inp, count, 10, "input must hold n_chunks x 10 words per sponge")
+    _chk(_lib.lib().tf_tip5_sponge_absorb_dev(_p(states), count, _p(inp), n_chunks, _stream(stream)), "Sponge::absorb")
+
+
+def tip5_sponge_pad_and_absorb_all_(states, inp, offsets=None, stream=None) -> None:
+    """Sponge::pad_and_absorb_all (util_types/sponge.rs:41-55).  offsets None: inp holds the same number of words for every sponge.
+    Otherwise offsets is a HOST array of count + 1 non-decreasing word offsets into inp and sponge i absorbs
+    inp[offsets[i] : offsets[i + 1]] (a length of 0 is one padding block)."""
+    count, inp = _sponge_states(states), _t(inp, "input")
+    if offsets is None:
+        length = _per_sponge(inp, count, 1, "input must hold the same number of words for every sponge")
+        _chk(_lib.lib().tf_tip5_sponge_pad_and_absorb_all_dev(_p(states), count, _p(inp), length, None, _stream(stream)),
+             "Sponge::pad_and_absorb_all")
+        return
+    off = _u64_host(offsets)
+    _need(off.size == count + 1, "offsets must hold count + 1 entries")
+    # (the library refuses decreasing offsets before it touches the device, so the last one bounds them all)
+    _need(count == 0 or int(off[-1]) <= inp.numel(), "offsets reach beyond the input")
+    _chk(_lib.lib().tf_tip5_sponge_pad_and_absorb_all_dev(_p(states), count, _p(inp), 0, _host(off), _stream(stream)),
+         "Sponge::pad_and_absorb_all")
+
+
+def tip5_sponge_squeeze(states, out, stream=None) -> None:
+    """n_squeezes successive Sponge::squeeze calls (tip5/mod.rs:693-698) per sponge: out receives count x n_squeezes x 10 words."""
+    count, out = _sponge_states(states), _t(out, "out")
+    n = _per_sponge(out, count, 10, "out must hold n_squeezes x 10 words per sponge")
+    _chk(_lib.lib().tf_tip5_sponge_squeeze_dev(_p(states), count, n, _p(out), _stream(stream)), "Sponge::squeeze")
+
+
+def tip5_sponge_sample_scalars(states, out, stream=None) -> None:
+    """Tip5::sample_scalars (tip5/mod.rs:664-674): out receives count x num_elements x 3 words ([c0, c1, c2] per XFieldElement)."""
+    count, out = _sponge_states(states), _t(out, "out")
+    n = _per_sponge(out, count, 3, "out must hold num_elements x 3 words per sponge")
+    _chk(_lib.lib().tf_tip5_sponge_sample_scalars_dev(_p(states), count, n, _p(out), _stream(stream)), "Tip5::sample_scalars")
+
+
+def tip5_sponge_sample_indices(states, upper_bound: int, out, stream=None) -> None:
+    """Tip5::sample_indices (tip5/mod.rs:636-656): out receives count x num_indices indices below upper_bound (a power of two).
+    out is a contiguous CUDA int32 tensor whose BITS are the reference's u32 values (torch has no arithmetic on uint32, and this
+    module already carries u64 words in int64 tensors): an index of 2^31 or above cannot occur, upper_bound being at most 2^31."""
+    import torch
+
+    count = _sponge_states(states)
+    _need(isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype in (torch.int32, torch.uint32),
+          "out must be a contiguous CUDA int32 tensor of count x num_indices entries")
+    n = _per_sponge(out, count, 1, "out must hold num_indices entries per sponge")
+    _need(0 <= upper_bound < 2 ** 32, "upper_bound is a u32")
+    _chk(_lib.lib().tf_tip5_sponge_sample_indices_dev(_p(states), count, upper_bound, n, _p(out), _stream(stream)), "Tip5::sample_indices")
+
+
 # ----------------------------------------------------------------------------- Merkle Mountain Range (include/tf_hip.h, "Merkle Mountain Range")
 def _u64_host(a):
     import numpy as np

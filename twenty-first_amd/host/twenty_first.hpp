@@ -411,18 +411,23 @@ struct Tip5 {
         permutation();
         return produce;
     }
-    void pad_and_absorb_all(const std::vector<BFieldElement>& input) {
-        size_t i = 0;
-        std::array<BFieldElement, RATE> chunk;
-        for (; i + RATE <= input.size(); i += RATE) {
-            for (size_t k = 0; k < RATE; ++k) chunk[k] = input[i + k];
-            absorb(chunk);
-        }
-        chunk.fill(BFieldElement{});
-        const size_t rem = input.size() - i;
-        for (size_t k = 0; k < rem; ++k) chunk[k] = input[i + k];
-        chunk[rem] = BFieldElement::from_raw_u64(0xffffffffULL);  // BFieldElement::ONE
-        absorb(chunk);
+    void pad_and_absorb_all(const std::vector<BFieldElement>& input) {  // one library call (one launch) for all chunks and the padding
+        check(tf_tip5_sponge_pad_and_absorb_all(reinterpret_cast<uint64_t*>(state.data()), 1, reinterpret_cast<const uint64_t*>(input.data()),
+                                                input.size(), nullptr),
+              "Sponge::pad_and_absorb_all");
+    }
+    // :636-656.  Panics in the reference if upper_bound is not a power of two: BackendError(TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO) here.
+    std::vector<uint32_t> sample_indices(uint32_t upper_bound, size_t num_indices) {
+        std::vector<uint32_t> indices(num_indices);
+        check(tf_tip5_sponge_sample_indices(reinterpret_cast<uint64_t*>(state.data()), 1, upper_bound, num_indices, indices.data()),
+              "Tip5::sample_indices");
+        return indices;
+    }
+    std::vector<XFieldElement> sample_scalars(size_t num_elements) {  // :664-674
+        std::vector<XFieldElement> scalars(num_elements);
+        check(tf_tip5_sponge_sample_scalars(reinterpret_cast<uint64_t*>(state.data()), 1, num_elements, reinterpret_cast<uint64_t*>(scalars.data())),
+              "Tip5::sample_scalars");
+        return scalars;
     }
     // batched forms -- the reason to cross the boundary at all
     static std::vector<Digest> hash_pairs(const std::vector<Digest>& pairs) {  // pairs.size() even: (l0, r0, l1, r1, ...)
