@@ -671,6 +671,10 @@ int tf_debug_stamps(unsigned long long *host_out, size_t words);
 /* Synthetic inputs for benches/tests: d_out[i] = BFieldElement::new(splitmix64(seed ^ (first_index + i)) mod p),
  * raw Montgomery words, generated on the device (the oracle's tfo_fill_random is the same counter-based sequence). */
 int tf_debug_fill_random_dev(uint64_t *d_out, size_t count, uint64_t seed, uint64_t first_index, void *stream);
+/* Test helper: d_x[i] <- d_x[i] * 2^e mod p (canonical word) for ANY 64-bit words d_x[i], 0 <= e < 192, in place, through the
+ * power-of-two products (and their sign) of the NTT networks -- hand-scheduled blocks of four and of two per thread.
+ * TF_ERR_INVALID_ARGUMENT for an exponent outside [0, 192). */
+int tf_debug_mul_pow2_dev(uint64_t *d_x, size_t count, int e, void *stream);
 
 #ifdef __cplusplus
 }

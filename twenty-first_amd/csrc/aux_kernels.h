@@ -35,4 +35,33 @@ __global__ void __launch_bounds__(256) fill_random_kernel(u64* out, unsigned lon
     }
 }
 
+// tf_debug_mul_pow2_dev: x[i] <- x[i] * 2^E mod p (canonical) for ANY 64-bit words x[i], through gl::Pow2Mul<E> and its sign exactly
+// as the NTT networks use them (ntt_network.h).  Six words per thread: four through one block-of-four, two through one block-of-two
+// (gl::pow2_mul_block), so both block shapes are exercised.  E = 0 / 96 is the networks' pass-through: the operand made canonical
+// (gl::add(x, 0), tw_operand).  Loads and stores are guarded by count.
+template <int E>
+__global__ void __launch_bounds__(256) mul_pow2_kernel(u64* x, unsigned long long count) {
+    const unsigned long long base = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * 6;
+    u64 v4[4], v2[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v4[i] = base + i < count ? x[base + i] : 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) v2[i] = base + 4 + i < count ? x[base + 4 + i] : 0;
+    if constexpr (gl::Pow2Mul<E>::cls == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] = gl::add(v4[i], 0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) v2[i] = gl::add(v2[i], 0);
+    } else {
+        gl::pow2_mul_block<E, E, E, E>(v4);
+        gl::pow2_mul_block<E, E>(v2);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (base + i < count) x[base + i] = gl::Pow2Mul<E>::negate ? gl::neg(v4[i]) : v4[i];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        if (base + 4 + i < count) x[base + 4 + i] = gl::Pow2Mul<E>::negate ? gl::neg(v2[i]) : v2[i];
+}
+
 }  // namespace tfk

@@ -546,6 +546,131 @@ GL_HD u64 shl_monty(u64 x) {
 #endif
 }
 
+#ifndef TF_ASM_POW2
+#define TF_ASM_POW2 1  // 0 (A/B build): the compiler's shl_fold / shl_monty above instead of the hand-scheduled forms below
+#endif
+
+#if defined(__HIPCC__)
+// ---- hand-scheduled power-of-two products (device code; same contract: ANY 64-bit x in, canonical word out) ----------------
+// shl_fold<K> in six VALU instructions (the compiler spends nine: a zero-addend v_mad_u64_u32 and a separate 64-bit add, two
+// 64-bit compares for the carries, a third 64-bit add and two selects):
+//   hi = x >> (64 - K), lo = x << K                     v_lshrrev_b32, v_lshlrev_b64
+//   t  = hi * 0xffffffff + lo, carry c                  ONE v_mad_u64_u32, its carry-out kept in an SGPR pair (as in mont_mul2)
+//   sel = c | (t >= p)                                  v_cmp_lt_u64 (p - 1 < t) and a scalar or
+//   t += EPS where sel:  t0 -= sel (borrow n);  t1 += sel & ~n          (EPS = 2^32 - 1: -1 on the low word, +1 on the high word)
+// hi < 2^31, so c:t < 2^64 + 2^63: with c set the true value t + 2^64 = t + EPS (mod p) is < 2^63 + 2^32 < p and does not carry;
+// without c and t >= p, t - p = t + EPS (mod 2^64).  Every carry mask a VALU instruction writes here is read by the SCALAR unit
+// (s_or / s_andn2), and every mask a VALU instruction reads was written by the scalar unit: no VALU-to-VALU mask dependency, so
+// the sequence needs no wait states and no partner chain -- the compiler is free to interleave any number of them.
+template <int K>
+__device__ __forceinline__ u64 shl_fold_asm(u64 x) {
+    static_assert(K > 0 && K < 32, "");
+    const u64 lo = x << K;
+    const u32 hi = (u32)(x >> 32) >> (32 - K);
+    u64 t, c, ge, n;
+    asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t), "=s"(c) : "v"(hi), "v"(lo));
+    u32 r0, r1;
+    asm("v_cmp_lt_u64_e64 %[ge], %[pm1], %[t]\n\t"
+        "s_or_b64 %[c], %[c], %[ge]\n\t"
+        "v_subbrev_co_u32_e64 %[r0], %[n], 0, %[t0], %[c]\n\t"
+        "s_andn2_b64 %[c], %[c], %[n]\n\t"
+        "v_addc_co_u32_e64 %[r1], %[n], 0, %[t1], %[c]"
+        : [r0] "=&v"(r0), [r1] "=v"(r1), [c] "+s"(c), [n] "=&s"(n), [ge] "=&s"(ge)
+        : [pm1] "s"(P - 1), [t] "v"(t), [t0] "v"((u32)t), [t1] "v"((u32)(t >> 32))
+        : "scc");
+    return ((u64)r1 << 32) | r0;
+}
+
+// x >= p ? x - p : x  for any 64-bit word (the canonical word of a lazy operand; = add(x, 0)) in three VALU instructions: the tail of
+// shl_fold_asm without a carry-in.  The compare's mask goes through the scalar unit (s_mov) before a VALU instruction reads it.
+__device__ __forceinline__ u64 canonical_asm(u64 x) {
+    u32 r0, r1;
+    u64 c, n;
+    asm("v_cmp_lt_u64_e64 %[n], %[pm1], %[x]\n\t"
+        "s_mov_b64 %[c], %[n]\n\t"
+        "v_subbrev_co_u32_e64 %[r0], %[n], 0, %[x0], %[c]\n\t"
+        "s_andn2_b64 %[c], %[c], %[n]\n\t"
+        "v_addc_co_u32_e64 %[r1], %[n], 0, %[x1], %[c]"
+        : [r0] "=&v"(r0), [r1] "=v"(r1), [c] "=&s"(c), [n] "=&s"(n)
+        : [pm1] "s"(P - 1), [x] "v"(x), [x0] "v"((u32)x), [x1] "v"((u32)(x >> 32))
+        : "scc");
+    return ((u64)r1 << 32) | r0;
+}
+
+// shl_monty<S> for N = 1, 2 or 4 independent products: montyred of the 128-bit word x << S on ONE carry chain per product, the
+// chains issued round-robin.  x << S has at most three non-zero 32-bit limbs (v0, v1, v2) = x << (S mod 32):
+//   S < 32  (h1 = 0):  (l0, l1, h0) = (v0, v1, v2)      a1 = l1 + l0 (e); b0 = l0 - a1 - e; b1 = a1 - borrow; r0 = h0 - b0;
+//                                                        r1 = 0 - b1 - borrow; "+ p" on borrow as r0 += c, r1 -= c & ~carry
+//                                                        three shifts + seven carry steps = 10 VALU
+//   S >= 32 (l0 = 0):  (l1, h0, h1) = (v0, v1, v2)      a1 = l1, e = 0: the first step drops out,  b0 = 0 - l1; ...       9 VALU
+// (the compiler's montyred spends one more for the final select and a wait-state s_nop after almost every step).
+// Wait states: gfx950 wants two between a VALU instruction writing a carry mask and a VALU instruction reading it.  Round-robin
+// over four chains provides them for free; two chains take one s_nop per dependent step, a single chain two.
+// All limbs are updated in place (no temporaries beyond b0 of the l0 = 0 form).
+#define TF_P2_RR1(S) S(a)
+#define TF_P2_RR2(S) S(a) S(b)
+#define TF_P2_RR4(S) S(a) S(b) S(c) S(d)
+#define TF_P2_GAP1 "s_nop 1\n\t"
+#define TF_P2_GAP2 "s_nop 0\n\t"
+#define TF_P2_GAP4
+// h1 = 0 form on (w, u, r) = (l0, l1, h0); result (u : r)
+#define TF_P2B_1(X) "v_add_co_u32_e64 %[u" #X "], %[c" #X "], %[u" #X "], %[w" #X "]\n\t"          /* a1 = l1 + l0, carry e      */
+#define TF_P2B_2(X) "v_subb_co_u32_e64 %[w" #X "], %[c" #X "], %[w" #X "], %[u" #X "], %[c" #X "]\n\t" /* b0 = l0 - a1 - e            */
+#define TF_P2B_3(X) "v_subbrev_co_u32_e64 %[u" #X "], %[c" #X "], 0, %[u" #X "], %[c" #X "]\n\t"    /* b1 = a1 - borrow           */
+#define TF_P2B_4(X) "v_sub_co_u32_e64 %[r" #X "], %[c" #X "], %[r" #X "], %[w" #X "]\n\t"          /* r0 = h0 - b0               */
+#define TF_P2B_5(X) "v_subb_co_u32_e64 %[u" #X "], %[c" #X "], 0, %[u" #X "], %[c" #X "]\n\t"       /* r1 = 0 - b1 - borrow       */
+#define TF_P2B_6(X) "v_addc_co_u32_e64 %[r" #X "], %[k" #X "], 0, %[r" #X "], %[c" #X "]\n\t"       /* r0 += borrow (carry k)     */
+#define TF_P2B_7(X) "s_andn2_b64 %[c" #X "], %[c" #X "], %[k" #X "]\n\t"
+#define TF_P2B_8(X) "v_subbrev_co_u32_e64 %[u" #X "], %[k" #X "], 0, %[u" #X "], %[c" #X "]\n\t"    /* r1 -= borrow & ~k          */
+#define TF_P2B_BODY(RR, GAP) RR(TF_P2B_1) GAP RR(TF_P2B_2) GAP RR(TF_P2B_3) RR(TF_P2B_4) GAP RR(TF_P2B_5) GAP RR(TF_P2B_6) RR(TF_P2B_7) RR(TF_P2B_8)
+#define TF_P2B_OPS(X, i) [w##X] "+v"(w[i]), [u##X] "+v"(u[i]), [r##X] "+v"(r[i]), [c##X] "=&s"(c[i]), [k##X] "=&s"(k[i])
+// l0 = 0 form on (u, r, q) = (l1, h0, h1), temporary w = b0; result (q : r)
+#define TF_P2C_1(X) "v_sub_co_u32_e64 %[w" #X "], %[c" #X "], 0, %[u" #X "]\n\t"                    /* b0 = 0 - a1, borrow        */
+#define TF_P2C_2(X) "v_subbrev_co_u32_e64 %[u" #X "], %[c" #X "], 0, %[u" #X "], %[c" #X "]\n\t"    /* b1 = a1 - borrow           */
+#define TF_P2C_3(X) "v_sub_co_u32_e64 %[r" #X "], %[c" #X "], %[r" #X "], %[w" #X "]\n\t"          /* r0 = h0 - b0               */
+#define TF_P2C_4(X) "v_subb_co_u32_e64 %[q" #X "], %[c" #X "], %[q" #X "], %[u" #X "], %[c" #X "]\n\t" /* r1 = h1 - b1 - borrow      */
+#define TF_P2C_5(X) "v_addc_co_u32_e64 %[r" #X "], %[k" #X "], 0, %[r" #X "], %[c" #X "]\n\t"       /* r0 += borrow (carry k)     */
+#define TF_P2C_6(X) "s_andn2_b64 %[c" #X "], %[c" #X "], %[k" #X "]\n\t"
+#define TF_P2C_7(X) "v_subbrev_co_u32_e64 %[q" #X "], %[k" #X "], 0, %[q" #X "], %[c" #X "]\n\t"    /* r1 -= borrow & ~k          */
+#define TF_P2C_BODY(RR, GAP) RR(TF_P2C_1) GAP RR(TF_P2C_2) RR(TF_P2C_3) GAP RR(TF_P2C_4) GAP RR(TF_P2C_5) RR(TF_P2C_6) RR(TF_P2C_7)
+#define TF_P2C_OPS(X, i) [w##X] "=&v"(w[i]), [u##X] "+v"(u[i]), [r##X] "+v"(r[i]), [q##X] "+v"(q[i]), [c##X] "=&s"(c[i]), [k##X] "=&s"(k[i])
+
+// x[i] = montyred(x[i] << S[i]) for N products of ONE form: all S[i] < 32 (HIGH = false) or all S[i] >= 32 (HIGH = true).
+template <bool HIGH, int N>
+__device__ __forceinline__ void shl_monty_block(u64 (&x)[N], const int (&S)[N]) {
+    static_assert(N == 1 || N == 2 || N == 4, "");
+    u32 w[N], u[N], r[N], q[N];
+    u64 c[N], k[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {  // (v0, v1, v2) = x << T on three limbs: at most shift, funnel shift, shift
+        const int T = S[i] & 31;
+        const u32 x0 = (u32)x[i], x1 = (u32)(x[i] >> 32);
+        const u32 v0 = x0 << T, v1 = T ? __builtin_amdgcn_alignbit(x1, x0, 32 - T) : x1, v2 = T ? x1 >> (32 - T) : 0u;
+        if constexpr (HIGH) u[i] = v0, r[i] = v1, q[i] = v2;
+        else w[i] = v0, u[i] = v1, r[i] = v2;
+    }
+    if constexpr (!HIGH) {
+        if constexpr (N == 1) asm(TF_P2B_BODY(TF_P2_RR1, TF_P2_GAP1) : TF_P2B_OPS(a, 0) : : "scc");
+        else if constexpr (N == 2) asm(TF_P2B_BODY(TF_P2_RR2, TF_P2_GAP2) : TF_P2B_OPS(a, 0), TF_P2B_OPS(b, 1) : : "scc");
+        else asm(TF_P2B_BODY(TF_P2_RR4, TF_P2_GAP4) : TF_P2B_OPS(a, 0), TF_P2B_OPS(b, 1), TF_P2B_OPS(c, 2), TF_P2B_OPS(d, 3) : : "scc");
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i] = ((u64)u[i] << 32) | r[i];
+    } else {
+        if constexpr (N == 1) asm(TF_P2C_BODY(TF_P2_RR1, TF_P2_GAP1) : TF_P2C_OPS(a, 0) : : "scc");
+        else if constexpr (N == 2) asm(TF_P2C_BODY(TF_P2_RR2, TF_P2_GAP2) : TF_P2C_OPS(a, 0), TF_P2C_OPS(b, 1) : : "scc");
+        else asm(TF_P2C_BODY(TF_P2_RR4, TF_P2_GAP4) : TF_P2C_OPS(a, 0), TF_P2C_OPS(b, 1), TF_P2C_OPS(c, 2), TF_P2C_OPS(d, 3) : : "scc");
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i] = ((u64)q[i] << 32) | r[i];
+    }
+}
+#endif  // __HIPCC__
+
+#if defined(__HIP_DEVICE_COMPILE__) && TF_ASM_POW2
+#define TF_POW2_DEVICE_ASM 1
+#else
+#define TF_POW2_DEVICE_ASM 0
+#endif
+
 // x * 2^E mod p as (value, sign): E taken mod 192; returns v with  x * 2^E = negate ? -v : v.
 template <int E>
 struct Pow2Mul {
@@ -553,16 +678,48 @@ struct Pow2Mul {
     static constexpr bool high = (((E % 192) + 192) % 192) >= 96;  // 2^96 = -1
     static constexpr bool via_monty = e96 >= 32;
     static constexpr bool negate = high != via_monty;
+    static constexpr int cls = e96 == 0 ? 0 : e96 < 32 ? 1 : e96 < 64 ? 2 : 3;  // pass-through, shl_fold, shl_monty with h1 = 0 / l0 = 0
     static GL_HD u64 apply(u64 x) {
         if constexpr (e96 == 0) {
             return x;
         } else if constexpr (e96 < 32) {
+#if TF_POW2_DEVICE_ASM
+            return shl_fold_asm<e96>(x);
+#else
             return shl_fold<e96>(x);
+#endif
         } else {
+#if TF_POW2_DEVICE_ASM
+            u64 v[1] = {x};
+            const int s[1] = {e96 - 32};
+            shl_monty_block<(e96 >= 64), 1>(v, s);
+            return v[0];
+#else
             return shl_monty<e96 - 32>(x);
+#endif
         }
     }
 };
+
+#if defined(__HIPCC__)
+// x[i] = Pow2Mul<E_i>::apply(x[i]) for two or four exponents of ONE class (Pow2Mul::cls): the Montgomery forms share a block of
+// round-robin carry chains (no wait-state s_nop with four products), the fold form needs none and is simply repeated.
+template <int... E>
+__device__ __forceinline__ void pow2_mul_block(u64 (&x)[sizeof...(E)]) {
+    constexpr int N = sizeof...(E);
+    constexpr int cls[N] = {Pow2Mul<E>::cls...};
+    static_assert(((Pow2Mul<E>::cls == cls[0]) && ...), "one exponent class per block");
+#if TF_POW2_DEVICE_ASM
+    if constexpr (cls[0] >= 2) {
+        const int s[N] = {(Pow2Mul<E>::e96 - 32)...};
+        shl_monty_block<(cls[0] == 3), N>(x, s);
+        return;
+    }
+#endif
+    int i = 0;
+    ((x[i] = Pow2Mul<E>::apply(x[i]), ++i), ...);
+}
+#endif
 
 // x * 2^K mod p (canonical), 0 <= K < 192
 template <int K>

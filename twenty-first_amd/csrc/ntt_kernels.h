@@ -1382,6 +1382,7 @@ struct NttBlockArgs {
 // transform keeps its register budget
 template <int LOGP3, bool INV, int SCALE = 0>
 __global__ void __launch_bounds__(512, 4) ntt_block_kernel(const NttBlockArgs A) {
+    constexpr int W = LOGP3 == 4 ? 2 : TF_POW2_WIDE;  // power-of-two products per block in stages A and B: four-wide blocks cost the 2^14 instantiations a VGPR
     constexpr int P3 = 1 << LOGP3, N = 1024 << LOGP3, REST = 32 << LOGP3, T = 16 >> LOGP3;
     constexpr int PS1 = 1056 + 32 / P3;      // exchange 1: pair slot stride (k1 * 33 + j2 inside a slot)
     constexpr int KS2 = 32 * P3 + 1;         // exchange 2: stride between k1 (k2 * P3 + j3 inside)
@@ -1426,9 +1427,9 @@ __global__ void __launch_bounds__(512, 4) ntt_block_kernel(const NttBlockArgs A)
             }
         }
     }
-    dit_half<INV, 0, true>(x);   // lazy networks in stages A and B: a Montgomery product follows (see ntt_pass_kernel)
-    dit_half<INV, 16, true>(x);
-    dit_level<INV, 5, true>(x);
+    dit_half<INV, 0, true, W>(x);   // lazy networks in stages A and B: a Montgomery product follows (see ntt_pass_kernel)
+    dit_half<INV, 16, true, W>(x);
+    dit_level<INV, 5, true, W>(x);
     {
         const u64* tw = A.tw1 + rest;
 #pragma unroll
@@ -1465,9 +1466,9 @@ __global__ void __launch_bounds__(512, 4) ntt_block_kernel(const NttBlockArgs A)
         }
     }
     // ---- stage B
-    dit_half<INV, 0, true>(x);
-    dit_half<INV, 16, true>(x);
-    dit_level<INV, 5, true>(x);
+    dit_half<INV, 0, true, W>(x);
+    dit_half<INV, 16, true, W>(x);
+    dit_level<INV, 5, true, W>(x);
     {
         const u64* tw = A.tw2 + j3B;
 #pragma unroll

@@ -59,6 +59,9 @@ struct Bf {
 template <int E, bool LAZY_IN>
 __device__ __forceinline__ u64 tw_operand(u64 b) {
     if constexpr (E % 192 == 0) {
+#if TF_ASM_POW2
+        if constexpr (LAZY_IN) return gl::canonical_asm(b);  // b >= p ? b - p : b   (3 VALU)
+#endif
         if constexpr (LAZY_IN) return gl::add(b, 0);  // b >= p ? b - p : b   (4 VALU)
         return b;
     } else {
@@ -105,10 +108,109 @@ __device__ __forceinline__ void butterfly_pow2(u64& a, u64& b) {
     }
 }
 
+#ifndef TF_POW2_WIDE
+#define TF_POW2_WIDE 4  // most power-of-two products per block: 4 or 2
+#endif
+#if TF_ASM_BFLY && TF_ASM_POW2
+// ---- a level's butterflies, grouped by the exponent class of their twiddle ---------------------------------------------------------
+// The Montgomery-form products (gl::shl_monty_block) want four carry chains per block to hide the carry-mask wait states, and a
+// block takes one form; neighbouring butterflies (I, I + 1) rarely share one.  The butterflies of a level touch disjoint slots, so
+// they may run in any order: class by class, the twiddled operands of four (or two) butterflies are multiplied in one block and
+// their butterflies follow at once (class_fused); the odd one of a class is left over and paired with another class's
+// (leftover_fused).  Same words as butterfly_pair computes for the pairs (I, I + 1).
+constexpr int bf_exp(bool inv, int lvl, int i) {  // = Bf<INV, LVL, I>::E
+    const int fwd = ((39 << (6 - lvl)) * (i % (1 << (lvl - 1)))) % 192;
+    return inv ? (192 - fwd) % 192 : fwd;
+}
+constexpr int bf_cls(bool inv, int lvl, int i) {  // = gl::Pow2Mul<E>::cls
+    const int e96 = bf_exp(inv, lvl, i) % 96;
+    return e96 == 0 ? 0 : e96 < 32 ? 1 : e96 < 64 ? 2 : 3;
+}
+constexpr int bf_count(bool inv, int lvl, int i0, int end, int cls) {
+    int n = 0;
+    for (int i = i0; i < end; ++i) n += bf_cls(inv, lvl, i) == cls;
+    return n;
+}
+constexpr int bf_nth(bool inv, int lvl, int i0, int end, int cls, int pos) {  // the pos-th butterfly of the class in [i0, end)
+    for (int i = i0; i < end; ++i)
+        if (bf_cls(inv, lvl, i) == cls && pos-- == 0) return i;
+    return i0;
+}
+// two butterflies BA, BB (any two of one level) on operands that are already multiplied
+template <typename BA, typename BB, bool LAZY>
+__device__ __forceinline__ void bfly2(u64 (&x)[32]) {
+    u64 s0, d0, s1, d1;
+    if constexpr (LAZY) gl::add_sub_lazy2(x[BA::ia], x[BA::ib], x[BB::ia], x[BB::ib], s0, d0, s1, d1);
+    else gl::add_sub2(x[BA::ia], x[BA::ib], x[BB::ia], x[BB::ib], s0, d0, s1, d1);
+    x[BA::ia] = BA::neg ? d0 : s0;
+    x[BA::ib] = BA::neg ? s0 : d0;
+    x[BB::ia] = BB::neg ? d1 : s1;
+    x[BB::ib] = BB::neg ? s1 : d1;
+}
+// class CLS of butterflies [I0, END): blocks of four or two products, each followed at once by its butterflies; an odd one is left over
+template <bool INV, int LVL, int I0, int END, int CLS, bool LAZY, int WIDE, int POS = 0>
+__device__ __forceinline__ void class_fused(u64 (&x)[32]) {
+    constexpr int rem = bf_count(INV, LVL, I0, END, CLS) - POS;
+    if constexpr (rem >= 2) {
+        constexpr int take = (rem >= 4 && WIDE >= 4) ? 4 : 2;
+        using A = Bf<INV, LVL, bf_nth(INV, LVL, I0, END, CLS, POS)>;
+        using B = Bf<INV, LVL, bf_nth(INV, LVL, I0, END, CLS, POS + 1)>;
+        using C = Bf<INV, LVL, bf_nth(INV, LVL, I0, END, CLS, POS + (take > 2 ? 2 : 0))>;
+        using D = Bf<INV, LVL, bf_nth(INV, LVL, I0, END, CLS, POS + (take > 2 ? 3 : 1))>;
+        if constexpr (CLS == 0) {
+            x[A::ib] = tw_operand<A::E, LAZY && (LVL > 1)>(x[A::ib]);
+            x[B::ib] = tw_operand<B::E, LAZY && (LVL > 1)>(x[B::ib]);
+            bfly2<A, B, LAZY>(x);
+        } else if constexpr (take == 2) {
+            u64 v[2] = {x[A::ib], x[B::ib]};
+            gl::pow2_mul_block<A::E, B::E>(v);
+            x[A::ib] = v[0], x[B::ib] = v[1];
+            bfly2<A, B, LAZY>(x);
+        } else {
+            u64 v[4] = {x[A::ib], x[B::ib], x[C::ib], x[D::ib]};
+            gl::pow2_mul_block<A::E, B::E, C::E, D::E>(v);
+            x[A::ib] = v[0], x[B::ib] = v[1], x[C::ib] = v[2], x[D::ib] = v[3];
+            bfly2<A, B, LAZY>(x);
+            bfly2<C, D, LAZY>(x);
+        }
+        class_fused<INV, LVL, I0, END, CLS, LAZY, WIDE, POS + (CLS == 0 ? 2 : take)>(x);
+    }
+}
+// the k-th left-over butterfly: the last one of each class with an odd count, classes in order
+constexpr int bf_leftover(bool inv, int lvl, int i0, int end, int k) {
+    for (int c = 0; c < 4; ++c) {
+        const int n = bf_count(inv, lvl, i0, end, c);
+        if ((n & 1) && k-- == 0) return bf_nth(inv, lvl, i0, end, c, n - 1);
+    }
+    return -1;
+}
+template <bool INV, int LVL, int I0, int END, bool LAZY, int K = 0>
+__device__ __forceinline__ void leftover_fused(u64 (&x)[32]) {
+    constexpr int ia = bf_leftover(INV, LVL, I0, END, K), ib = bf_leftover(INV, LVL, I0, END, K + 1);
+    if constexpr (ia >= 0) {
+        static_assert(ib >= 0, "an even number of butterflies leaves an even number over");
+        using A = Bf<INV, LVL, ia>;
+        using B = Bf<INV, LVL, (ib >= 0 ? ib : 0)>;
+        x[A::ib] = tw_operand<A::E, LAZY && (LVL > 1)>(x[A::ib]);
+        x[B::ib] = tw_operand<B::E, LAZY && (LVL > 1)>(x[B::ib]);
+        bfly2<A, B, LAZY>(x);
+        leftover_fused<INV, LVL, I0, END, LAZY, K + 2>(x);
+    }
+}
+#endif
+
 // butterflies [I, END) of level LVL, two at a time
-template <bool INV, int LVL, int I, int END, bool LAZY>
+template <bool INV, int LVL, int I, int END, bool LAZY, int WIDE = TF_POW2_WIDE>
 struct DitRange {
     static __device__ __forceinline__ void run(u64 (&x)[32]) {
+#if TF_ASM_BFLY && TF_ASM_POW2
+        static_assert(bf_exp(INV, LVL, I) == Bf<INV, LVL, I>::E && bf_exp(INV, LVL, END - 1) == Bf<INV, LVL, END - 1>::E, "");
+        class_fused<INV, LVL, I, END, 0, LAZY, WIDE>(x);
+        class_fused<INV, LVL, I, END, 1, LAZY, WIDE>(x);
+        class_fused<INV, LVL, I, END, 2, LAZY, WIDE>(x);
+        class_fused<INV, LVL, I, END, 3, LAZY, WIDE>(x);
+        leftover_fused<INV, LVL, I, END, LAZY>(x);
+#else
 #if TF_ASM_BFLY
         butterfly_pair<INV, LVL, I, LAZY>(x);
 #else
@@ -116,19 +218,20 @@ struct DitRange {
         butterfly_pow2<Bf<INV, LVL, I + 1>::E>(x[Bf<INV, LVL, I + 1>::ia], x[Bf<INV, LVL, I + 1>::ib]);
 #endif
         if constexpr (I + 2 < END) DitRange<INV, LVL, I + 2, END, LAZY>::run(x);
+#endif
     }
 };
 // Level LVL of a DIT network over all 32 registers.
-template <bool INV, int LVL, bool LAZY = false>
-__device__ __forceinline__ void dit_level(u64 (&x)[32]) { DitRange<INV, LVL, 0, 16, LAZY && TF_LAZY>::run(x); }
+template <bool INV, int LVL, bool LAZY = false, int WIDE = TF_POW2_WIDE>
+__device__ __forceinline__ void dit_level(u64 (&x)[32]) { DitRange<INV, LVL, 0, 16, LAZY && TF_LAZY, WIDE>::run(x); }
 
 // levels 1..4 restricted to the 16 register slots starting at FIRST (0 or 16): butterflies FIRST/2 .. FIRST/2 + 7 of each level
-template <bool INV, int FIRST, bool LAZY = false>
+template <bool INV, int FIRST, bool LAZY = false, int WIDE = TF_POW2_WIDE>
 __device__ __forceinline__ void dit_half(u64 (&x)[32]) {
-    DitRange<INV, 1, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY>::run(x);
-    DitRange<INV, 2, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY>::run(x);
-    DitRange<INV, 3, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY>::run(x);
-    DitRange<INV, 4, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY>::run(x);
+    DitRange<INV, 1, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY, WIDE>::run(x);
+    DitRange<INV, 2, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY, WIDE>::run(x);
+    DitRange<INV, 3, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY, WIDE>::run(x);
+    DitRange<INV, 4, FIRST / 2, FIRST / 2 + 8, LAZY && TF_LAZY, WIDE>::run(x);
 }
 
 // x[q0 .. q0+3] *= w[0 .. 3]  (four Montgomery products, no wait-state nops: gl::mont_mul4)

@@ -3,6 +3,7 @@
 #include "aux_kernels.h"
 
 #include <functional>
+#include <utility>
 
 namespace tfi {
 
@@ -148,6 +149,18 @@ int merkle_proofs_host(const uint32_t* heights, size_t n, const uint64_t* loff, 
     return sync(s);
 }
 
+// tf_debug_mul_pow2_dev: one kernel instantiation per exponent, picked from a table
+template <int E>
+void mul_pow2_launch(u64* d_x, size_t count, hipStream_t s) {
+    const unsigned blocks = (unsigned)((count + 6 * 256 - 1) / (6 * 256));
+    hipLaunchKernelGGL(tfk::mul_pow2_kernel<E>, dim3(blocks), dim3(256), 0, s, d_x, (unsigned long long)count);
+}
+template <int... E>
+void mul_pow2_dispatch(int e, u64* d_x, size_t count, hipStream_t s, std::integer_sequence<int, E...>) {
+    using Fn = void (*)(u64*, size_t, hipStream_t);
+    static const Fn table[] = {&mul_pow2_launch<E>...};
+    table[e](d_x, count, s);
+}
 }  // namespace tfi
 
 using namespace tfi;
@@ -263,6 +276,19 @@ int tf_debug_fill_random_dev(uint64_t* d_out, size_t count, uint64_t seed, uint6
     const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, size_t(1) << 20);
     hipLaunchKernelGGL(tfk::fill_random_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), d_out,
                        (unsigned long long)count, (u64)seed, (unsigned long long)first_index);
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+} TF_ABI_CATCH
+
+// test helper (not part of the drop-in boundary): d_x[i] <- d_x[i] * 2^e mod p, one kernel instantiation per exponent
+int tf_debug_mul_pow2_dev(uint64_t* d_x, size_t count, int e, void* stream) try {
+    if (e < 0 || e >= 192 || count > (size_t(1) << 40)) return TF_ERR_INVALID_ARGUMENT;
+    if (count == 0) return TF_OK;
+    if (!d_x) return TF_ERR_NULL_POINTER;
+    DeviceCtx* ctx = nullptr;
+    int rc = current_ctx(&ctx);
+    if (rc) return rc;
+    mul_pow2_dispatch(e, reinterpret_cast<u64*>(d_x), count, static_cast<hipStream_t>(stream), std::make_integer_sequence<int, 192>{});
     HIPCHK(hipGetLastError());
     return TF_OK;
 } TF_ABI_CATCH

@@ -56,6 +56,14 @@ def fill_random(out, seed: int, first_index: int = 0, stream=None) -> None:
                                              _stream(stream)), "fill_random")
 
 
+def debug_mul_pow2_(x, e: int, stream=None) -> None:
+    """Test helper, in place on device: x[i] <- x[i] * 2^e mod p (canonical) for ANY 64-bit words, 0 <= e < 192, through the
+    power-of-two products of the NTT networks (tf_debug_mul_pow2_dev)."""
+    x = _t(x, "x")
+    _need(0 <= e < 192, "the exponent must be in [0, 192)")
+    _chk(_lib.lib().tf_debug_mul_pow2_dev(_p(x), x.numel(), int(e), _stream(stream)), "debug_mul_pow2")
+
+
 def ntt_(x, n: int, batch: int = 1, width: int = 1, inverse: bool = False, stream=None) -> None:
     """In place on device: `batch` slices of n elements (math/ntt.rs:67-82, :109-125)."""
     x = _t(x, "x")
