@@ -445,6 +445,30 @@ int tf_merkle_from_rows_dev(const uint64_t *d_rows, size_t row_len, size_t n_row
 int tf_merkle_auth_structure_indices(size_t num_leafs, const uint64_t *leaf_indices, size_t k, uint64_t *out_indices, size_t capacity, size_t *out_count);
 int tf_merkle_authentication_structure_dev(const uint64_t *d_nodes, size_t num_leafs, const uint64_t *leaf_indices, size_t k,
                                            uint64_t *out_digests, size_t capacity_digests, size_t *out_count, void *stream);
+/* MerkleTree::sequential_authentication_structure_from_leafs / par_authentication_structure_from_leafs   util_types/merkle_tree.rs:506-542
+ * The authentication structure AND the root of `batch` trees from their leafs alone: commit and open in one call, without the node
+ * array of 2 n digests per tree that tf_merkle_authentication_structure_dev reads (the companion of tf_merkle_root).
+ * leafs: batch x num_leafs digests, as for tf_merkle_build.  ONE list of leaf indices opens every tree of the batch (a prover's query
+ * indices on its main, auxiliary and quotient trees).  *out_count: structure nodes per tree, what tf_merkle_auth_structure_indices
+ * reports for the same indices.  out_digests: tree-major, batch x count digests; within a tree in the reference's order (descending
+ * node index, :502-503), each the digest nodes[i] of the full tree.  roots: NULL, or batch x 5 words (the values of tf_merkle_root).
+ * k == 0, every leaf opened, and num_leafs == 1 all give count 0: roots only.
+ * Sizing as the pair above: *out_count is always written; out_digests == NULL or capacity_digests == 0 is the sizing call (TF_OK,
+ * nothing else written, roots included); capacity_digests (digests PER TREE) < count -> TF_ERR_BUFFER_TOO_SMALL, nothing written.
+ * Errors, before any device is touched and in this order: TF_ERR_TOO_FEW_LEAFS (num_leafs == 0), TF_ERR_INCORRECT_NUMBER_OF_LEAFS
+ * (not a power of two), TF_ERR_TREE_TOO_HIGH (more than 2^31 leafs), TF_ERR_LEAF_INDEX_INVALID (an index >= num_leafs),
+ * TF_ERR_NULL_POINTER (leafs; leaf_indices with k > 0; out_count).  batch == 0: TF_OK with *out_count set.
+ * _dev: leaf_indices is a HOST array (*out_count is host arithmetic, valid on return); leafs, digests and roots are device memory.
+ * Nothing is copied back and `stream` is not synchronised.  Work space comes from the library's stream-ordered pool and goes back
+ * on `stream`: tf_merkle_auth_structure_from_leafs_workspace is the number of bytes the call requests for k_nodes structure nodes per
+ * tree (pure host arithmetic; 0 for arguments the call rejects).  It never shrinks as batch grows and is at most
+ *   batch * (3 num_leafs / 4) + 2^15 + 128 batch   digests of 40 bytes, plus 8 bytes per structure node,
+ * and never more than 2 num_leafs batch digests plus those 8 bytes per node (trees of up to 2^14 / batch leafs are built whole). */
+int tf_merkle_auth_structure_from_leafs(const uint64_t *leafs, size_t num_leafs, size_t batch, const uint64_t *leaf_indices, size_t k,
+                                        uint64_t *out_digests, size_t capacity_digests, size_t *out_count, uint64_t *roots);
+int tf_merkle_auth_structure_from_leafs_dev(const uint64_t *d_leafs, size_t num_leafs, size_t batch, const uint64_t *leaf_indices, size_t k,
+                                            uint64_t *d_out_digests, size_t capacity_digests, size_t *out_count, uint64_t *d_roots, void *stream);
+size_t tf_merkle_auth_structure_from_leafs_workspace(size_t num_leafs, size_t batch, size_t k_nodes);
 
 /* ---------------------------------------------------------------------------------------------
  * Inclusion proofs, batched.   replaces  MerkleTreeInclusionProof::try_verify / verify   util_types/merkle_tree.rs:727-748

@@ -857,6 +857,35 @@ class MerkleTree:
         idx = self.authentication_structure_node_indices(self.num_leafs(), leaf_indices)
         return self.nodes[idx.astype(np.int64)]
 
+    @staticmethod
+    def authentication_structure_from_leafs(leafs, leaf_indices, batch: int = 1, with_root: bool = False):
+        """util_types/merkle_tree.rs:506-542: the authentication structure of `leaf_indices` from the leafs alone -- one level sweep on
+        the device, no node array.  leafs: `batch` trees of equally many digests; the one index list opens every tree.  Returns
+        (count, 5) raw words for batch == 1, else (batch, count, 5), in the order of authentication_structure; with_root: also the
+        root(s), (5,) or (batch, 5)."""
+        where = "MerkleTree::authentication_structure_from_leafs"
+        leafs = _words(np.ascontiguousarray(leafs, dtype=np.uint64).reshape(-1), "leafs")
+        if batch < 1 or leafs.size % (5 * batch):
+            raise ValueError("leafs must hold batch trees of whole digests (5 words each)")
+        n = leafs.size // (5 * batch)
+        li = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+        lp = _ptr(leafs)
+        cnt = C.c_size_t(0)
+        _check(lib().tf_merkle_auth_structure_from_leafs(lp, n, batch, _ptr(li), li.size, None, 0, C.byref(cnt), None), where)
+        count = cnt.value
+        out = np.empty((batch, max(count, 1), 5), dtype=np.uint64)  # (one digest of room: a NULL or empty buffer is the sizing call)
+        roots = np.empty((batch, 5), dtype=np.uint64)
+        if count or with_root:
+            _check(lib().tf_merkle_auth_structure_from_leafs(lp, n, batch, _ptr(li), li.size, _ptr(out), max(count, 1), C.byref(cnt),
+                                                             _ptr(roots) if with_root else None), where)
+        out = out.reshape(-1)[: batch * count * 5].reshape(batch, count, 5)
+        if batch == 1:
+            out, roots = out[0], roots[0]
+        return (out, roots) if with_root else out
+
+    sequential_authentication_structure_from_leafs = authentication_structure_from_leafs  # :514-522
+    par_authentication_structure_from_leafs = authentication_structure_from_leafs  # :532-542 -- same result by construction
+
     def root(self) -> np.ndarray:  # :624-626
         return self.nodes[1]
 

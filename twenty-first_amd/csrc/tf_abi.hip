@@ -1020,6 +1020,23 @@ int tf_merkle_authentication_structure_dev(const uint64_t* d_nodes, size_t num_l
     return sync(s);
 } TF_ABI_CATCH
 
+int tf_merkle_auth_structure_from_leafs(const uint64_t* leafs, size_t num_leafs, size_t batch, const uint64_t* leaf_indices, size_t k,
+                                        uint64_t* out_digests, size_t capacity_digests, size_t* out_count, uint64_t* roots) try {
+    return merkle_open_host(leafs, num_leafs, batch, leaf_indices, k, out_digests, capacity_digests, out_count, roots);
+} TF_ABI_CATCH
+int tf_merkle_auth_structure_from_leafs_dev(const uint64_t* d_leafs, size_t num_leafs, size_t batch, const uint64_t* leaf_indices, size_t k,
+                                            uint64_t* d_out_digests, size_t capacity_digests, size_t* out_count, uint64_t* d_roots,
+                                            void* stream) try {
+    return merkle_open_dev(d_leafs, num_leafs, batch, leaf_indices, k, d_out_digests, capacity_digests, out_count, d_roots,
+                           static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+size_t tf_merkle_auth_structure_from_leafs_workspace(size_t num_leafs, size_t batch, size_t k_nodes) try {
+    return merkle_open_workspace(num_leafs, batch, k_nodes);
+} catch (...) {  // (a size, not a status: the guard's message is kept, the size is 0)
+    ::tfi::abi_caught("C++ exception in tf_merkle_auth_structure_from_leafs_workspace", TF_ERR_INTERNAL);
+    return 0;
+}
+
 int tf_merkle_verify_proofs(const uint32_t* tree_heights, size_t n_proofs, const uint64_t* leaf_offsets, const uint64_t* leaf_indices,
                             const uint64_t* leaf_digests, const uint64_t* auth_offsets, const uint64_t* auth_digests,
                             const uint64_t* expected_roots, int* statuses) try {

@@ -10,6 +10,7 @@
 //   tf_mmr.hip    batched Merkle Mountain Range accumulators and membership proofs (mmr_kernels.h), with their host flavours
 //   tf_divide.hip division with remainder and the power-series inverse (divide_kernels.h), with their entry points
 //   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
+//   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -161,6 +162,13 @@ int merkle_root_dev(const u64* d_leaves, size_t n, u64* d_root, size_t batch, vo
 int merkle_from_rows_dev(const u64* d_rows, size_t row_len, size_t n_rows, u64* d_nodes, size_t batch, void* stream);
 int merkle_from_columns_dev(const u64* d_table, size_t n_rows, size_t n_cols, int width, size_t col_stride, u64* d_nodes, size_t batch, void* stream);
 int gather_digests_dev(const u64* d_nodes, const unsigned long long* d_idx, size_t count, u64* d_out, hipStream_t s);
+// the pieces of the level sweeps, for the unit that runs one of its own (tf_merkle_open.hip); tf_tip5.hip documents them
+int ensure_tip5(DeviceCtx* ctx);
+int launch_hash_pairs(const u64* in, u64* out, u64* leaf_copy, long long count, long long per_tree, long long in_ts, long long out_ts, long long copy_ts,
+                      hipStream_t s);
+int merkle_narrow_levels(const u64* level, long long in_ts, long long w, u64* d_nodes, long long nodes_ts, u64* d_root, u64* scratch, size_t batch,
+                         bool copy_input, hipStream_t s);
+bool merkle_narrow_from(long long w, size_t batch);  // narrow_from: the level of w nodes per tree and all above it go to merkle_narrow_levels
 extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (canonical values; tf_tip5.hip)
 // the planner's rules for a launch of `count` permutation chains (tf_tip5.hip has the measurements behind them)
 constexpr long long kCoopMaxCount = 1ll << 13;
@@ -214,6 +222,15 @@ int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, c
                    const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified, uint64_t mbase, uint64_t pbase, hipStream_t s);
 int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, const u64* leafs, const uint64_t* moff, const u64* mpaths, size_t P,
                     const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified);
+
+// ------------------------------------------------------------------------------------ tf_merkle_open.hip
+// authentication structure and roots of `batch` trees from their leafs (include/tf_hip.h has the contract): _dev takes device
+// pointers and HOST leaf indices and never waits for its stream, _host takes host pointers; the work-space rule is pure host arithmetic
+int merkle_open_dev(const u64* d_leafs, size_t n, size_t batch, const uint64_t* leaf_indices, size_t k, u64* d_out, size_t capacity, size_t* out_count,
+                    u64* d_roots, hipStream_t s);
+int merkle_open_host(const u64* leafs, size_t n, size_t batch, const uint64_t* leaf_indices, size_t k, u64* out, size_t capacity, size_t* out_count,
+                     u64* roots);
+size_t merkle_open_workspace(size_t n, size_t batch, size_t k_nodes);
 
 // ------------------------------------------------------------------------------------ tf_sponge.hip
 // the sponge calls of include/tf_hip.h.  absorb: pad = false, len = 10 n_chunks, no offsets; pad_and_absorb_all: pad = true (the _dev

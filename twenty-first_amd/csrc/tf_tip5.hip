@@ -402,4 +402,7 @@ int gather_digests_dev(const u64* d_nodes, const unsigned long long* d_idx, size
     return TF_OK;
 }
 
+// narrow_from for the unit that plans a sweep of its own (tf_merkle_open.hip): one rule, kept here with its constants
+bool merkle_narrow_from(long long w, size_t batch) { return narrow_from(w, batch); }
+
 }  // namespace tfi

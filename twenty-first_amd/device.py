@@ -267,6 +267,44 @@ def authentication_structure(nodes, num_leafs: int, leaf_indices):
     return out[: cnt.value * 5].reshape(-1, 5).copy()
 
 
+def authentication_structure_from_leafs(leafs, num_leafs: int, leaf_indices, out=None, roots=None, batch: int = 1, stream=None):
+    """util_types/merkle_tree.rs:506-542 on device buffers: the authentication structure of `leaf_indices` (a HOST list, the same for
+    every tree) from `batch` trees of num_leafs leaf digests, without a node array; `roots` (batch * 5 words), when given, receives
+    the roots.  Returns the device tensor of batch * count * 5 words (tree-major, the order of authentication_structure): `out` when
+    given -- it must hold at least that many words --, otherwise a new tensor.  Nothing is synchronised."""
+    import numpy as np
+    import torch
+
+    where = "MerkleTree::authentication_structure_from_leafs"
+    leafs = _t(leafs, "leafs")
+    _need(batch >= 1 and leafs.numel() == batch * num_leafs * 5, "leafs must hold batch * num_leafs digests")
+    li = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+    fn = _lib.lib().tf_merkle_auth_structure_from_leafs_dev
+    lp = _p(leafs)
+    cnt = C.c_size_t(0)
+    _chk(fn(lp, num_leafs, batch, _host(li), li.size, None, 0, C.byref(cnt), None, _stream(stream)), where)
+    count = cnt.value
+    words = batch * count * 5
+    if out is None:
+        out = torch.empty(max(words, 5), dtype=torch.int64, device=leafs.device)  # (one digest of room: an empty buffer is the sizing call)
+    else:
+        out = _t(out, "out")
+        _need(out.numel() >= max(words, 1), "out must hold batch * count digests (and at least one word)")
+    if roots is not None:
+        roots = _t(roots, "roots")
+        _need(roots.numel() == batch * 5, "roots must hold one digest per tree")
+    if count or roots is not None:
+        _chk(fn(lp, num_leafs, batch, _host(li), li.size, _p(out), max(count, 1), C.byref(cnt), _p(roots) if roots is not None else None,
+                _stream(stream)), where)
+    return out[:words]
+
+
+def authentication_structure_from_leafs_workspace(num_leafs: int, batch: int, k_nodes: int) -> int:
+    """Bytes of device work space authentication_structure_from_leafs requests from the library's pool for k_nodes structure nodes per
+    tree (tf_merkle_auth_structure_from_leafs_workspace: host arithmetic, no device needed)."""
+    return int(_lib.lib().tf_merkle_auth_structure_from_leafs_workspace(num_leafs, batch, k_nodes))
+
+
 def batch_evaluate(coeffs, n_coeffs: int, points, out, width: int = 1, stream=None) -> None:
     """Polynomial::batch_evaluate (math/polynomial.rs:1840-1878) on device buffers: out[i] = f(points[i])."""
     coeffs, points, out = _t(coeffs, "coeffs"), _t(points, "points"), _t(out, "out")

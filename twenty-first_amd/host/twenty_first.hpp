@@ -8,6 +8,7 @@
 //   twenty_first::Tip5::{hash_10, hash_pair, hash_varlen, permutation}   tip5/mod.rs:529-623
 //   twenty_first::MerkleTree::{par_new, sequential_new, par_frugal_root, sequential_frugal_root}
 //                                                     util_types/merkle_tree.rs:149-364
+//   twenty_first::MerkleTree::{par,sequential}_authentication_structure_from_leafs   util_types/merkle_tree.rs:506-542
 //   twenty_first::MerkleTreeError                     util_types/merkle_tree.rs:933-965
 //
 // Everything executes on the GPU through the C ABI; there is no CPU fallback in this header.
@@ -491,6 +492,26 @@ struct MerkleTree {
         std::vector<Digest> out(count);
         for (size_t i = 0; i < count; ++i) out[i] = nodes[idx[i]];
         return out;
+    }
+    // the authentication structure from the leafs alone, no node array (:532-542): one level sweep on the device; root_out, when given,
+    // receives the root the same sweep ends in
+    static std::vector<Digest> par_authentication_structure_from_leafs(const std::vector<Digest>& leafs, const std::vector<size_t>& leaf_indices,
+                                                                       Digest* root_out = nullptr) {
+        const char* where = "MerkleTree::par_authentication_structure_from_leafs";
+        const std::vector<uint64_t> li(leaf_indices.begin(), leaf_indices.end());
+        const uint64_t* lp = reinterpret_cast<const uint64_t*>(leafs.data());
+        size_t count = 0;
+        check(tf_merkle_auth_structure_from_leafs(lp, leafs.size(), 1, li.data(), li.size(), nullptr, 0, &count, nullptr), where);
+        std::vector<Digest> out(count + 1);  // (one digest of room: an empty buffer is the sizing call)
+        if (count || root_out)
+            check(tf_merkle_auth_structure_from_leafs(lp, leafs.size(), 1, li.data(), li.size(), reinterpret_cast<uint64_t*>(out.data()), out.size(),
+                                                      &count, root_out ? reinterpret_cast<uint64_t*>(root_out->values.data()) : nullptr), where);
+        out.resize(count);
+        return out;
+    }
+    static std::vector<Digest> sequential_authentication_structure_from_leafs(const std::vector<Digest>& leafs, const std::vector<size_t>& leaf_indices,
+                                                                              Digest* root_out = nullptr) {  // :514-522, same result
+        return par_authentication_structure_from_leafs(leafs, leaf_indices, root_out);
     }
     const Digest& root() const { return nodes[1]; }            // :624-626
     size_t num_leafs() const { return nodes.size() / 2; }       // :628-631
