@@ -69,7 +69,15 @@ enum tf_status {
     TF_ERR_MMR_PEAK_COUNT_MISMATCH = 23,         /* peaks.len() != num_leafs.count_ones()  :50-54 */
     TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH = 24,   /* authentication path length != height of the leaf's peak  :56-60 */
     TF_ERR_MMR_PEAK_MISMATCH = 25,               /* the path does not hash to the leaf's peak  :76 */
-    TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO = 26     /* Tip5::sample_indices panic: assert!(upper_bound.is_power_of_two())  tip5/mod.rs:637 */
+    TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO = 26,    /* Tip5::sample_indices panic: assert!(upper_bound.is_power_of_two())  tip5/mod.rs:637 */
+    /* the errors of MmrSuccessorProof::verify_internal, in the order it can raise them (mmr/mmr_successor_proof.rs:142-223) */
+    TF_ERR_MMR_INCONSISTENT_OLD = 27,            /* the old accumulator has not popcount(num_leafs) peaks  :143-145 */
+    TF_ERR_MMR_INCONSISTENT_NEW = 28,            /* the new accumulator has not popcount(num_leafs) peaks  :147-149 */
+    TF_ERR_MMR_OLD_HAS_MORE_LEAFS = 29,          /* OldHasMoreLeafsThanNew  :170 */
+    TF_ERR_MMR_SUCCESSOR_PATH_TOO_SHORT = 30,    /* AuthenticationPathTooShort  :196, :203 */
+    TF_ERR_MMR_SUCCESSOR_PATH_TOO_LONG = 31,     /* AuthenticationPathTooLong  :151-157, :213-215 */
+    TF_ERR_MMR_DIFFERENT_SHARED_PEAK = 32,       /* DifferentSharedPeak  :164-168, :182-184 */
+    TF_ERR_MMR_DIFFERENT_UNSHARED_PEAK = 33      /* DifferentUnsharedPeak  :217-220 */
 };
 
 /* Human-readable name of a status code. */
@@ -503,6 +511,7 @@ int tf_merkle_authentication_paths_dev(const uint32_t *tree_heights, size_t n_pr
                                        const uint64_t *d_auth_digests, uint64_t *d_paths_out, int *d_statuses, void *stream);
 
 /* ---- Merkle Mountain Range accumulators (util_types/mmr/; mmr.rs, mmr_accumulator.rs, mmr_membership_proof.rs, shared_basic.rs)
+ * (and mmr_successor_proof.rs)
  * A digest is 5 raw Montgomery words; a list of peaks runs from the highest to the lowest, popcount(leaf_count) digests.  Every
  * call returns TF_ERR_INVALID_ARGUMENT for a leaf count above 2^63 (the limit of mmr.rs:12-13), before the device is touched; so
  * do the other argument errors named below.  The host forms take host pointers and return when the results are in place; the
@@ -550,6 +559,57 @@ int tf_mmr_batch_mutate_leafs(uint64_t leaf_count, uint64_t *peaks, size_t n_mut
 int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t *d_peaks, size_t n_mut, const uint64_t *mut_indices, const uint64_t *d_new_leafs,
                                   const uint64_t *mut_offsets, const uint64_t *d_mut_paths, size_t n_own, const uint64_t *own_indices,
                                   const uint64_t *own_offsets, uint64_t *d_own_paths, int *d_modified, void *stream);
+/* tf_mmr_successor_proof_new: MmrSuccessorProof::new_from_batch_append (mmr_successor_proof.rs:34-91) for the accumulator
+ *   (leaf_count, old_peaks) and k new leafs.  paths_out receives tf_mmr_successor_proof_len(leaf_count, k) digests (host arithmetic:
+ *   0 where leaf_count = 0 or k < 2^trailing_zeros(leaf_count), and for arguments the calls reject); it may be NULL when that is 0.
+ *   new_peaks is NULL or receives the popcount(leaf_count + k) peaks tf_mmr_append writes: proof and peaks come from ONE level
+ *   sweep over the new leafs, not from one tree per proof digest.  The proof's digests are roots of new leafs alone, so old_peaks
+ *   is read only when new_peaks is given and leaf_count > 0.
+ *   Errors: leaf_count + k > 2^63 -> TF_ERR_INVALID_ARGUMENT; a NULL pointer where one is needed -> TF_ERR_NULL_POINTER. */
+size_t tf_mmr_successor_proof_len(uint64_t leaf_count, uint64_t k);
+int tf_mmr_successor_proof_new(uint64_t leaf_count, const uint64_t *old_peaks, const uint64_t *new_leafs, size_t k, uint64_t *paths_out,
+                               uint64_t *new_peaks);
+int tf_mmr_successor_proof_new_dev(uint64_t leaf_count, const uint64_t *d_old_peaks, const uint64_t *d_new_leafs, size_t k, uint64_t *d_paths_out,
+                                   uint64_t *d_new_peaks, void *stream);
+/* tf_mmr_verify_successor_proofs: MmrSuccessorProof::verify (:94-223) of n_proofs independent (old accumulator, new accumulator,
+ *   proof) triples in CSR layout: triple p has old_leaf_counts[p] / new_leaf_counts[p] leafs, the old peaks [old_peak_offsets[p],
+ *   old_peak_offsets[p + 1]) of old_peaks, the new peaks [new_peak_offsets[p], ..) of new_peaks and the proof digests
+ *   [path_offsets[p], ..) of paths; the three offset arrays have n_proofs + 1 entries, count digests and never decrease.  The peak
+ *   counts are those of the offsets, so an inconsistent accumulator can be stated.  statuses[p] = 0 where verify returns true, else
+ *   the first error of verify_internal: TF_ERR_MMR_INCONSISTENT_OLD, _INCONSISTENT_NEW; for an empty old accumulator a proof that is
+ *   not empty -> _SUCCESSOR_PATH_TOO_LONG; for equal counts unequal peaks -> _DIFFERENT_SHARED_PEAK, then the same length check;
+ *   _OLD_HAS_MORE_LEAFS; else the shared peaks (_DIFFERENT_SHARED_PEAK), then the proof's length (_SUCCESSOR_PATH_TOO_SHORT /
+ *   _TOO_LONG, also where the new leafs do not reach the lowest old peak and the proof is not empty), then the hash chain against
+ *   the first unshared new peak (_DIFFERENT_UNSHARED_PEAK).  MissingOldPeak / MissingNewPeak cannot occur past the first two.
+ *   Errors of the call: a count above 2^63 or decreasing offsets -> TF_ERR_INVALID_ARGUMENT.  n_proofs = 0 returns TF_OK. */
+int tf_mmr_verify_successor_proofs(size_t n_proofs, const uint64_t *old_leaf_counts, const uint64_t *new_leaf_counts, const uint64_t *old_peak_offsets,
+                                   const uint64_t *old_peaks, const uint64_t *new_peak_offsets, const uint64_t *new_peaks, const uint64_t *path_offsets,
+                                   const uint64_t *paths, int *statuses);
+int tf_mmr_verify_successor_proofs_dev(size_t n_proofs, const uint64_t *old_leaf_counts, const uint64_t *new_leaf_counts,
+                                       const uint64_t *old_peak_offsets, const uint64_t *d_old_peaks, const uint64_t *new_peak_offsets,
+                                       const uint64_t *d_new_peaks, const uint64_t *path_offsets, const uint64_t *d_paths, int *d_statuses,
+                                       void *stream);
+/* tf_mmr_update_proofs_from_append: k rounds of MmrMembershipProof::batch_update_from_append (mmr_membership_proof.rs:224-331) and
+ *   append, for n_own membership proofs of the accumulator (leaf_count, old_peaks): own proof p belongs to leaf own_indices[p]
+ *   (repeats allowed) and has the digests [own_offsets[p], own_offsets[p + 1]) of own_paths.  The updated proof p, valid in the
+ *   accumulator of leaf_count + k leafs, is written to the digests [out_offsets[p], out_offsets[p + 1]) of out_paths: the old path,
+ *   then the digests the appends add.  out_offsets (n_own + 1 entries, out_offsets[0] = 0) and modified (NULL, or n_own flags: 1
+ *   where the path grew, the union of the indices the k reference calls return) are HOST arrays in both forms, pure arithmetic and
+ *   written by every call that passes the argument checks.  With out_paths = NULL or capacity_digests = 0 and a result that is not
+ *   empty the call only sizes; capacity_digests < out_offsets[n_own] -> TF_ERR_BUFFER_TOO_SMALL and out_paths is untouched.
+ *   out_paths must not overlap own_paths.  new_peaks is NULL or as in tf_mmr_successor_proof_new.  old_peaks and new_leafs are read
+ *   where a proof grows or new_peaks is given.
+ *   Errors, before a device is touched: leaf_count + k > 2^63 -> TF_ERR_INVALID_ARGUMENT; an own index >= leaf_count ->
+ *   TF_ERR_LEAF_INDEX_INVALID; an own path whose length is not bit_length(index ^ leaf_count) - 1, the height of the leaf's peak ->
+ *   TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH; decreasing own_offsets -> TF_ERR_INVALID_ARGUMENT.  The length error is a divergence: the
+ *   reference takes the path's length for the peak's height, and on such input panics or writes a proof that cannot verify. */
+int tf_mmr_update_proofs_from_append(uint64_t leaf_count, const uint64_t *old_peaks, const uint64_t *new_leafs, size_t k, size_t n_own,
+                                     const uint64_t *own_indices, const uint64_t *own_offsets, const uint64_t *own_paths, uint64_t *out_offsets,
+                                     uint64_t *out_paths, size_t capacity_digests, int *modified, uint64_t *new_peaks);
+int tf_mmr_update_proofs_from_append_dev(uint64_t leaf_count, const uint64_t *d_old_peaks, const uint64_t *d_new_leafs, size_t k, size_t n_own,
+                                         const uint64_t *own_indices, const uint64_t *own_offsets, const uint64_t *d_own_paths,
+                                         uint64_t *out_offsets, uint64_t *d_out_paths, size_t capacity_digests, int *modified,
+                                         uint64_t *d_new_peaks, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Tip5 sponges.     replaces  Tip5::new(Domain)              tip5/mod.rs:511-526

@@ -1055,6 +1055,42 @@ class MmrMembershipProof:
         return _mmr_mutate(None, num_leafs, membership_proofs, membership_proof_leaf_indices, leaf_mutations)[1]
 
 
+    @staticmethod
+    def batch_update_from_append_many(membership_proofs, membership_proof_leaf_indices, old_leaf_count: int, new_leafs, old_peaks):
+        """batch_update_from_append (:224-331) and append, once per digest of new_leafs, in one call on the GPU: the proofs are
+        extended in place to the accumulator of old_leaf_count + len(new_leafs) leafs; returns the indices of those that grew (the
+        union of what the reference's calls return).  A proof whose length is not the height of its leaf's peak is an error
+        (TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH; the reference trusts the length, include/tf_hip.h)."""
+        proofs = list(membership_proofs)
+        idx = np.ascontiguousarray(membership_proof_leaf_indices, dtype=np.uint64).reshape(-1)
+        if idx.size != len(proofs):
+            raise ValueError(f"Lists must have same length. Got: {len(proofs)} and {idx.size}")
+        leafs = np.ascontiguousarray(_digests(new_leafs, "new_leafs").reshape(-1))
+        pk = np.ascontiguousarray(old_peaks, dtype=np.uint64).reshape(-1)
+        off, paths = MmrMembershipProof._pack(proofs)
+        out_off = np.zeros(len(proofs) + 1, dtype=np.uint64)
+        mod = np.zeros(max(len(proofs), 1), dtype=np.int32)
+
+        def call(out, capacity):
+            _check(lib().tf_mmr_update_proofs_from_append(C.c_uint64(old_leaf_count), _ptr(pk), _ptr(leafs), leafs.size // 5, len(proofs), _ptr(idx),
+                                                          _ptr(off), _ptr(paths), _ptr(out_off), out, capacity, _ptr(mod), None),
+                   "MmrMembershipProof::batch_update_from_append")
+
+        call(None, 0)
+        out = np.empty(max(5 * int(out_off[-1]), 1), dtype=np.uint64)
+        if out_off[-1]:
+            call(_ptr(out), int(out_off[-1]))
+        for p, a, b in zip(proofs, out_off[:-1].tolist(), out_off[1:].tolist()):
+            p.authentication_path = out[5 * a: 5 * b].reshape(-1, 5).copy()
+        return [i for i in range(len(proofs)) if mod[i]]
+
+    @staticmethod
+    def batch_update_from_append(membership_proofs, membership_proof_leaf_indices, old_leaf_count: int, new_leaf, old_peaks):
+        """:224-331 for one appended leaf."""
+        return MmrMembershipProof.batch_update_from_append_many(membership_proofs, membership_proof_leaf_indices, old_leaf_count,
+                                                                np.asarray(new_leaf, dtype=np.uint64).reshape(1, 5), old_peaks)
+
+
 class LeafMutation:
     """mmr_trait.rs: the leaf at leaf_index becomes new_leaf; membership_proof is its proof before the mutation."""
 
@@ -1148,6 +1184,54 @@ class MmrAccumulator:
         peaks, modified = _mmr_mutate(self._peaks, self.leaf_count, membership_proofs, membership_proof_leaf_indices, mutation_data)
         self._peaks = peaks.reshape(-1, 5)
         return modified
+
+
+class MmrSuccessorProof:
+    """mmr_successor_proof.rs:15-18: `paths`, (len, 5) raw words; states that one accumulator is what appends make of another."""
+
+    def __init__(self, paths):
+        self.paths = _digests(paths, "paths")
+
+    def __eq__(self, other):
+        return isinstance(other, MmrSuccessorProof) and np.array_equal(self.paths, other.paths)
+
+    @classmethod
+    def new_from_batch_append(cls, mmra: "MmrAccumulator", new_leafs) -> "MmrSuccessorProof":  # :34-91
+        leafs = np.ascontiguousarray(_digests(new_leafs, "new_leafs").reshape(-1))
+        n, k = mmra.num_leafs(), leafs.size // 5
+        if n + k > mmr_index.MAX_LEAFS:
+            raise ValueError("at most 2^63 leafs (mmr.rs:12-13)")
+        out = np.empty(max(5 * int(lib().tf_mmr_successor_proof_len(C.c_uint64(n), C.c_uint64(k))), 1), dtype=np.uint64)
+        _check(lib().tf_mmr_successor_proof_new(C.c_uint64(n), None, _ptr(leafs), k, _ptr(out), None), "MmrSuccessorProof::new_from_batch_append")
+        return cls(out[: 5 * int(lib().tf_mmr_successor_proof_len(C.c_uint64(n), C.c_uint64(k)))].reshape(-1, 5).copy())
+
+    @staticmethod
+    def verify_status_batch(proofs, olds, news) -> np.ndarray:
+        """Status of verify_internal (:142-223) for every (proof, old, new): 0 or its first error (27..33, include/tf_hip.h).  An
+        accumulator is an MmrAccumulator or a (leaf_count, peaks) pair, which may be inconsistent."""
+        proofs = list(proofs)
+
+        def pack(accs):
+            pairs = [(a.num_leafs(), a._peaks) if isinstance(a, MmrAccumulator) else (int(a[0]), _digests(a[1], "peaks")) for a in accs]
+            off = np.zeros(len(pairs) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([p.shape[0] for _, p in pairs])
+            flat = np.ascontiguousarray(np.concatenate([p for _, p in pairs]).reshape(-1) if pairs else np.empty(0), dtype=np.uint64)
+            return np.array([c for c, _ in pairs], dtype=np.uint64), off, flat
+
+        oc, oo, od = pack(list(olds))
+        nc, no, nd = pack(list(news))
+        if oc.size != len(proofs) or nc.size != len(proofs):
+            raise ValueError("one old and one new accumulator per proof")
+        po = np.zeros(len(proofs) + 1, dtype=np.uint64)
+        po[1:] = np.cumsum([p.paths.shape[0] for p in proofs])
+        pd = np.ascontiguousarray(np.concatenate([p.paths for p in proofs]).reshape(-1) if proofs else np.empty(0), dtype=np.uint64)
+        st = np.zeros(max(len(proofs), 1), dtype=np.int32)
+        _check(lib().tf_mmr_verify_successor_proofs(len(proofs), _ptr(oc), _ptr(nc), _ptr(oo), _ptr(od), _ptr(no), _ptr(nd), _ptr(po), _ptr(pd),
+                                                    _ptr(st)), "MmrSuccessorProof::verify")
+        return st[: len(proofs)]
+
+    def verify(self, old, new) -> bool:  # :94-96
+        return bool(self.verify_status_batch([self], [old], [new])[0] == 0)
 
 
 def bag_peaks_batch(leaf_counts, peaks) -> np.ndarray:

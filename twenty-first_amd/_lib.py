@@ -157,6 +157,13 @@ SIGNATURES = {
     "tf_mmr_verify_membership_proofs_dev": (C.c_int, [C.c_uint64, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tf_mmr_batch_mutate_leafs": (C.c_int, [C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "tf_mmr_batch_mutate_leafs_dev": (C.c_int, [C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "tf_mmr_successor_proof_len": (_sz, [C.c_uint64, C.c_uint64]),
+    "tf_mmr_successor_proof_new": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _vp, _vp]),
+    "tf_mmr_successor_proof_new_dev": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "tf_mmr_verify_successor_proofs": (C.c_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tf_mmr_verify_successor_proofs_dev": (C.c_int, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tf_mmr_update_proofs_from_append": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tf_mmr_update_proofs_from_append_dev": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "tf_tip5_sponge_init": (C.c_int, [_vp, _sz, C.c_int]),
     "tf_tip5_sponge_init_dev": (C.c_int, [_vp, _sz, C.c_int, _vp]),
     "tf_tip5_sponge_absorb": (C.c_int, [_vp, _sz, _vp, _sz]),

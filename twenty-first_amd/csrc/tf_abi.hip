@@ -198,6 +198,13 @@ const char* tf_status_string(int status) {
         case TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH: return "TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH";
         case TF_ERR_MMR_PEAK_MISMATCH: return "TF_ERR_MMR_PEAK_MISMATCH";
         case TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO: return "TF_ERR_UPPER_BOUND_NOT_POWER_OF_TWO";
+        case TF_ERR_MMR_INCONSISTENT_OLD: return "TF_ERR_MMR_INCONSISTENT_OLD";
+        case TF_ERR_MMR_INCONSISTENT_NEW: return "TF_ERR_MMR_INCONSISTENT_NEW";
+        case TF_ERR_MMR_OLD_HAS_MORE_LEAFS: return "TF_ERR_MMR_OLD_HAS_MORE_LEAFS";
+        case TF_ERR_MMR_SUCCESSOR_PATH_TOO_SHORT: return "TF_ERR_MMR_SUCCESSOR_PATH_TOO_SHORT";
+        case TF_ERR_MMR_SUCCESSOR_PATH_TOO_LONG: return "TF_ERR_MMR_SUCCESSOR_PATH_TOO_LONG";
+        case TF_ERR_MMR_DIFFERENT_SHARED_PEAK: return "TF_ERR_MMR_DIFFERENT_SHARED_PEAK";
+        case TF_ERR_MMR_DIFFERENT_UNSHARED_PEAK: return "TF_ERR_MMR_DIFFERENT_UNSHARED_PEAK";
         default: return "TF_ERR_UNKNOWN";
     }
 }
@@ -1097,6 +1104,41 @@ int tf_mmr_batch_mutate_leafs_dev(uint64_t leaf_count, uint64_t* d_peaks, size_t
                                   const uint64_t* own_offsets, uint64_t* d_own_paths, int* d_modified, void* stream) try {
     return mmr_mutate_dev(leaf_count, d_peaks, n_mut, mut_indices, d_new_leafs, mut_offsets, d_mut_paths, n_own, own_indices, own_offsets,
                           d_own_paths, d_modified, 0, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+size_t tf_mmr_successor_proof_len(uint64_t leaf_count, uint64_t k) { return mmr_successor_proof_len(leaf_count, k); }  // bit arithmetic only
+int tf_mmr_successor_proof_new(uint64_t leaf_count, const uint64_t* old_peaks, const uint64_t* new_leafs, size_t k, uint64_t* paths_out,
+                               uint64_t* new_peaks) try {
+    return mmr_successor_new_host(leaf_count, old_peaks, new_leafs, k, paths_out, new_peaks);
+} TF_ABI_CATCH
+int tf_mmr_successor_proof_new_dev(uint64_t leaf_count, const uint64_t* d_old_peaks, const uint64_t* d_new_leafs, size_t k, uint64_t* d_paths_out,
+                                   uint64_t* d_new_peaks, void* stream) try {
+    return mmr_successor_new_dev(leaf_count, d_old_peaks, d_new_leafs, k, d_paths_out, d_new_peaks, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_mmr_verify_successor_proofs(size_t n_proofs, const uint64_t* old_leaf_counts, const uint64_t* new_leaf_counts, const uint64_t* old_peak_offsets,
+                                   const uint64_t* old_peaks, const uint64_t* new_peak_offsets, const uint64_t* new_peaks, const uint64_t* path_offsets,
+                                   const uint64_t* paths, int* statuses) try {
+    return mmr_successor_verify_host(n_proofs, old_leaf_counts, new_leaf_counts, old_peak_offsets, old_peaks, new_peak_offsets, new_peaks, path_offsets,
+                                     paths, statuses);
+} TF_ABI_CATCH
+int tf_mmr_verify_successor_proofs_dev(size_t n_proofs, const uint64_t* old_leaf_counts, const uint64_t* new_leaf_counts,
+                                       const uint64_t* old_peak_offsets, const uint64_t* d_old_peaks, const uint64_t* new_peak_offsets,
+                                       const uint64_t* d_new_peaks, const uint64_t* path_offsets, const uint64_t* d_paths, int* d_statuses,
+                                       void* stream) try {
+    return mmr_successor_verify_dev(n_proofs, old_leaf_counts, new_leaf_counts, old_peak_offsets, d_old_peaks, new_peak_offsets, d_new_peaks,
+                                    path_offsets, d_paths, d_statuses, 0, 0, 0, static_cast<hipStream_t>(stream));
+} TF_ABI_CATCH
+int tf_mmr_update_proofs_from_append(uint64_t leaf_count, const uint64_t* old_peaks, const uint64_t* new_leafs, size_t k, size_t n_own,
+                                     const uint64_t* own_indices, const uint64_t* own_offsets, const uint64_t* own_paths, uint64_t* out_offsets,
+                                     uint64_t* out_paths, size_t capacity_digests, int* modified, uint64_t* new_peaks) try {
+    return mmr_update_proofs_host(leaf_count, old_peaks, new_leafs, k, n_own, own_indices, own_offsets, own_paths, out_offsets, out_paths,
+                                  capacity_digests, modified, new_peaks);
+} TF_ABI_CATCH
+int tf_mmr_update_proofs_from_append_dev(uint64_t leaf_count, const uint64_t* d_old_peaks, const uint64_t* d_new_leafs, size_t k, size_t n_own,
+                                         const uint64_t* own_indices, const uint64_t* own_offsets, const uint64_t* d_own_paths,
+                                         uint64_t* out_offsets, uint64_t* d_out_paths, size_t capacity_digests, int* modified, uint64_t* d_new_peaks,
+                                         void* stream) try {
+    return mmr_update_proofs_dev(leaf_count, d_old_peaks, d_new_leafs, k, n_own, own_indices, own_offsets, d_own_paths, out_offsets, d_out_paths,
+                                 capacity_digests, modified, d_new_peaks, 0, static_cast<hipStream_t>(stream));
 } TF_ABI_CATCH
 
 // ---- device-resident Tip5 sponges (tf_sponge.hip)

@@ -222,6 +222,20 @@ int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, c
                    const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified, uint64_t mbase, uint64_t pbase, hipStream_t s);
 int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, const u64* leafs, const uint64_t* moff, const u64* mpaths, size_t P,
                     const uint64_t* pidx, const uint64_t* poff, u64* ppaths, int* modified);
+// successor proofs and membership proofs under appends: the same level sweep as mmr_append_dev with other digests taken from it
+size_t mmr_successor_proof_len(u64 n, u64 k);
+int mmr_successor_new_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* paths_out, u64* new_peaks, hipStream_t s);
+int mmr_successor_new_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* paths_out, u64* new_peaks);
+int mmr_successor_verify_dev(size_t P, const uint64_t* old_counts, const uint64_t* new_counts, const uint64_t* old_off, const u64* old_peaks,
+                             const uint64_t* new_off, const u64* new_peaks, const uint64_t* path_off, const u64* paths, int* statuses, uint64_t old_base,
+                             uint64_t new_base, uint64_t path_base, hipStream_t s);
+int mmr_successor_verify_host(size_t P, const uint64_t* old_counts, const uint64_t* new_counts, const uint64_t* old_off, const u64* old_peaks,
+                              const uint64_t* new_off, const u64* new_peaks, const uint64_t* path_off, const u64* paths, int* statuses);
+int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, size_t P, const uint64_t* own_idx, const uint64_t* own_off,
+                          const u64* own_paths, uint64_t* out_off, u64* out_paths, size_t capacity, int* modified, u64* new_peaks, uint64_t own_base,
+                          hipStream_t s);
+int mmr_update_proofs_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, size_t P, const uint64_t* own_idx, const uint64_t* own_off,
+                           const u64* own_paths, uint64_t* out_off, u64* out_paths, size_t capacity, int* modified, u64* new_peaks);
 
 // ------------------------------------------------------------------------------------ tf_merkle_open.hip
 // authentication structure and roots of `batch` trees from their leafs (include/tf_hip.h has the contract): _dev takes device

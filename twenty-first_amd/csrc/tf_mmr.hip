@@ -127,16 +127,38 @@ inline u64 peak_index(u64 i, u64 n) {
 // After each level one move launch takes what is needed from it: the proof siblings (for appended leaf L, node (L >> h) - 1), the
 // new peak of that height (the last node of level h where bit h of n + k is set), and the old peak of height h + 1 into the first
 // slot of the next level's buffer.  Every move list is built on the host and uploaded once.
+//
+// The successor proof and the proof update (below) are the same sweep with other digests taken from it: a SweepWant names node `index`
+// of level `level`, or with old_peak the old peak of that height, and the digest of `wanted` it goes to.  They pass no proofs, may
+// pass no new_peaks (the peaks are then not written), and may pass no old_peaks: the nodes that cover old leafs then hold
+// unspecified words, and no want may name one.
+namespace {
+struct SweepWant {
+    int level;
+    u64 index;
+    bool old_peak;
+    u64 dst;
+};
+int mmr_sweep(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_peaks, u64* proofs, const std::vector<SweepWant>& wants, u64* wanted,
+              hipStream_t s);
+}  // namespace
+
 int mmr_append_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_peaks, u64* proofs, hipStream_t s) {
     if (n > kMaxLeafs || k > kMaxLeafs - n) return TF_ERR_INVALID_ARGUMENT;
     if (!new_peaks || (k && !leafs) || (n && !old_peaks)) return TF_ERR_NULL_POINTER;
+    return mmr_sweep(n, old_peaks, leafs, k, new_peaks, proofs, {}, nullptr, s);
+}
+
+namespace {
+int mmr_sweep(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_peaks, u64* proofs, const std::vector<SweepWant>& wants, u64* wanted,
+              hipStream_t s) {
     const u64 N = n + k;
     const int old_count = __builtin_popcountll(n);
     // index of the peak of height h in the old / new list (peaks above it: the set bits above h; no shift by 64)
     auto old_at = [&](int h) { return h == 63 ? 0ull : (u64)__builtin_popcountll(n >> (h + 1)); };
     auto new_at = [&](int h) { return h == 63 ? 0ull : (u64)__builtin_popcountll(N >> (h + 1)); };
     if (k == 0) {
-        if (old_count) HIPCHK(hipMemcpyAsync(new_peaks, old_peaks, 5 * sizeof(u64) * old_count, hipMemcpyDeviceToDevice, s));
+        if (old_count && new_peaks) HIPCHK(hipMemcpyAsync(new_peaks, old_peaks, 5 * sizeof(u64) * old_count, hipMemcpyDeviceToDevice, s));
         return TF_OK;
     }
     int dev = 0;
@@ -167,17 +189,27 @@ int mmr_append_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64*
     std::vector<unsigned long long> moves;
     std::vector<size_t> moves_at(top + 2, 0);
     const bool odd_pair = n & 1;  // level 1 starts with hash_pair(old peak of height 0, leaf 0)
+    std::vector<std::vector<unsigned long long>> want_moves(wants.empty() ? 0 : top + 1);  // by the level whose launch makes them
+    for (const SweepWant& w : wants) {
+        if (!w.old_peak && (w.level > top || w.index < start[w.level] || w.index >= end[w.level])) return TF_ERR_INTERNAL;  // not a node of the sweep
+        auto& list = want_moves[std::min(w.level, top)];
+        list.insert(list.end(), {w.old_peak ? at(S_OLD, old_at(w.level)) : node_src(w.level, w.index), at(D_PROOFS, w.dst)});
+    }
     for (int h = 0; h <= top; ++h) {
         moves_at[h] = moves.size() / 2;
-        if (h == 0 && odd_pair && top >= 1) moves.insert(moves.end(), {at(S_OLD, old_at(0)), at(D_EVEN, 0), at(S_LEAFS, 0), at(D_EVEN, 1)});
+        if (h == 0 && odd_pair && top >= 1) {
+            if (old_peaks) moves.insert(moves.end(), {at(S_OLD, old_at(0)), at(D_EVEN, 0)});
+            moves.insert(moves.end(), {at(S_LEAFS, 0), at(D_EVEN, 1)});
+        }
+        if (!wants.empty()) moves.insert(moves.end(), want_moves[h].begin(), want_moves[h].end());
         if (proofs && h < 63) {  // the appended leafs whose proof has a digest h: bits 0 .. h of L set, L = -1 mod 2^(h + 1)
             const u64 m = 2ull << h;
             for (u64 L = n + ((m - 1 - (n & (m - 1))) & (m - 1)); L < N; L += m)
                 moves.insert(moves.end(), {node_src(h, (L >> h) - 1), at(D_PROOFS, proof_off[L - n] + (u64)h)});
         }
-        if ((N >> h) & 1) moves.insert(moves.end(), {node_src(h, end[h] - 1), at(D_PEAKS, new_at(h))});
-        if (h < top && ((n >> (h + 1)) & 1)) moves.insert(moves.end(), {at(S_OLD, old_at(h + 1)), at(buf_dst(h + 1), 0)});
-        if (h == top)  // peaks above the sweep are old peaks
+        if (new_peaks && ((N >> h) & 1)) moves.insert(moves.end(), {node_src(h, end[h] - 1), at(D_PEAKS, new_at(h))});
+        if (old_peaks && h < top && ((n >> (h + 1)) & 1)) moves.insert(moves.end(), {at(S_OLD, old_at(h + 1)), at(buf_dst(h + 1), 0)});
+        if (new_peaks && h == top)  // peaks above the sweep are old peaks
             for (int g = top + 1; g < 64; ++g)
                 if ((N >> g) & 1) moves.insert(moves.end(), {at(S_OLD, old_at(g)), at(D_PEAKS, new_at(g))});
     }
@@ -188,7 +220,7 @@ int mmr_append_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64*
     Temp even(s), odd(s);
     TRY(even.alloc(5 * even_words));
     TRY(odd.alloc(5 * odd_words));
-    const MmrMoveArrays arrays{{leafs, old_peaks, even.p, odd.p}, {proofs, new_peaks, even.p, odd.p}};
+    const MmrMoveArrays arrays{{leafs, old_peaks, even.p, odd.p}, {wants.empty() ? proofs : wanted, new_peaks, even.p, odd.p}};
     auto level = [&](int h) { return h & 1 ? odd.p : even.p; };
     for (int h = 0; h <= top; ++h) {
         TRY(launch_moves(arrays, dm + 2 * moves_at[h], (long long)(moves_at[h + 1] - moves_at[h]), s));
@@ -205,6 +237,7 @@ int mmr_append_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64*
     }
     return TF_OK;
 }
+}  // namespace
 
 // ------------------------------------------------------------------------------------ bag_peaks
 int mmr_bag_peaks_dev(const uint64_t* leaf_counts, size_t n_acc, const u64* peaks, u64* out, hipStream_t s) {
@@ -364,6 +397,153 @@ int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, c
     return TF_OK;
 }
 
+// ------------------------------------------------------------------------------------ successor proofs
+// MmrSuccessorProof (mmr_successor_proof.rs).  With t = trailing_zeros(n) and H the highest bit in which n and N = n + k differ,
+// the proof starts with the root of the first 2^t new leafs, node (t, n >> t) of the sweep, and climbs to level H: where the node
+// (g, n >> g) is a left child its sibling (g, (n >> g) + 1) is a sweep node of new leafs only and joins the proof, where it is a
+// right child the sibling is the old peak of height g, which the verifier has.
+namespace {
+inline int top_difference(u64 n, u64 N) { return 63 - __builtin_clzll(n ^ N); }  // n != N
+}  // namespace
+
+size_t mmr_successor_proof_len(u64 n, u64 k) {
+    if (n > kMaxLeafs || k > kMaxLeafs - n || n == 0) return 0;
+    const int t = __builtin_ctzll(n);
+    if (k < (1ull << t)) return 0;
+    const int H = top_difference(n, n + k);  // > t: the first 2^t new leafs carry into bit t + 1 or above
+    return (size_t)(1 + (H - t) - __builtin_popcountll((n >> t) & ((1ull << (H - t)) - 1)));
+}
+
+int mmr_successor_new_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* paths_out, u64* new_peaks, hipStream_t s) {
+    if (n > kMaxLeafs || k > kMaxLeafs - n) return TF_ERR_INVALID_ARGUMENT;
+    const size_t len = mmr_successor_proof_len(n, k);
+    if ((len && !paths_out) || (k && (len || new_peaks) && !leafs) || (n && new_peaks && !old_peaks)) return TF_ERR_NULL_POINTER;
+    if (!len) return new_peaks ? mmr_sweep(n, old_peaks, leafs, k, new_peaks, nullptr, {}, nullptr, s) : TF_OK;
+    const int t = __builtin_ctzll(n), H = top_difference(n, n + k);
+    std::vector<SweepWant> wants{{t, n >> t, false, 0}};
+    for (int g = t; g < H; ++g)
+        if (!((n >> g) & 1)) wants.push_back({g, (n >> g) + 1, false, (u64)wants.size()});
+    return mmr_sweep(n, new_peaks ? old_peaks : nullptr, leafs, k, new_peaks, nullptr, wants, paths_out, s);
+}
+
+// One chain per proof (mmr_kernels.h: mmr_successor_kernel); the host settles what the counts settle, in verify_internal's order.
+int mmr_successor_verify_dev(size_t P, const uint64_t* old_counts, const uint64_t* new_counts, const uint64_t* old_off, const u64* old_peaks,
+                             const uint64_t* new_off, const u64* new_peaks, const uint64_t* path_off, const u64* paths, int* statuses, uint64_t old_base,
+                             uint64_t new_base, uint64_t path_base, hipStream_t s) {
+    if (P == 0) return TF_OK;
+    if (!old_counts || !new_counts || !old_off || !new_off || !path_off || !statuses) return TF_ERR_NULL_POINTER;
+    for (size_t p = 0; p < P; ++p)
+        if (old_counts[p] > kMaxLeafs || new_counts[p] > kMaxLeafs) return TF_ERR_INVALID_ARGUMENT;
+    TRY(check_offsets(old_off, P));
+    TRY(check_offsets(new_off, P));
+    TRY(check_offsets(path_off, P));
+    if (old_off[0] < old_base || new_off[0] < new_base || path_off[0] < path_base) return TF_ERR_INVALID_ARGUMENT;
+    if ((old_off[P] > old_off[0] && !old_peaks) || (new_off[P] > new_off[0] && !new_peaks) || (path_off[P] > path_off[0] && !paths))
+        return TF_ERR_NULL_POINTER;
+    std::vector<tfm::tfk::MmrSuccessorChain> ch(P);
+    for (size_t p = 0; p < P; ++p) {
+        const u64 n = old_counts[p], N = new_counts[p], n_old = old_off[p + 1] - old_off[p], n_new = new_off[p + 1] - new_off[p];
+        const u64 len = path_off[p + 1] - path_off[p];
+        tfm::tfk::MmrSuccessorChain c{p, 0, path_off[p] - path_base, old_off[p] - old_base, new_off[p] - new_base, (unsigned)n_old, 0, 0, 0, 0};
+        const unsigned empty_path = len ? TF_ERR_MMR_SUCCESSOR_PATH_TOO_LONG : TF_OK;
+        if ((u64)__builtin_popcountll(n) != n_old) c.verdict = TF_ERR_MMR_INCONSISTENT_OLD;
+        else if ((u64)__builtin_popcountll(N) != n_new) c.verdict = TF_ERR_MMR_INCONSISTENT_NEW;
+        else if (n == 0) c.verdict = empty_path;
+        else if (n == N) {
+            c.cmp = (unsigned)n_old;
+            c.verdict = empty_path;
+        } else if (n > N) c.verdict = TF_ERR_MMR_OLD_HAS_MORE_LEAFS;
+        else {
+            const int t = __builtin_ctzll(n), H = top_difference(n, N);
+            c.cmp = H == 63 ? 0u : (unsigned)__builtin_popcountll(n >> (H + 1));  // the peaks above the first difference
+            const u64 want = mmr_successor_proof_len(n, N - n);
+            if (want == 0) c.verdict = empty_path;  // the new leafs do not reach the lowest old peak
+            else if (len < want) c.verdict = TF_ERR_MMR_SUCCESSOR_PATH_TOO_SHORT;
+            else if (len > want) c.verdict = TF_ERR_MMR_SUCCESSOR_PATH_TOO_LONG;
+            else {
+                c.steps = (unsigned)(H - t);
+                c.bits = n >> t;
+            }
+        }
+        ch[p] = c;
+    }
+    std::stable_sort(ch.begin(), ch.end(), [](const auto& x, const auto& y) { return x.steps > y.steps; });
+    int dev = 0;
+    TRY(ctx_dev(&dev));
+    Upload up;
+    TRY(up.put(dev, ch.data(), ch.size() * sizeof(ch[0]), s));
+    hipLaunchKernelGGL(tfm::tfk::mmr_successor_kernel, dim3(grid_for((long long)P, 64)), dim3(256), 0, s,
+                       static_cast<const tfm::tfk::MmrSuccessorChain*>(up.d), (long long)P, old_peaks, new_peaks, paths, statuses);
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+}
+
+// ------------------------------------------------------------------------------------ membership proofs under appends
+// k rounds of MmrMembershipProof::batch_update_from_append (mmr_membership_proof.rs:224-331) and append.  The proof of leaf i has
+// h0 = bit_length(i ^ n) - 1 digests in the MMR of n leafs (the height of its peak) and max(h0, H) in that of N = n + k, the old
+// path first.  The new digests are those of levels h0 .. H - 1: at level h0 the sweep node (h0, n >> h0), which grows beside the old
+// peak; above it the sibling of node (g, n >> g), which is the old peak of height g or the sweep node (g, (n >> g) + 1).  So every
+// proof under one old peak receives the same suffix: the sweep fills one list per old peak, and mmr_gather_paths_kernel writes each
+// proof as its old path and its peak's list.
+int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t k, size_t P, const uint64_t* own_idx, const uint64_t* own_off,
+                          const u64* own_paths, uint64_t* out_off, u64* out_paths, size_t capacity, int* modified, u64* new_peaks, uint64_t own_base,
+                          hipStream_t s) {
+    if (n > kMaxLeafs || k > kMaxLeafs - n) return TF_ERR_INVALID_ARGUMENT;
+    if (!out_off || (P && (!own_idx || !own_off))) return TF_ERR_NULL_POINTER;
+    for (size_t p = 0; p < P; ++p)
+        if (own_idx[p] >= n) return TF_ERR_LEAF_INDEX_INVALID;
+    for (size_t p = 0; p < P; ++p)
+        if (own_off[p + 1] >= own_off[p] && own_off[p + 1] - own_off[p] != (u64)top_difference(own_idx[p], n))
+            return TF_ERR_MMR_AUTH_PATH_LENGTH_MISMATCH;
+    if (P) TRY(check_offsets(own_off, P));
+    if (P && own_off[0] < own_base) return TF_ERR_INVALID_ARGUMENT;
+    const u64 N = n + k;
+    const int H = k ? top_difference(n, N) : -1;
+    out_off[0] = 0;
+    bool grows = false;
+    for (size_t p = 0; p < P; ++p) {
+        const int h0 = top_difference(own_idx[p], n);
+        out_off[p + 1] = out_off[p] + (u64)std::max(h0, H);
+        if (modified) modified[p] = H > h0;
+        grows |= H > h0;
+    }
+    const u64 total = out_off[P];
+    if (total && (!out_paths || capacity == 0)) return TF_OK;  // the sizing call
+    if (capacity < total) return TF_ERR_BUFFER_TOO_SMALL;
+    // one list per old peak below H
+    std::vector<SweepWant> wants;
+    u64 list_at[64] = {};
+    for (int h0 = 0; h0 < H; ++h0) {
+        if (!((n >> h0) & 1)) continue;
+        list_at[h0] = wants.size();
+        wants.push_back({h0, n >> h0, false, (u64)wants.size()});
+        for (int g = h0 + 1; g < H; ++g)
+            wants.push_back((n >> g) & 1 ? SweepWant{g, 0, true, (u64)wants.size()} : SweepWant{g, (n >> g) + 1, false, (u64)wants.size()});
+    }
+    const bool sweep = new_peaks || grows;
+    if ((sweep && ((k && !leafs) || (n && !old_peaks))) || (P && own_off[P] > own_off[0] && !own_paths)) return TF_ERR_NULL_POINTER;
+    if (!sweep && !total) return TF_OK;
+    int dev = 0;
+    TRY(ctx_dev(&dev));
+    Temp table(s);
+    if (grows) {
+        TRY(table.alloc(5 * wants.size()));
+        TRY(mmr_sweep(n, old_peaks, leafs, k, new_peaks, nullptr, wants, table.p, s));
+    } else if (sweep) TRY(mmr_sweep(n, old_peaks, leafs, k, new_peaks, nullptr, {}, nullptr, s));
+    if (!total) return TF_OK;
+    std::vector<tfm::tfk::MmrGatherDesc> desc(P);
+    for (size_t p = 0; p < P; ++p) {
+        const int h0 = top_difference(own_idx[p], n);
+        desc[p] = {own_off[p] - own_base, out_off[p], H > h0 ? list_at[h0] : 0, (unsigned)h0, (unsigned)(H > h0 ? H - h0 : 0)};
+    }
+    Upload up;
+    TRY(up.put(dev, desc.data(), desc.size() * sizeof(desc[0]), s));
+    hipLaunchKernelGGL(tfm::tfk::mmr_gather_paths_kernel, dim3(grid_for(16 * (long long)P, 256)), dim3(256), 0, s,
+                       static_cast<const tfm::tfk::MmrGatherDesc*>(up.d), (long long)P, own_paths, table.p, out_paths);
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+}
+
 // ------------------------------------------------------------------------------------ host flavours
 // Upload the inputs (waiting for each upload: pageable memory), run the _dev form on the thread's stream, copy back, synchronise.
 namespace {
@@ -457,6 +637,85 @@ int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, 
     if (np) TRY(d2h(peaks, dpk.p, 5 * np, s));
     if (nq) TRY(d2h(ppaths + 5 * poff[0], dq.p, 5 * nq, s));
     if (P) HIPCHK(hipMemcpyAsync(modified, dmod.p, P * sizeof(int), hipMemcpyDeviceToHost, s));
+    return sync(s);
+}
+
+int mmr_successor_new_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* paths_out, u64* new_peaks) {
+    if (n > kMaxLeafs || k > kMaxLeafs - n) return TF_ERR_INVALID_ARGUMENT;
+    const size_t len = mmr_successor_proof_len(n, k);
+    if ((len && !paths_out) || (k && (len || new_peaks) && !leafs) || (n && new_peaks && !old_peaks)) return TF_ERR_NULL_POINTER;
+    if (!len && !new_peaks) return TF_OK;
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    hipStream_t s = host_stream();
+    const size_t np_old = new_peaks ? __builtin_popcountll(n) : 0, np_new = new_peaks ? __builtin_popcountll(n + k) : 0;
+    Temp dold(s), dl(s), dnew(s), dpa(s);
+    TRY(up_words(dold, old_peaks, 5 * np_old, s));
+    TRY(up_words(dl, leafs, 5 * k, s));
+    TRY(dnew.alloc(5 * np_new));
+    TRY(dpa.alloc(5 * len));
+    u64 dummy = 0;
+    TRY(mmr_successor_new_dev(n, np_old ? dold.p : (new_peaks ? &dummy : nullptr), k ? dl.p : &dummy, k, dpa.p,
+                              new_peaks ? (np_new ? dnew.p : &dummy) : nullptr, s));
+    if (len) TRY(d2h(paths_out, dpa.p, 5 * len, s));
+    if (np_new) TRY(d2h(new_peaks, dnew.p, 5 * np_new, s));
+    return sync(s);
+}
+
+int mmr_successor_verify_host(size_t P, const uint64_t* old_counts, const uint64_t* new_counts, const uint64_t* old_off, const u64* old_peaks,
+                              const uint64_t* new_off, const u64* new_peaks, const uint64_t* path_off, const u64* paths, int* statuses) {
+    if (P == 0) return TF_OK;
+    if (!old_counts || !new_counts || !old_off || !new_off || !path_off || !statuses) return TF_ERR_NULL_POINTER;
+    for (size_t p = 0; p < P; ++p)
+        if (old_counts[p] > kMaxLeafs || new_counts[p] > kMaxLeafs) return TF_ERR_INVALID_ARGUMENT;
+    TRY(check_offsets(old_off, P));
+    TRY(check_offsets(new_off, P));
+    TRY(check_offsets(path_off, P));
+    const size_t no = old_off[P] - old_off[0], nn = new_off[P] - new_off[0], na = path_off[P] - path_off[0];
+    if ((no && !old_peaks) || (nn && !new_peaks) || (na && !paths)) return TF_ERR_NULL_POINTER;
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    hipStream_t s = host_stream();
+    Temp dold(s), dnew(s), dpa(s), dst(s);
+    TRY(up_words(dold, no ? old_peaks + 5 * old_off[0] : nullptr, 5 * no, s));
+    TRY(up_words(dnew, nn ? new_peaks + 5 * new_off[0] : nullptr, 5 * nn, s));
+    TRY(up_words(dpa, na ? paths + 5 * path_off[0] : nullptr, 5 * na, s));
+    TRY(dst.alloc((P + 1) / 2));
+    u64 dummy = 0;
+    TRY(mmr_successor_verify_dev(P, old_counts, new_counts, old_off, no ? dold.p : &dummy, new_off, nn ? dnew.p : &dummy, path_off, na ? dpa.p : &dummy,
+                                 reinterpret_cast<int*>(dst.p), old_off[0], new_off[0], path_off[0], s));
+    HIPCHK(hipMemcpyAsync(statuses, dst.p, P * sizeof(int), hipMemcpyDeviceToHost, s));
+    return sync(s);
+}
+
+int mmr_update_proofs_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, size_t P, const uint64_t* own_idx, const uint64_t* own_off,
+                           const u64* own_paths, uint64_t* out_off, u64* out_paths, size_t capacity, int* modified, u64* new_peaks) {
+    // the argument errors, the offsets, the flags and the sizing rule are the _dev form's, which touches no device for them
+    TRY(mmr_update_proofs_dev(n, nullptr, nullptr, k, P, own_idx, own_off, nullptr, out_off, nullptr, 0, modified, nullptr, 0, nullptr));
+    const u64 total = out_off[P];
+    if (total && (!out_paths || capacity == 0)) return TF_OK;
+    if (capacity < total) return TF_ERR_BUFFER_TOO_SMALL;
+    if (!total && !new_peaks) return TF_OK;
+    const size_t nq = P ? own_off[P] - own_off[0] : 0;
+    // what the device call will need (it repeats the check on the device copies)
+    const bool grows = total > nq, sweep = new_peaks || grows;
+    if ((sweep && ((k && !leafs) || (n && !old_peaks))) || (nq && !own_paths)) return TF_ERR_NULL_POINTER;
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    hipStream_t s = host_stream();
+    const size_t np_old = sweep ? __builtin_popcountll(n) : 0, np_new = new_peaks ? __builtin_popcountll(n + k) : 0;
+    Temp dold(s), dl(s), dq(s), dout(s), dnew(s);
+    TRY(up_words(dold, old_peaks, 5 * np_old, s));
+    TRY(up_words(dl, sweep ? leafs : nullptr, sweep ? 5 * k : 0, s));
+    TRY(up_words(dq, nq ? own_paths + 5 * own_off[0] : nullptr, 5 * nq, s));
+    TRY(dout.alloc(5 * total));
+    TRY(dnew.alloc(5 * np_new));
+    u64 dummy = 0;
+    TRY(mmr_update_proofs_dev(n, np_old ? dold.p : &dummy, k && sweep ? dl.p : &dummy, k, P, own_idx, own_off, nq ? dq.p : &dummy, out_off,
+                              total ? dout.p : &dummy, total ? (size_t)total : 1, modified, new_peaks ? (np_new ? dnew.p : &dummy) : nullptr,
+                              P ? own_off[0] : 0, s));
+    if (total) TRY(d2h(out_paths, dout.p, 5 * total, s));
+    if (np_new) TRY(d2h(new_peaks, dnew.p, 5 * np_new, s));
     return sync(s);
 }
 

@@ -704,3 +704,72 @@ def mmr_batch_mutate_leafs(leaf_count: int, peaks, mut_indices, new_leafs, mut_o
     _chk(_lib.lib().tf_mmr_batch_mutate_leafs_dev(C.c_uint64(leaf_count), _opt(peaks, "peaks"), M, _host(mi), _p(new_leafs), _host(mo),
                                                   _p(mut_paths), P, _host(oi), _host(oo), _p(own_paths), mod_p, _stream(stream)),
          "batch_mutate_leaf_and_update_mps")
+
+
+def mmr_successor_proof_len(leaf_count: int, k: int) -> int:
+    """Digests of MmrSuccessorProof::new_from_batch_append for an accumulator of leaf_count leafs and k new ones (host arithmetic)."""
+    return int(_lib.lib().tf_mmr_successor_proof_len(C.c_uint64(leaf_count), C.c_uint64(k)))
+
+
+def mmr_successor_proof_new(leaf_count: int, old_peaks, new_leafs, paths_out, new_peaks=None, stream=None) -> int:
+    """MmrSuccessorProof::new_from_batch_append (mmr_successor_proof.rs:34-91): paths_out receives the proof's digests (their number is
+    returned), new_peaks (if given) the peaks of the accumulator after the appends, from the same level sweep.  old_peaks may be None
+    without new_peaks.  Nothing is synchronised."""
+    new_leafs = _t(new_leafs, "new_leafs")
+    _need(new_leafs.numel() % 5 == 0, "new_leafs must hold whole digests")
+    k = new_leafs.numel() // 5
+    n = mmr_successor_proof_len(leaf_count, k)
+    _need(n == 0 or (paths_out is not None and _t(paths_out, "paths_out").numel() >= 5 * n), "paths_out must hold mmr_successor_proof_len digests")
+    if new_peaks is not None:
+        _need(_t(new_peaks, "new_peaks").numel() >= 5 * bin(leaf_count + k).count("1"), "new_peaks must hold popcount(leaf_count + k) digests")
+        _need(leaf_count == 0 or (old_peaks is not None and _t(old_peaks, "old_peaks").numel() >= 5 * bin(leaf_count).count("1")),
+              "old_peaks must hold popcount(leaf_count) digests")
+    _chk(_lib.lib().tf_mmr_successor_proof_new_dev(C.c_uint64(leaf_count), _opt(old_peaks, "old_peaks"), _p(new_leafs), k,
+                                                   _opt(paths_out, "paths_out"), _opt(new_peaks, "new_peaks"), _stream(stream)),
+         "MmrSuccessorProof::new_from_batch_append")
+    return n
+
+
+def mmr_verify_successor_proofs(old_leaf_counts, new_leaf_counts, old_peak_offsets, old_peaks, new_peak_offsets, new_peaks, path_offsets, paths,
+                                statuses, stream=None) -> None:
+    """MmrSuccessorProof::verify (mmr_successor_proof.rs:94-223) of a batch of (old, new, proof) triples in CSR layout: statuses[p]
+    (device int32) = 0 or the first error of verify_internal (27..33).  Counts and the three offset arrays (n_proofs + 1 entries, in
+    digests) are host arrays; peaks and paths are on the device.  Nothing is synchronised."""
+    oc, nc = _u64_host(old_leaf_counts), _u64_host(new_leaf_counts)
+    oo, no, po = _u64_host(old_peak_offsets), _u64_host(new_peak_offsets), _u64_host(path_offsets)
+    n = oc.size
+    _need(nc.size == n and oo.size == n + 1 and no.size == n + 1 and po.size == n + 1, "one count per proof, offsets one entry more")
+    old_peaks, new_peaks, paths = _t(old_peaks, "old_peaks"), _t(new_peaks, "new_peaks"), _t(paths, "paths")
+    statuses = _status_tensor(statuses, n)
+    _need(old_peaks.numel() >= 5 * int(oo[-1]) and new_peaks.numel() >= 5 * int(no[-1]) and paths.numel() >= 5 * int(po[-1]),
+          "buffer sizes do not match the offsets")
+    _chk(_lib.lib().tf_mmr_verify_successor_proofs_dev(n, _host(oc), _host(nc), _host(oo), _p(old_peaks), _host(no), _p(new_peaks), _host(po),
+                                                       _p(paths), _p(statuses), _stream(stream)), "MmrSuccessorProof::verify")
+
+
+def mmr_update_proofs_from_append(leaf_count: int, old_peaks, new_leafs, own_indices, own_offsets, own_paths, out_paths=None, new_peaks=None,
+                                  stream=None):
+    """k rounds of MmrMembershipProof::batch_update_from_append (mmr_membership_proof.rs:224-331) and append for the proofs
+    (own_indices, own_offsets: host arrays; own_paths: device): out_paths receives every proof in the accumulator of leaf_count + k
+    leafs, at the returned offsets.  Returns (out_offsets, modified) as host arrays; with out_paths=None the call only sizes
+    (out_offsets[-1] digests).  new_peaks as in mmr_successor_proof_new.  Nothing is synchronised."""
+    import numpy as np
+
+    oi, oo = _u64_host(own_indices), _u64_host(own_offsets)
+    P = oi.size
+    _need(oo.size == P + 1, "offsets need one entry more than indices")
+    new_leafs, own_paths = _t(new_leafs, "new_leafs"), _t(own_paths, "own_paths")
+    _need(new_leafs.numel() % 5 == 0, "new_leafs must hold whole digests")
+    k = new_leafs.numel() // 5
+    _need(own_paths.numel() >= 5 * int(oo[-1]), "own_paths does not match own_offsets")
+    if new_peaks is not None:
+        _need(_t(new_peaks, "new_peaks").numel() >= 5 * bin(leaf_count + k).count("1"), "new_peaks must hold popcount(leaf_count + k) digests")
+    _need(old_peaks is None or _t(old_peaks, "old_peaks").numel() >= 5 * bin(leaf_count).count("1"), "old_peaks must hold popcount(leaf_count) digests")
+    out_off = np.zeros(P + 1, dtype=np.uint64)
+    modified = np.zeros(max(P, 1), dtype=np.int32)
+    capacity = 0 if out_paths is None else _t(out_paths, "out_paths").numel() // 5
+    _chk(_lib.lib().tf_mmr_update_proofs_from_append_dev(C.c_uint64(leaf_count), _opt(old_peaks, "old_peaks"), _p(new_leafs), k, P, _host(oi),
+                                                         _host(oo), _p(own_paths), _host(out_off), _opt(out_paths, "out_paths"), capacity,
+                                                         _host(modified), _opt(new_peaks, "new_peaks"), _stream(stream)),
+         "MmrMembershipProof::batch_update_from_append")
+    return out_off, modified[:P]

@@ -636,6 +636,38 @@ struct MmrMembershipProof {  // mmr_membership_proof.rs:23-34
             off.push_back(paths.size());
         }
     }
+    // batch_update_from_append (:224-331) and append, once per digest of new_leafs, in one call: the proofs are extended in place to the
+    // accumulator of old_leaf_count + new_leafs.size() leafs; returns the indices of those that grew, which is the union of what the
+    // reference's calls return.  A proof whose length is not the height of its leaf's peak is an error (include/tf_hip.h).
+    static std::vector<size_t> batch_update_from_append_many(std::vector<MmrMembershipProof>& proofs, const std::vector<uint64_t>& leaf_indices,
+                                                             uint64_t old_leaf_count, const std::vector<Digest>& new_leafs,
+                                                             const std::vector<Digest>& old_peaks) {
+        if (leaf_indices.size() != proofs.size()) throw std::invalid_argument("Lists must have same length");
+        std::vector<uint64_t> off, out_off(proofs.size() + 1);
+        std::vector<Digest> paths;
+        pack(proofs, off, paths);
+        std::vector<int> mod(proofs.size() + 1);
+        auto call = [&](Digest* out, size_t capacity) {
+            check(tf_mmr_update_proofs_from_append(old_leaf_count, reinterpret_cast<const uint64_t*>(old_peaks.data()),
+                                                   reinterpret_cast<const uint64_t*>(new_leafs.data()), new_leafs.size(), proofs.size(),
+                                                   leaf_indices.data(), off.data(), reinterpret_cast<const uint64_t*>(paths.data()), out_off.data(),
+                                                   reinterpret_cast<uint64_t*>(out), capacity, mod.data(), nullptr),
+                  "MmrMembershipProof::batch_update_from_append");
+        };
+        call(nullptr, 0);  // sizes
+        std::vector<Digest> out(out_off.back() + 1);
+        if (out_off.back()) call(out.data(), out_off.back());
+        std::vector<size_t> grown;
+        for (size_t p = 0; p < proofs.size(); ++p) {
+            proofs[p].authentication_path.assign(out.begin() + (long)out_off[p], out.begin() + (long)out_off[p + 1]);
+            if (mod[p]) grown.push_back(p);
+        }
+        return grown;
+    }
+    static std::vector<size_t> batch_update_from_append(std::vector<MmrMembershipProof>& proofs, const std::vector<uint64_t>& leaf_indices,
+                                                        uint64_t old_leaf_count, const Digest& new_leaf, const std::vector<Digest>& old_peaks) {
+        return batch_update_from_append_many(proofs, leaf_indices, old_leaf_count, {new_leaf}, old_peaks);
+    }
 };
 
 struct LeafMutation {  // mmr_trait.rs
@@ -717,6 +749,47 @@ struct MmrAccumulator {  // mmr_accumulator.rs
     std::vector<size_t> batch_mutate_leaf_and_update_mps(std::vector<MmrMembershipProof>& proofs, const std::vector<uint64_t>& indices,
                                                          const std::vector<LeafMutation>& mutations) {  // :180-302
         return mmr_batch_mutate(leaf_count, &peaks, proofs, indices, mutations);
+    }
+};
+
+struct MmrSuccessorProof {  // mmr_successor_proof.rs:15-18
+    std::vector<Digest> paths;
+    bool operator==(const MmrSuccessorProof& o) const { return paths == o.paths; }
+
+    static MmrSuccessorProof new_from_batch_append(const MmrAccumulator& mmra, const std::vector<Digest>& new_leafs) {  // :34-91
+        MmrSuccessorProof p;
+        p.paths.resize(tf_mmr_successor_proof_len(mmra.leaf_count, new_leafs.size()) + 1);  // (+ 1: never an empty buffer)
+        check(tf_mmr_successor_proof_new(mmra.leaf_count, nullptr, reinterpret_cast<const uint64_t*>(new_leafs.data()), new_leafs.size(),
+                                         reinterpret_cast<uint64_t*>(p.paths.data()), nullptr),
+              "MmrSuccessorProof::new_from_batch_append");
+        p.paths.pop_back();
+        return p;
+    }
+    // verify_internal (:142-223) of many (proof, old, new) triples: 0, or its first error (TF_ERR_MMR_INCONSISTENT_OLD ..)
+    static std::vector<int> verify_statuses(const std::vector<MmrSuccessorProof>& proofs, const std::vector<MmrAccumulator>& olds,
+                                            const std::vector<MmrAccumulator>& news) {
+        if (olds.size() != proofs.size() || news.size() != proofs.size()) throw std::invalid_argument("one old and one new accumulator per proof");
+        std::vector<uint64_t> oc, nc, oo(1, 0), no(1, 0), po(1, 0);
+        std::vector<Digest> od, nd, pd;
+        for (size_t p = 0; p < proofs.size(); ++p) {
+            oc.push_back(olds[p].leaf_count);
+            nc.push_back(news[p].leaf_count);
+            od.insert(od.end(), olds[p].peaks.begin(), olds[p].peaks.end());
+            nd.insert(nd.end(), news[p].peaks.begin(), news[p].peaks.end());
+            pd.insert(pd.end(), proofs[p].paths.begin(), proofs[p].paths.end());
+            oo.push_back(od.size());
+            no.push_back(nd.size());
+            po.push_back(pd.size());
+        }
+        std::vector<int> st(proofs.size());
+        check(tf_mmr_verify_successor_proofs(proofs.size(), oc.data(), nc.data(), oo.data(), reinterpret_cast<const uint64_t*>(od.data()), no.data(),
+                                             reinterpret_cast<const uint64_t*>(nd.data()), po.data(), reinterpret_cast<const uint64_t*>(pd.data()),
+                                             st.data()),
+              "MmrSuccessorProof::verify");
+        return st;
+    }
+    bool verify(const MmrAccumulator& old_mmra, const MmrAccumulator& new_mmra) const {  // :94-96
+        return verify_statuses({*this}, {old_mmra}, {new_mmra})[0] == TF_OK;
     }
 };
 
