@@ -681,6 +681,71 @@ int tf_inverse_or_zero_bfe_dev(const uint64_t *d_in, size_t n, uint64_t *d_out, 
 int tf_inverse_or_zero_xfe_dev(const uint64_t *d_in, size_t n, uint64_t *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Polynomial arithmetic on packed coefficients and codewords (math/polynomial.rs unless noted).  replaces
+ *   Add :2526-2563, Sub :2565-, Neg :2700-              tf_poly_add / _sub / _neg
+ *   scalar_mul / scalar_mul_mut :498-532, Mul<S> :2650-2686   tf_poly_scalar_mul
+ *   scale :760-773                                      tf_poly_scale           out[j] = a[j] * alpha^j
+ *   formal_derivative :275-285                          tf_poly_formal_derivative   out[j] = FF::from(j + 1) * a[j + 1]
+ *   degree :181                                         tf_poly_degree
+ *   Mul<BFieldElement> for XFieldElement, x_field_element.rs:540-548   tf_hadamard_xfe_bfe_dev   d_out[i] = d_a[i] * d_b[i]
+ *   "scalar_mul each, then Add them all"                tf_poly_linear_combination   out[i] = sum_{j<k} polys[j * stride + i] * weights[j]
+ * `width` is 1 for BFieldElement and 3 for XFieldElement, as in tf_tip5_hash_table_rows.  Lengths count coefficients.  Words are
+ * canonical raw Montgomery words in and out: every result is the unique representative of its field element, so it equals the
+ * reference's word for word however a power or a sum is formed.  The `batch` polynomials of a call are packed, n* coefficients each.
+ * Each entry point has a host form (host pointers, blocking) and a _dev form (device pointers, enqueued on `stream`); the _dev
+ * forms never synchronise, copy nothing back and use no work space.  There is no data-dependent error, so none takes a status word.
+ *   add, sub         out: batch x max(na, nb) coefficients; the shorter operand reads as zero above its length.  One width: the
+ *                    reference's Add is Polynomial<FF> + Polynomial<FF>.
+ *   neg, formal_derivative, degree   one width.  The derivative writes batch x (na - 1) coefficients; na <= 1 writes nothing.
+ *   scalar_mul, scale    `scalar` / `alpha` is a HOST array of width_s / width_alpha words in both forms (the _dev form passes it to
+ *                    the kernel by value); out has max(width_a, width_s) words per coefficient.  All four combinations 1.1, 3.3,
+ *                    3.1, 1.3 are valid: they are the reference's Mul impls, with x_field_element.rs:491-556 between the fields.
+ *   degree           degrees[row] = index of the highest non-zero coefficient, -1 for the zero polynomial and for na == 0; an
+ *                    XFieldElement is zero only if all three limbs are.  The _dev form writes int64_t words in device memory (set
+ *                    to -1 on the stream, then raised by the scan, which starts at the top and stops at the first non-zero block).
+ *   linear_combination   column j starts `stride` WORDS after column j - 1, stride >= n * width_p; the words between n * width_p
+ *                    and stride are never read.  This is the column-major layout tf_tip5_hash_table_rows and
+ *                    tf_merkle_from_columns take, so a table can be combined and committed without a copy.  `weights` holds
+ *                    k x width_w words and is a DEVICE pointer in the _dev form (tf_tip5_sponge_sample_scalars_dev leaves its
+ *                    output there).  out has max(width_p, width_w) words per element; the four width combinations are valid.
+ *                    k == 0 writes n zeros, the reference's empty Sum (b_field_element.rs:214, x_field_element.rs:294).
+ *   aliasing         out may be an input of the same element width and length in add, sub, neg, scalar_mul and scale.  It may not
+ *                    overlap an input in linear_combination or formal_derivative.
+ *   lengths          outputs have a fixed length and are zero padded at the top, as the division calls above document (the
+ *                    reference trims, and its equality ignores the padding).  tf_poly_degree gives the normalised length the
+ *                    division calls require.
+ *   empty calls      na == 0 (add / sub: na == nb == 0), n == 0 or batch == 0: TF_OK, nothing written, NULL pointers allowed --
+ *                    except that degree with na == 0 writes -1 per row.
+ *   errors           returned before any HIP call, in this order: TF_ERR_NULL_POINTER (a pointer the call would use);
+ *                    TF_ERR_INVALID_ARGUMENT (a width other than 1 or 3, stride < n * width_p); TF_ERR_LEN_TOO_LARGE (a length
+ *                    above 2^30, k > 65 535); then TF_ERR_NO_DEVICE on a machine without a GPU.
+ * Not provided because they are no kernel: shift_coefficients, mod_x_to_the_n and truncate are a pointer offset or a
+ * hipMemcpyAsync on packed coefficients.
+ * The weighted sum keeps the unreduced 128-bit products in a three-word accumulator per output word and reduces once
+ * (csrc/algebra_kernels.h). */
+int tf_poly_add(const uint64_t *a, size_t na, const uint64_t *b, size_t nb, int width, uint64_t *out, size_t batch);
+int tf_poly_add_dev(const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, int width, uint64_t *d_out, size_t batch, void *stream);
+int tf_poly_sub(const uint64_t *a, size_t na, const uint64_t *b, size_t nb, int width, uint64_t *out, size_t batch);
+int tf_poly_sub_dev(const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, int width, uint64_t *d_out, size_t batch, void *stream);
+int tf_poly_neg(const uint64_t *a, size_t na, int width, uint64_t *out, size_t batch);
+int tf_poly_neg_dev(const uint64_t *d_a, size_t na, int width, uint64_t *d_out, size_t batch, void *stream);
+int tf_poly_scalar_mul(const uint64_t *a, size_t na, int width_a, const uint64_t *scalar, int width_s, uint64_t *out, size_t batch);
+int tf_poly_scalar_mul_dev(const uint64_t *d_a, size_t na, int width_a, const uint64_t *scalar, int width_s, uint64_t *d_out, size_t batch,
+                           void *stream);
+int tf_poly_scale(const uint64_t *a, size_t na, int width_a, const uint64_t *alpha, int width_alpha, uint64_t *out, size_t batch);
+int tf_poly_scale_dev(const uint64_t *d_a, size_t na, int width_a, const uint64_t *alpha, int width_alpha, uint64_t *d_out, size_t batch,
+                      void *stream);
+int tf_poly_formal_derivative(const uint64_t *a, size_t na, int width, uint64_t *out, size_t batch);
+int tf_poly_formal_derivative_dev(const uint64_t *d_a, size_t na, int width, uint64_t *d_out, size_t batch, void *stream);
+int tf_poly_degree(const uint64_t *a, size_t na, int width, size_t batch, int64_t *degrees);
+int tf_poly_degree_dev(const uint64_t *d_a, size_t na, int width, size_t batch, int64_t *d_degrees, void *stream);
+int tf_hadamard_xfe_bfe_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count, void *stream);
+int tf_poly_linear_combination(const uint64_t *polys, size_t n, int width_p, size_t stride, size_t k, const uint64_t *weights, int width_w,
+                               uint64_t *out);
+int tf_poly_linear_combination_dev(const uint64_t *d_polys, size_t n, int width_p, size_t stride, size_t k, const uint64_t *d_weights,
+                                   int width_w, uint64_t *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the
  * first call); every other TF_* switch of DESIGN_HISTORY.md exists in the laboratory build alone (TF_AB_BUILD, below).
  *   TF_NTT_TILE_BYTES : bytes of batch processed between the passes of a multi-pass NTT (scratch size),

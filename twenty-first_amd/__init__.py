@@ -26,7 +26,7 @@ import numpy as np
 from . import _lib
 
 __all__ = [
-    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
+    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "linear_combination", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
     "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "set_device", "get_device", "shard_range",
 ]
 
@@ -317,6 +317,40 @@ def inverse_or_zero(x: np.ndarray, width: int = 1) -> np.ndarray:
     return out
 
 
+def _scalar(x, width: int, name: str) -> np.ndarray:
+    """One field element of `width` raw words, from an int (width 1) or a sequence."""
+    if width not in (1, 3):
+        raise ValueError(f"the width of {name} must be 1 (BFieldElement) or 3 (XFieldElement)")
+    s = np.ascontiguousarray(np.atleast_1d(np.asarray(x, dtype=np.uint64)).reshape(-1))
+    if s.size != width:
+        raise ValueError(f"{name} must hold {width} raw word(s)")
+    return s
+
+
+def linear_combination(columns: np.ndarray, weights: np.ndarray, n: int, width: int = 1, width_w: int = 1, stride=None) -> np.ndarray:
+    """out[i] = sum_j columns[j][i] * weights[j] for i < n: "scalar_mul each, then Add them all" (math/polynomial.rs:498-532,
+    :2526-2563) in one pass over the columns.  Column j starts `stride` words after column j - 1 (default n * width, packed), the
+    layout Tip5.hash_table_rows and MerkleTree.from_columns take; weights holds one element of width_w words per column.  The result
+    has n elements of max(width, width_w) words; no column gives n zeros (the reference's empty Sum)."""
+    c = _words(np.ascontiguousarray(columns, dtype=np.uint64).reshape(-1), "columns")
+    w = _words(np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1), "weights")
+    if width not in (1, 3) or width_w not in (1, 3):
+        raise ValueError("width and width_w must be 1 (BFieldElement) or 3 (XFieldElement)")
+    n = int(n)
+    stride = n * width if stride is None else int(stride)
+    if n < 0 or stride < n * width:
+        raise ValueError("stride must be at least n * width words")
+    if w.size % width_w:
+        raise ValueError("weights must hold whole elements of width_w words")
+    k = w.size // width_w
+    if k and c.size < (k - 1) * stride + n * width:
+        raise ValueError("columns must hold (k - 1) * stride + n * width words for the k weights")
+    out = np.empty(n * max(width, width_w), dtype=np.uint64)
+    if n:
+        _check(lib().tf_poly_linear_combination(_ptr(c), n, width, stride, k, _ptr(w), width_w, _ptr(out)), "linear_combination")
+    return out
+
+
 class Polynomial:
     """Coefficients low -> high degree (math/polynomial.rs:78-84); only the hot-path members."""
 
@@ -480,6 +514,57 @@ class Polynomial:
         if self.degree() < 0 or other.degree() < 0:
             return Polynomial(np.zeros(0, dtype=np.uint64), width=self.width)
         return Polynomial(fast_multiply(self.coefficients, other.coefficients, width=self.width), width=self.width)
+
+    def _len(self) -> int:
+        return self.coefficients.size // self.width
+
+    def _add_sub(self, other: "Polynomial", fn, where: str) -> "Polynomial":
+        if not isinstance(other, Polynomial):
+            return NotImplemented
+        if self.width != other.width:
+            raise TypeError("both polynomials must be over the same field (Polynomial<FF> + Polynomial<FF>)")
+        na, nb = self._len(), other._len()
+        out = np.empty(max(na, nb) * self.width, dtype=np.uint64)
+        if out.size:
+            _check(fn(_ptr(self.coefficients), na, _ptr(other.coefficients), nb, self.width, _ptr(out), 1), where)
+        return Polynomial(out, width=self.width)
+
+    def __add__(self, other: "Polynomial") -> "Polynomial":  # Add (:2526-2563)
+        return self._add_sub(other, lib().tf_poly_add, "add")
+
+    def __sub__(self, other: "Polynomial") -> "Polynomial":  # Sub (:2565-)
+        return self._add_sub(other, lib().tf_poly_sub, "sub")
+
+    def __neg__(self) -> "Polynomial":  # Neg (:2700-)
+        out = np.empty_like(self.coefficients)
+        if out.size:
+            _check(lib().tf_poly_neg(_ptr(self.coefficients), self._len(), self.width, _ptr(out), 1), "neg")
+        return Polynomial(out, width=self.width)
+
+    def _by_scalar(self, scalar, width_s: int, fn, where: str) -> "Polynomial":
+        s = _scalar(scalar, width_s, "the scalar")
+        wo = max(self.width, width_s)
+        out = np.empty(self._len() * wo, dtype=np.uint64)
+        if out.size:
+            _check(fn(_ptr(self.coefficients), self._len(), self.width, _ptr(s), width_s, _ptr(out), 1), where)
+        return Polynomial(out, width=wo)
+
+    def scalar_mul(self, scalar, width_s: int = 1) -> "Polynomial":
+        """math/polynomial.rs:498-532 (and Mul<S> :2650-2686): every coefficient times `scalar`, a raw word (width_s = 1) or three
+        (width_s = 3); the result is over the larger of the two fields."""
+        return self._by_scalar(scalar, width_s, lib().tf_poly_scalar_mul, "scalar_mul")
+
+    def scale(self, alpha, width_alpha: int = 1) -> "Polynomial":
+        """math/polynomial.rs:760-773: P(alpha * x), coefficient j times alpha^j."""
+        return self._by_scalar(alpha, width_alpha, lib().tf_poly_scale, "scale")
+
+    def formal_derivative(self) -> "Polynomial":
+        """math/polynomial.rs:275-285"""
+        n = self._len()
+        out = np.empty(max(n - 1, 0) * self.width, dtype=np.uint64)
+        if out.size:
+            _check(lib().tf_poly_formal_derivative(_ptr(self.coefficients), n, self.width, _ptr(out), 1), "formal_derivative")
+        return Polynomial(out, width=self.width)
 
 
 def barycentric_evaluate(codewords: np.ndarray, indeterminate, width: int = 1, batch: int = 1) -> np.ndarray:

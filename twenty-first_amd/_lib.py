@@ -113,6 +113,23 @@ SIGNATURES = {
     "tf_inverse_or_zero_xfe": (C.c_int, [_vp, _sz, _vp]),
     "tf_inverse_or_zero_bfe_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
     "tf_inverse_or_zero_xfe_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "tf_poly_add": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _sz]),
+    "tf_poly_add_dev": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _sz, _vp]),
+    "tf_poly_sub": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _sz]),
+    "tf_poly_sub_dev": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _sz, _vp]),
+    "tf_poly_neg": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz]),
+    "tf_poly_neg_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _vp]),
+    "tf_poly_scalar_mul": (C.c_int, [_vp, _sz, C.c_int, _vp, C.c_int, _vp, _sz]),
+    "tf_poly_scalar_mul_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, C.c_int, _vp, _sz, _vp]),
+    "tf_poly_scale": (C.c_int, [_vp, _sz, C.c_int, _vp, C.c_int, _vp, _sz]),
+    "tf_poly_scale_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, C.c_int, _vp, _sz, _vp]),
+    "tf_poly_formal_derivative": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz]),
+    "tf_poly_formal_derivative_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _vp]),
+    "tf_poly_degree": (C.c_int, [_vp, _sz, C.c_int, _sz, _vp]),
+    "tf_poly_degree_dev": (C.c_int, [_vp, _sz, C.c_int, _sz, _vp, _vp]),
+    "tf_hadamard_xfe_bfe_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "tf_poly_linear_combination": (C.c_int, [_vp, _sz, C.c_int, _sz, _sz, _vp, C.c_int, _vp]),
+    "tf_poly_linear_combination_dev": (C.c_int, [_vp, _sz, C.c_int, _sz, _sz, _vp, C.c_int, _vp, _vp]),
     "tf_zerofier_tree_new_bfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_xfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_bfe_dev": (C.c_int, [_vp, _sz, _vp, C.POINTER(C.c_void_p)]),

@@ -951,6 +951,63 @@ int tf_inverse_or_zero_bfe_dev(const uint64_t* d_in, size_t n, uint64_t* d_out, 
 int tf_inverse_or_zero_xfe_dev(const uint64_t* d_in, size_t n, uint64_t* d_out, void* stream) try {
     return batch_inverse_dev(d_in, n, d_out, 3, true, stream, nullptr);
 } TF_ABI_CATCH
+
+// Add / Sub / Neg, scalar_mul, scale, formal_derivative, degree, XFieldElement x BFieldElement products and weighted sums (tf_algebra.hip)
+int tf_poly_add(const uint64_t* a, size_t na, const uint64_t* b, size_t nb, int width, uint64_t* out, size_t batch) try {
+    return poly_addsub(a, na, b, nb, width, out, batch, false, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_add_dev(const uint64_t* a, size_t na, const uint64_t* b, size_t nb, int width, uint64_t* out, size_t batch, void* stream) try {
+    return poly_addsub(a, na, b, nb, width, out, batch, false, false, stream);
+} TF_ABI_CATCH
+int tf_poly_sub(const uint64_t* a, size_t na, const uint64_t* b, size_t nb, int width, uint64_t* out, size_t batch) try {
+    return poly_addsub(a, na, b, nb, width, out, batch, true, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_sub_dev(const uint64_t* a, size_t na, const uint64_t* b, size_t nb, int width, uint64_t* out, size_t batch, void* stream) try {
+    return poly_addsub(a, na, b, nb, width, out, batch, true, false, stream);
+} TF_ABI_CATCH
+int tf_poly_neg(const uint64_t* a, size_t na, int width, uint64_t* out, size_t batch) try {
+    return poly_neg(a, na, width, out, batch, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_neg_dev(const uint64_t* a, size_t na, int width, uint64_t* out, size_t batch, void* stream) try {
+    return poly_neg(a, na, width, out, batch, false, stream);
+} TF_ABI_CATCH
+int tf_poly_scalar_mul(const uint64_t* a, size_t na, int width_a, const uint64_t* scalar, int width_s, uint64_t* out, size_t batch) try {
+    return poly_scalar_mul(a, na, width_a, scalar, width_s, out, batch, false, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_scalar_mul_dev(const uint64_t* a, size_t na, int width_a, const uint64_t* scalar, int width_s, uint64_t* out, size_t batch,
+                           void* stream) try {
+    return poly_scalar_mul(a, na, width_a, scalar, width_s, out, batch, false, false, stream);
+} TF_ABI_CATCH
+int tf_poly_scale(const uint64_t* a, size_t na, int width_a, const uint64_t* alpha, int width_alpha, uint64_t* out, size_t batch) try {
+    return poly_scalar_mul(a, na, width_a, alpha, width_alpha, out, batch, true, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_scale_dev(const uint64_t* a, size_t na, int width_a, const uint64_t* alpha, int width_alpha, uint64_t* out, size_t batch,
+                      void* stream) try {
+    return poly_scalar_mul(a, na, width_a, alpha, width_alpha, out, batch, true, false, stream);
+} TF_ABI_CATCH
+int tf_poly_formal_derivative(const uint64_t* a, size_t na, int width, uint64_t* out, size_t batch) try {
+    return poly_derivative(a, na, width, out, batch, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_formal_derivative_dev(const uint64_t* a, size_t na, int width, uint64_t* out, size_t batch, void* stream) try {
+    return poly_derivative(a, na, width, out, batch, false, stream);
+} TF_ABI_CATCH
+int tf_poly_degree(const uint64_t* a, size_t na, int width, size_t batch, int64_t* degrees) try {
+    return poly_degree(a, na, width, batch, reinterpret_cast<long long*>(degrees), true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_degree_dev(const uint64_t* a, size_t na, int width, size_t batch, int64_t* degrees, void* stream) try {
+    return poly_degree(a, na, width, batch, reinterpret_cast<long long*>(degrees), false, stream);
+} TF_ABI_CATCH
+int tf_hadamard_xfe_bfe_dev(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, void* stream) try {
+    return hadamard_xfe_bfe_dev(a, b, out, count, stream);
+} TF_ABI_CATCH
+int tf_poly_linear_combination(const uint64_t* polys, size_t n, int width_p, size_t stride, size_t k, const uint64_t* weights, int width_w,
+                               uint64_t* out) try {
+    return poly_lincomb(polys, n, width_p, stride, k, weights, width_w, out, true, nullptr);
+} TF_ABI_CATCH
+int tf_poly_linear_combination_dev(const uint64_t* polys, size_t n, int width_p, size_t stride, size_t k, const uint64_t* weights, int width_w,
+                                   uint64_t* out, void* stream) try {
+    return poly_lincomb(polys, n, width_p, stride, k, weights, width_w, out, false, stream);
+} TF_ABI_CATCH
 static int coset_extrapolate_host(uint64_t offset, const uint64_t* cw, size_t n, size_t batch, const uint64_t* pts, size_t np,
                                   uint64_t* out, int L) {
     if (n == 0) return TF_ERR_LEN_NOT_POWER_OF_TWO;

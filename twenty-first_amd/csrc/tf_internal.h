@@ -10,6 +10,7 @@
 //   tf_mmr.hip    batched Merkle Mountain Range accumulators and membership proofs (mmr_kernels.h), with their host flavours
 //   tf_divide.hip division with remainder and the power-series inverse (divide_kernels.h), with their entry points
 //   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
+//   tf_algebra.hip add / sub / neg, scalar_mul, scale, formal_derivative, degree and weighted sums of columns (algebra_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 #pragma once
 #include <hip/hip_runtime.h>
@@ -280,6 +281,17 @@ int fps_host(const u64* f, size_t nf, size_t precision, u64* out, int L);
 // contract); _dev: device pointers, d_status as the _dev_async entry points (null: a blocking check of a flag word), _host: host pointers
 int batch_inverse_dev(const u64* in, size_t n, u64* out, int L, bool or_zero, void* stream, int* d_status);
 int batch_inverse_host(const u64* in, size_t n, u64* out, int L, bool or_zero);
+
+// ------------------------------------------------------------------------------------ tf_algebra.hip
+// the plain polynomial arithmetic of include/tf_hip.h ("Polynomial arithmetic"): host = false takes device pointers and only
+// enqueues on `stream`, host = true takes host pointers and blocks.  Lengths count coefficients of `width` words.
+int poly_addsub(const u64* a, size_t na, const u64* b, size_t nb, int width, u64* out, size_t batch, bool sub, bool host, void* stream);
+int poly_neg(const u64* a, size_t na, int width, u64* out, size_t batch, bool host, void* stream);
+int poly_scalar_mul(const u64* a, size_t na, int width_a, const u64* scalar, int width_s, u64* out, size_t batch, bool scale, bool host, void* stream);
+int poly_derivative(const u64* a, size_t na, int width, u64* out, size_t batch, bool host, void* stream);
+int poly_degree(const u64* a, size_t na, int width, size_t batch, long long* degrees, bool host, void* stream);
+int hadamard_xfe_bfe_dev(const u64* a, const u64* b, u64* out, size_t count, void* stream);
+int poly_lincomb(const u64* polys, size_t n, int width_p, size_t stride, size_t k, const u64* weights, int width_w, u64* out, bool host, void* stream);
 
 // ------------------------------------------------------------------------------------ tf_poly.hip
 extern std::atomic<int> g_batch_eval_route;

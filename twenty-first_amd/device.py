@@ -205,13 +205,130 @@ def coset_interpolate(values, n: int, offset_raw: int, out, batch: int = 1, widt
     _chk(fn(_p(values), n, C.c_uint64(offset_raw), _p(out), batch, _stream(stream)), "fast_coset_interpolate")
 
 
-def hadamard(a, b, out, width: int = 1, stream=None) -> None:
-    """Pointwise field product (math/polynomial.rs:920-925); out may alias a or b."""
+def hadamard(a, b, out, width: int = 1, stream=None, width_b=None) -> None:
+    """Pointwise field product (math/polynomial.rs:920-925); out may alias a or b.  width = 3 with width_b = 1 is Mul<BFieldElement>
+    for XFieldElement (x_field_element.rs:540-548): b holds one word per element of a, and out may alias a."""
     a, b, out = _t(a, "a"), _t(b, "b"), _t(out, "out")
     _width(width)
+    if width_b is not None and width_b != width:
+        _need(width == 3 and width_b == 1, "the mixed product is XFieldElement (width 3) times BFieldElement (width_b 1)")
+        _need(a.numel() % 3 == 0 and b.numel() * 3 == a.numel() and out.numel() == a.numel(), "a and out must hold three words per word of b")
+        _chk(_lib.lib().tf_hadamard_xfe_bfe_dev(_p(a), _p(b), _p(out), b.numel(), _stream(stream)), "hadamard")
+        return
     _need(a.numel() % width == 0 and b.numel() == a.numel() and out.numel() == a.numel(), "a, b and out must hold the same number of elements")
     fn = _lib.lib().tf_hadamard_bfe_dev if width == 1 else _lib.lib().tf_hadamard_xfe_dev
     _chk(fn(_p(a), _p(b), _p(out), a.numel() // width, _stream(stream)), "hadamard")
+
+
+def _apart_or_same(x, out, what: str) -> None:
+    xb, ob = x.numel() * 8, out.numel() * 8
+    _need((out.data_ptr() == x.data_ptr() and ob == xb) or out.data_ptr() >= x.data_ptr() + xb or x.data_ptr() >= out.data_ptr() + ob, what)
+
+
+def _apart(x, out, what: str) -> None:
+    _need(out.data_ptr() >= x.data_ptr() + x.numel() * 8 or x.data_ptr() >= out.data_ptr() + out.numel() * 8, what)
+
+
+def _poly_add_sub(fn, where, a, na: int, b, nb: int, out, batch: int, width: int, stream) -> None:
+    a, b, out = _t(a, "a"), _t(b, "b"), _t(out, "out")
+    _width(width)
+    _need(na >= 0 and nb >= 0 and batch >= 0, "lengths and batch must not be negative")
+    _need(a.numel() == na * batch * width and b.numel() == nb * batch * width, "operand sizes do not match na/nb/batch/width")
+    _need(out.numel() == max(na, nb) * batch * width, "out must hold batch * max(na, nb) coefficients")
+    _apart_or_same(a, out, "out must be an operand of its own length or not overlap it")
+    _apart_or_same(b, out, "out must be an operand of its own length or not overlap it")
+    _chk(fn(_p(a), na, _p(b), nb, width, _p(out), batch, _stream(stream)), where)
+
+
+def poly_add(a, na: int, b, nb: int, out, batch: int = 1, width: int = 1, stream=None) -> None:
+    """Polynomial + Polynomial (math/polynomial.rs:2526-2563) on device buffers: out = batch x max(na, nb) coefficients; out may be
+    the operand of that length."""
+    _poly_add_sub(_lib.lib().tf_poly_add_dev, "add", a, na, b, nb, out, batch, width, stream)
+
+
+def poly_sub(a, na: int, b, nb: int, out, batch: int = 1, width: int = 1, stream=None) -> None:
+    """Polynomial - Polynomial (math/polynomial.rs:2565-) on device buffers, as poly_add."""
+    _poly_add_sub(_lib.lib().tf_poly_sub_dev, "sub", a, na, b, nb, out, batch, width, stream)
+
+
+def poly_neg_(a, na: int, out=None, batch: int = 1, width: int = 1, stream=None) -> None:
+    """Neg (math/polynomial.rs:2700-) on device buffers; in place when out is None."""
+    a = _t(a, "a")
+    out = a if out is None else _t(out, "out")
+    _width(width)
+    _need(na >= 0 and a.numel() == na * batch * width and out.numel() == a.numel(), "buffer sizes do not match na/batch/width")
+    _apart_or_same(a, out, "out must be a itself or not overlap it")
+    _chk(_lib.lib().tf_poly_neg_dev(_p(a), na, width, _p(out), batch, _stream(stream)), "neg")
+
+
+def _scalar_words(x, width: int, name: str):
+    import numpy as np
+
+    _width(width)
+    s = np.ascontiguousarray(np.atleast_1d(np.asarray(x, dtype=np.uint64)).reshape(-1))
+    _need(s.size == width, f"{name} must hold {width} raw word(s)")
+    return s
+
+
+def _poly_by_scalar(fn, where, a, na: int, scalar, out, batch: int, width: int, width_s: int, stream) -> None:
+    a, out = _t(a, "a"), _t(out, "out")
+    _width(width)
+    s = _scalar_words(scalar, width_s, "the scalar")
+    wo = max(width, width_s)
+    _need(na >= 0 and a.numel() == na * batch * width and out.numel() == na * batch * wo, "buffer sizes do not match na/batch/widths")
+    _apart_or_same(a, out, "out must be a itself (same element width) or not overlap it")
+    _chk(fn(_p(a), na, width, C.c_void_p(s.ctypes.data), width_s, _p(out), batch, _stream(stream)), where)
+
+
+def poly_scalar_mul(a, na: int, scalar, out, batch: int = 1, width: int = 1, width_s: int = 1, stream=None) -> None:
+    """scalar_mul (math/polynomial.rs:498-532, Mul<S> :2650-2686) on device buffers: every coefficient times the HOST scalar (an int
+    or width_s raw words); out holds max(width, width_s) words per coefficient and may be a when the widths agree."""
+    _poly_by_scalar(_lib.lib().tf_poly_scalar_mul_dev, "scalar_mul", a, na, scalar, out, batch, width, width_s, stream)
+
+
+def poly_scale(a, na: int, alpha, out, batch: int = 1, width: int = 1, width_alpha: int = 1, stream=None) -> None:
+    """scale (math/polynomial.rs:760-773) on device buffers: out[j] = a[j] * alpha^j, alpha a HOST scalar; sizes as poly_scalar_mul."""
+    _poly_by_scalar(_lib.lib().tf_poly_scale_dev, "scale", a, na, alpha, out, batch, width, width_alpha, stream)
+
+
+def poly_formal_derivative(a, na: int, out, batch: int = 1, width: int = 1, stream=None) -> None:
+    """formal_derivative (math/polynomial.rs:275-285) on device buffers: out = batch x (na - 1) coefficients, not overlapping a."""
+    a, out = _t(a, "a"), _t(out, "out")
+    _width(width)
+    _need(na >= 0 and a.numel() == na * batch * width and out.numel() == max(na - 1, 0) * batch * width, "buffer sizes do not match na/batch/width")
+    _apart(a, out, "out must not overlap a")
+    _chk(_lib.lib().tf_poly_formal_derivative_dev(_p(a), na, width, _p(out), batch, _stream(stream)), "formal_derivative")
+
+
+def poly_degree(a, na: int, degrees, batch: int = 1, width: int = 1, stream=None) -> None:
+    """degree (math/polynomial.rs:181) of `batch` packed polynomials into an int64 tensor of `batch` entries (-1: the zero
+    polynomial).  Only enqueues."""
+    import torch
+
+    a = _t(a, "a")
+    _width(width)
+    _need(isinstance(degrees, torch.Tensor) and degrees.is_cuda and degrees.is_contiguous() and degrees.dtype == torch.int64
+          and degrees.numel() == batch, "degrees must be a contiguous CUDA int64 tensor of `batch` entries")
+    _need(na >= 0 and a.numel() == na * batch * width, "a does not match na/batch/width")
+    _chk(_lib.lib().tf_poly_degree_dev(_p(a), na, width, batch, _p(degrees), _stream(stream)), "degree")
+
+
+def linear_combination(columns, n: int, k: int, weights, out, width: int = 1, width_w: int = 1, stride=None, stream=None) -> None:
+    """out[i] = sum_{j<k} columns[j * stride + i] * weights[j], i < n, on device buffers (weights too: k x width_w words, where
+    tip5_sponge_sample_scalars leaves them).  stride counts words (default n * width); out = n x max(width, width_w) words and
+    overlaps no input."""
+    columns, weights, out = _t(columns, "columns"), _t(weights, "weights"), _t(out, "out")
+    _width(width)
+    _width(width_w)
+    stride = n * width if stride is None else int(stride)
+    _need(n >= 0 and k >= 0 and stride >= n * width, "stride must be at least n * width words")
+    _need(weights.numel() == k * width_w, "weights must hold k elements of width_w words")
+    _need(k == 0 or columns.numel() >= (k - 1) * stride + n * width, "columns must hold (k - 1) * stride + n * width words")
+    _need(out.numel() == n * max(width, width_w), "out must hold n elements of max(width, width_w) words")
+    _apart(columns, out, "out must not overlap the columns")
+    _apart(weights, out, "out must not overlap the weights")
+    _chk(_lib.lib().tf_poly_linear_combination_dev(_p(columns), n, width, stride, k, _p(weights), width_w, _p(out), _stream(stream)),
+         "linear_combination")
 
 
 def poly_mul(a, na: int, b, nb: int, out, batch: int = 1, width: int = 1, stream=None) -> None:

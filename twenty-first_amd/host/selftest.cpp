@@ -257,6 +257,31 @@ int main() {
         // batch_evaluate: 1 + 2x + 3x^2 at 0, 1, 2, 10
         EXPECT(a.batch_evaluate(bfe_vec({0, 1, 2, 10})) == bfe_vec({1, 6, 17, 321}));
     }
+    {  // formal_derivative doc example (polynomial.rs:265-273): 1 + 2x + 3x^2 + 4x^3 -> 2 + 6x + 12x^2; scalar_mul doc example
+       // (:518-520): [1, 2, 3] * 2 = [2, 4, 6]; Add / Sub / Neg, scale and the weighted sum against values worked out by hand
+        using Poly = Polynomial<BFieldElement>;
+        const int failures_before = failures;
+        Poly f(bfe_vec({1, 2, 3, 4}));
+        EXPECT(f.formal_derivative().coefficients == bfe_vec({2, 6, 12}));
+        EXPECT(Poly(bfe_vec({7})).formal_derivative().degree() == -1);
+        Poly g(bfe_vec({1, 2, 3}));
+        EXPECT(g.scalar_mul(BFieldElement::new_(2)).coefficients == bfe_vec({2, 4, 6}));
+        EXPECT((f + g).coefficients == bfe_vec({2, 4, 6, 4}));
+        EXPECT((f - g).coefficients == bfe_vec({0, 0, 0, 4}));
+        EXPECT((g - g).degree() == -1);  // the result is normalised, as every Polynomial::new
+        EXPECT((g + (-g)).degree() == -1);
+        EXPECT(g.scale(BFieldElement::new_(3)).coefficients == bfe_vec({1, 6, 27}));  // g(3x)
+        XFieldElement x{};  // the indeterminate of the extension, (0, 1, 0)
+        x.coefficients[1] = BFieldElement::new_(1);
+        auto gx = g.scalar_mul(x);  // a BFieldElement polynomial times an XFieldElement: coefficients (0, c, 0)
+        EXPECT(gx.coefficients.size() == 3 && gx.coefficients[2].coefficients[1] == BFieldElement::new_(3) &&
+               gx.coefficients[2].coefficients[0] == BFieldElement::new_(0));
+        // 2 * [1, 2, 3] + 10 * [4, 5, 6] = [42, 54, 66]
+        EXPECT(linear_combination(bfe_vec({1, 2, 3, 4, 5, 6}), 3, bfe_vec({2, 10})) == bfe_vec({42, 54, 66}));
+        EXPECT(linear_combination(std::vector<BFieldElement>{}, 3, std::vector<BFieldElement>{}) == bfe_vec({0, 0, 0}));
+        if (failures == failures_before)
+            printf("polynomial arithmetic: formal_derivative and scalar_mul doc examples, add / sub / neg, scale, linear_combination: PASS\n");
+    }
     {  // zerofier doc example (polynomial.rs:1426-1434): roots 2, 4, 6 -> degree 3, zero exactly there; interpolate doc example
        // (:1490-1497): through (0,1) (1,3) (2,5) (3,7) -> 1 + 2x (degree 1, value 9 at 4)
         using Poly = Polynomial<BFieldElement>;

@@ -14,11 +14,13 @@
 // Everything executes on the GPU through the C ABI; there is no CPU fallback in this header.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <utility>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tf_hip.h"
@@ -156,6 +158,10 @@ inline std::vector<XFieldElement> inverse_or_zero(std::vector<XFieldElement> inp
     return input;
 }
 
+// the field a product of an A and a B lives in (x_field_element.rs:491-556): the extension field if either is
+template <class A, class B>
+using ProductField = std::conditional_t<(sizeof(A) >= sizeof(B)), A, B>;
+
 // ---- Polynomial (math/polynomial.rs:78-84): only the hot-path members ------------------------------
 template <class FF>
 struct Polynomial {
@@ -215,6 +221,50 @@ struct Polynomial {
             check(tf_poly_mul_bfe(a, coefficients.size(), b, other.coefficients.size(), o, 1), "fast_multiply");
         else
             check(tf_poly_mul_xfe(a, coefficients.size(), b, other.coefficients.size(), o, 1), "fast_multiply");
+        return Polynomial(std::move(out));
+    }
+    // Add (polynomial.rs:2526-2563), Sub (:2565-), Neg (:2700-): Polynomial<FF> with Polynomial<FF>
+  private:
+    Polynomial add_sub(const Polynomial& other, bool sub) const {
+        const size_t na = coefficients.size(), nb = other.coefficients.size();
+        std::vector<FF> out(std::max(na, nb));
+        const uint64_t* a = reinterpret_cast<const uint64_t*>(coefficients.data());
+        const uint64_t* b = reinterpret_cast<const uint64_t*>(other.coefficients.data());
+        uint64_t* o = reinterpret_cast<uint64_t*>(out.data());
+        check(sub ? tf_poly_sub(a, na, b, nb, sizeof(FF) / 8, o, 1) : tf_poly_add(a, na, b, nb, sizeof(FF) / 8, o, 1), sub ? "sub" : "add");
+        return Polynomial(std::move(out));
+    }
+    template <class S>
+    Polynomial<ProductField<FF, S>> by_scalar(S scalar, bool scale) const {
+        std::vector<ProductField<FF, S>> out(coefficients.size());
+        const uint64_t* a = reinterpret_cast<const uint64_t*>(coefficients.data());
+        const uint64_t* sc = reinterpret_cast<const uint64_t*>(&scalar);
+        uint64_t* o = reinterpret_cast<uint64_t*>(out.data());
+        if (scale) check(tf_poly_scale(a, coefficients.size(), sizeof(FF) / 8, sc, sizeof(S) / 8, o, 1), "scale");
+        else check(tf_poly_scalar_mul(a, coefficients.size(), sizeof(FF) / 8, sc, sizeof(S) / 8, o, 1), "scalar_mul");
+        return Polynomial<ProductField<FF, S>>(std::move(out));
+    }
+
+  public:
+    Polynomial operator+(const Polynomial& other) const { return add_sub(other, false); }
+    Polynomial operator-(const Polynomial& other) const { return add_sub(other, true); }
+    Polynomial operator-() const {
+        std::vector<FF> out(coefficients.size());
+        check(tf_poly_neg(reinterpret_cast<const uint64_t*>(coefficients.data()), coefficients.size(), sizeof(FF) / 8,
+                          reinterpret_cast<uint64_t*>(out.data()), 1), "neg");
+        return Polynomial(std::move(out));
+    }
+    // scalar_mul (polynomial.rs:498-532, Mul<S> :2650-2686): every coefficient times a BFieldElement or an XFieldElement
+    template <class S>
+    Polynomial<ProductField<FF, S>> scalar_mul(S scalar) const { return by_scalar(scalar, false); }
+    // scale (polynomial.rs:760-773): P(alpha x), coefficient j times alpha^j
+    template <class S>
+    Polynomial<ProductField<FF, S>> scale(S alpha) const { return by_scalar(alpha, true); }
+    // formal_derivative (polynomial.rs:275-285)
+    Polynomial formal_derivative() const {
+        std::vector<FF> out(coefficients.empty() ? 0 : coefficients.size() - 1);
+        check(tf_poly_formal_derivative(reinterpret_cast<const uint64_t*>(coefficients.data()), coefficients.size(), sizeof(FF) / 8,
+                                        reinterpret_cast<uint64_t*>(out.data()), 1), "formal_derivative");
         return Polynomial(std::move(out));
     }
     // batch_evaluate (polynomial.rs:1840-1852): f at every point of `domain`
@@ -323,6 +373,18 @@ struct Polynomial {
 };
 
 // ---- barycentric_evaluate (math/polynomial.rs:2609-2637): every codeword of a batch at one indeterminate ------------------
+// sum_j weights[j] * column j, "scalar_mul each, then Add them all" in one pass: `columns` holds weights.size() packed columns of n
+// elements (the column-major table MerkleTree::from_columns takes); no column gives n zeros (the reference's empty Sum)
+template <class FF, class S>
+inline std::vector<ProductField<FF, S>> linear_combination(const std::vector<FF>& columns, size_t n, const std::vector<S>& weights) {
+    if (columns.size() != n * weights.size()) throw std::invalid_argument("linear_combination: columns must hold weights.size() columns of n elements");
+    std::vector<ProductField<FF, S>> out(n);
+    check(tf_poly_linear_combination(reinterpret_cast<const uint64_t*>(columns.data()), n, sizeof(FF) / 8, n * (sizeof(FF) / 8), weights.size(),
+                                     reinterpret_cast<const uint64_t*>(weights.data()), sizeof(S) / 8, reinterpret_cast<uint64_t*>(out.data())),
+          "linear_combination");
+    return out;
+}
+
 template <class Coeff>
 inline std::vector<XFieldElement> barycentric_evaluate(const std::vector<Coeff>& codewords, size_t codeword_length, XFieldElement indeterminate) {
     const size_t batch = codeword_length ? codewords.size() / codeword_length : 0;
