@@ -824,6 +824,42 @@ int tf_debug_fill_random_dev(uint64_t *d_out, size_t count, uint64_t seed, uint6
  * power-of-two products (and their sign) of the NTT networks -- hand-scheduled blocks of four and of two per thread.
  * TF_ERR_INVALID_ARGUMENT for an exponent outside [0, 192). */
 int tf_debug_mul_pow2_dev(uint64_t *d_x, size_t count, int e, void *stream);
+/* Test helper: ONE hand-scheduled field primitive of the kernels (csrc/gl64.h, csrc/tip5_kernels.h) over `count` operand pairs
+ * (d_a[i], d_b[i]), called exactly as the kernels call it -- the same function, whatever form the build's switches select.  A thread
+ * runs one block of the primitive on W consecutive elements, so element index mod W is the position in the block (which carry chain:
+ * vcc or an SGPR pair).  Loads and stores are guarded by count (missing operands are 0); nothing behind count is written.
+ *   op                               primitive                        W   operands                                 outputs
+ *   ADD, SUB                         gl::add, gl::sub                 1   a, b canonical                           out0
+ *   MONT_MUL                         gl::mont_mul                     1   any two words                            out0
+ *   ADD_SUB                          gl::add_sub                      1   canonical                                out0 = a + b, out1 = a - b
+ *   ADD_SUB2                         gl::add_sub2                     2   canonical                                out0, out1
+ *   ADD_SUB_LAZY2                    gl::add_sub_lazy2                2   a any word, b <= p                       out0, out1
+ *   ADD_LAZY4, SUB_LAZY4             gl::add_lazy4, gl::sub_lazy4     4   a any word, b <= p                       out0
+ *   MONT_MUL2 / 3 / 4                gl::mont_mul2 / 3 / 4            2 / 3 / 4   any two words                    out0
+ *   CANONICAL                        gl::canonical_asm                1   a any word (d_b is not read)             out0
+ *   MX_FOLD4_CANON, MX_FOLD4_LAZY    tfk::mx_fold4_tail<true / false> 4   a = (th : tl) < 2^63 + 2^59, h0 = low    out0
+ *   MX_FOLD2                         tfk::mx_fold2_tail               2   half of b                                out0
+ * d_out1 is written by the ops with two outputs only and may be null otherwise.  TF_ERR_INVALID_ARGUMENT for an unknown op or a count
+ * above 2^32, checked before anything else; a count of 0 is TF_OK. */
+enum {
+    TF_FIELD_OP_ADD = 0,
+    TF_FIELD_OP_SUB = 1,
+    TF_FIELD_OP_MONT_MUL = 2,
+    TF_FIELD_OP_ADD_SUB = 3,
+    TF_FIELD_OP_ADD_SUB2 = 4,
+    TF_FIELD_OP_ADD_SUB_LAZY2 = 5,
+    TF_FIELD_OP_ADD_LAZY4 = 6,
+    TF_FIELD_OP_SUB_LAZY4 = 7,
+    TF_FIELD_OP_MONT_MUL2 = 8,
+    TF_FIELD_OP_MONT_MUL3 = 9,
+    TF_FIELD_OP_MONT_MUL4 = 10,
+    TF_FIELD_OP_CANONICAL = 11,
+    TF_FIELD_OP_MX_FOLD4_CANON = 12,
+    TF_FIELD_OP_MX_FOLD4_LAZY = 13,
+    TF_FIELD_OP_MX_FOLD2 = 14,
+    TF_FIELD_OP_COUNT = 15
+};
+int tf_debug_field_op_dev(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out0, uint64_t *d_out1, size_t count, void *stream);
 
 #ifdef __cplusplus
 }

@@ -143,7 +143,8 @@ def test_ntt_ragged_batches(tf, oracle, n, batch):
 
 
 def test_ntt_edge_values(tf, oracle):
-    """all-zero, all-(p-1), single spike: extreme operands of the shift/reduce paths"""
+    """all-zero, all-(p-1), single spike, and a shuffled draw from every canonical edge word (BFieldElement and XFieldElement, both
+    directions): extreme operands of the shift/reduce paths"""
     for n in [64, 1024, 4096, 1 << 16]:
         for fill in ("zero", "max", "spike", "alt"):
             if fill == "zero":
@@ -163,6 +164,20 @@ def test_ntt_edge_values(tf, oracle):
             got = x.copy()
             tf.intt(got)
             assert np.array_equal(got, want_i), (n, fill)
+    # every canonical edge word of the carry paths (tests/field_ref.py) in one slice, drawn with a fixed seed: unlike the four
+    # patterns above the words differ from butterfly to butterfly, so the first levels meet edge x edge operands in every combination
+    from tests.field_ref import edge_words
+
+    edges = np.array([w for w in edge_words() if w < P], dtype=np.uint64)
+    rng = np.random.default_rng(0x65646765)
+    for n in [64, 4096, 1 << 16]:
+        for width in (1, 3):
+            x = edges[rng.integers(0, len(edges), size=n * width)]
+            for inverse in (False, True):
+                want = oracle.ntt(x, width=width, inverse=inverse)
+                got = x.copy()
+                tf.ntt(got, width=width, _inverse=inverse)
+                assert np.array_equal(got, want), (n, "edge words", width, inverse)
 
 
 def test_ntt_panics(tf):

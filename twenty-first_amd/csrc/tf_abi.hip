@@ -300,6 +300,19 @@ int tf_debug_mul_pow2_dev(uint64_t* d_x, size_t count, int e, void* stream) try 
     return TF_OK;
 } TF_ABI_CATCH
 
+// test helper (not part of the drop-in boundary): one hand-scheduled field primitive over count operand pairs
+int tf_debug_field_op_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out0, uint64_t* d_out1, size_t count, void* stream) try {
+    if (op < 0 || op >= TF_FIELD_OP_COUNT || count > (size_t(1) << 32)) return TF_ERR_INVALID_ARGUMENT;
+    if (count == 0) return TF_OK;
+    if (!d_a || !d_out0 || (!d_b && op != TF_FIELD_OP_CANONICAL) || (!d_out1 && field_op_two_outputs(op))) return TF_ERR_NULL_POINTER;
+    DeviceCtx* ctx = nullptr;
+    int rc = current_ctx(&ctx);
+    if (rc) return rc;
+    debug_field_op_dev(op, d_a, d_b, d_out0, d_out1, count, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+} TF_ABI_CATCH
+
 #ifdef TF_AB_BUILD
 // measurement helper (not part of the drop-in boundary): allocate / fetch the MODE-3 stamp buffer
 int tf_debug_stamps(unsigned long long* host_out, size_t words) try {

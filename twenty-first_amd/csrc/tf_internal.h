@@ -170,6 +170,19 @@ int launch_hash_pairs(const u64* in, u64* out, u64* leaf_copy, long long count, 
 int merkle_narrow_levels(const u64* level, long long in_ts, long long w, u64* d_nodes, long long nodes_ts, u64* d_root, u64* scratch, size_t batch,
                          bool copy_input, hipStream_t s);
 bool merkle_narrow_from(long long w, size_t batch);  // narrow_from: the level of w nodes per tree and all above it go to merkle_narrow_levels
+// tf_debug_field_op_dev: one kernel per op, all instantiated in tf_tip5.hip -- the unit that sees the fold tails of tip5_kernels.h next
+// to gl64.h, and a code object of its own: the ABI unit's (which every caller loads with its first fill_random) stays as it was.
+// A thread runs one block of the primitive on W = field_op_width(op) consecutive elements.
+constexpr int field_op_width(int op) {
+    return op == TF_FIELD_OP_ADD_SUB2 || op == TF_FIELD_OP_ADD_SUB_LAZY2 || op == TF_FIELD_OP_MONT_MUL2 || op == TF_FIELD_OP_MX_FOLD2 ? 2
+           : op == TF_FIELD_OP_MONT_MUL3                                                                                             ? 3
+           : op == TF_FIELD_OP_ADD_LAZY4 || op == TF_FIELD_OP_SUB_LAZY4 || op == TF_FIELD_OP_MONT_MUL4 || op == TF_FIELD_OP_MX_FOLD4_CANON ||
+                   op == TF_FIELD_OP_MX_FOLD4_LAZY
+               ? 4
+               : 1;
+}
+constexpr bool field_op_two_outputs(int op) { return op == TF_FIELD_OP_ADD_SUB || op == TF_FIELD_OP_ADD_SUB2 || op == TF_FIELD_OP_ADD_SUB_LAZY2; }
+void debug_field_op_dev(int op, const u64* d_a, const u64* d_b, u64* d_out0, u64* d_out1, size_t count, hipStream_t s);
 extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (canonical values; tf_tip5.hip)
 // the planner's rules for a launch of `count` permutation chains (tf_tip5.hip has the measurements behind them)
 constexpr long long kCoopMaxCount = 1ll << 13;

@@ -2,6 +2,8 @@
 #include "tf_internal.h"
 #include "tip5_kernels.h"
 
+#include <utility>
+
 namespace tfi {
 
 // ------------------------------------------------------------------------------------ Tip5 constants
@@ -63,6 +65,66 @@ inline int shift_of(long long per_tree) { return (per_tree > 0 && !(per_tree & (
 
 void launch_permute_mx(u64* d_states, u64* d_trace, long long count, hipStream_t s) {
     hipLaunchKernelGGL(tfk::tip5_permute_mx_kernel<1>, dim3(mx_blocks(count)), dim3(256), 0, s, d_states, d_trace, count);
+}
+
+// tf_debug_field_op_dev: ONE primitive of gl64.h or one fold tail of tip5_kernels.h over count operand pairs, called as the kernels call
+// it (so TF_MONT4 / TF_MONT_CC / TF_TIP5_I8 pick the form here as they do there).  A thread runs one block of the primitive on W
+// consecutive elements: element index mod W is the position in the block, i.e. which carry chain (vcc or an SGPR pair) the pair rides.
+// Loads and stores are guarded by count, missing operands are 0, out1 is written by the two-output ops only.  The fold tails take
+// t = a[i] = (th : tl) and h0 = the low half of b[i].
+template <int OP>
+__global__ void __launch_bounds__(256) field_op_kernel(const u64* a, const u64* b, u64* out0, u64* out1, unsigned long long count) {
+    constexpr int W = field_op_width(OP);
+    const unsigned long long base = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * W;
+    u64 x[W], y[W], r[W], q[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        x[i] = base + i < count ? a[base + i] : 0;
+        if constexpr (OP == TF_FIELD_OP_CANONICAL) y[i] = 0;
+        else y[i] = base + i < count ? b[base + i] : 0;
+        q[i] = 0;
+    }
+    if constexpr (OP == TF_FIELD_OP_ADD) r[0] = gl::add(x[0], y[0]);
+    else if constexpr (OP == TF_FIELD_OP_SUB) r[0] = gl::sub(x[0], y[0]);
+    else if constexpr (OP == TF_FIELD_OP_MONT_MUL) r[0] = gl::mont_mul(x[0], y[0]);
+    else if constexpr (OP == TF_FIELD_OP_ADD_SUB) gl::add_sub(x[0], y[0], r[0], q[0]);
+    else if constexpr (OP == TF_FIELD_OP_ADD_SUB2) gl::add_sub2(x[0], y[0], x[1], y[1], r[0], q[0], r[1], q[1]);
+    else if constexpr (OP == TF_FIELD_OP_ADD_SUB_LAZY2) gl::add_sub_lazy2(x[0], y[0], x[1], y[1], r[0], q[0], r[1], q[1]);
+    else if constexpr (OP == TF_FIELD_OP_ADD_LAZY4) gl::add_lazy4(x, y, r);
+    else if constexpr (OP == TF_FIELD_OP_SUB_LAZY4) gl::sub_lazy4(x, y, r);
+    else if constexpr (OP == TF_FIELD_OP_MONT_MUL2) gl::mont_mul2(x[0], y[0], x[1], y[1], r[0], r[1]);
+    else if constexpr (OP == TF_FIELD_OP_MONT_MUL3) gl::mont_mul3(x, y, r);
+    else if constexpr (OP == TF_FIELD_OP_MONT_MUL4) gl::mont_mul4(x, y, r);
+    else if constexpr (OP == TF_FIELD_OP_CANONICAL) r[0] = gl::canonical_asm(x[0]);
+    else {
+        u32 tl[W], th[W], h0[W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) tl[i] = (u32)x[i], th[i] = (u32)(x[i] >> 32), h0[i] = (u32)y[i];
+        if constexpr (OP == TF_FIELD_OP_MX_FOLD2) tfk::mx_fold2_tail(tl, th, h0, r);
+        else tfk::mx_fold4_tail<OP == TF_FIELD_OP_MX_FOLD4_CANON>(tl, th, h0, r);
+    }
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+        if (base + i < count) {
+            out0[base + i] = r[i];
+            if constexpr (field_op_two_outputs(OP)) out1[base + i] = q[i];
+        }
+}
+
+template <int OP>
+void field_op_launch(const u64* a, const u64* b, u64* out0, u64* out1, size_t count, hipStream_t s) {
+    const size_t per_block = size_t(256) * field_op_width(OP);
+    hipLaunchKernelGGL(field_op_kernel<OP>, dim3((unsigned)((count + per_block - 1) / per_block)), dim3(256), 0, s, a, b, out0, out1,
+                       (unsigned long long)count);
+}
+template <int... OP>
+void field_op_dispatch(int op, const u64* a, const u64* b, u64* out0, u64* out1, size_t count, hipStream_t s, std::integer_sequence<int, OP...>) {
+    using Fn = void (*)(const u64*, const u64*, u64*, u64*, size_t, hipStream_t);
+    static const Fn table[] = {&field_op_launch<OP>...};
+    table[op](a, b, out0, out1, count, s);
+}
+void debug_field_op_dev(int op, const u64* d_a, const u64* d_b, u64* d_out0, u64* d_out1, size_t count, hipStream_t s) {
+    field_op_dispatch(op, d_a, d_b, d_out0, d_out1, count, s, std::make_integer_sequence<int, TF_FIELD_OP_COUNT>{});
 }
 
 int tip5_permute_dev(u64* d_states, size_t count, void* stream) {

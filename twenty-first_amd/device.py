@@ -64,6 +64,26 @@ def debug_mul_pow2_(x, e: int, stream=None) -> None:
     _chk(_lib.lib().tf_debug_mul_pow2_dev(_p(x), x.numel(), int(e), _stream(stream)), "debug_mul_pow2")
 
 
+# op name -> (TF_FIELD_OP_* code of include/tf_hip.h, elements per block W, number of outputs)
+FIELD_OPS = {
+    "ADD": (0, 1, 1), "SUB": (1, 1, 1), "MONT_MUL": (2, 1, 1), "ADD_SUB": (3, 1, 2), "ADD_SUB2": (4, 2, 2), "ADD_SUB_LAZY2": (5, 2, 2),
+    "ADD_LAZY4": (6, 4, 1), "SUB_LAZY4": (7, 4, 1), "MONT_MUL2": (8, 2, 1), "MONT_MUL3": (9, 3, 1), "MONT_MUL4": (10, 4, 1),
+    "CANONICAL": (11, 1, 1), "MX_FOLD4_CANON": (12, 4, 1), "MX_FOLD4_LAZY": (13, 4, 1), "MX_FOLD2": (14, 2, 1),
+}
+
+
+def debug_field_op(op: str, a, b, out0, out1=None, stream=None) -> None:
+    """Test helper: one hand-scheduled field primitive of the kernels over the operand pairs (a[i], b[i]), W consecutive elements per
+    thread (tf_debug_field_op_dev; FIELD_OPS lists the ops).  out1 is needed by the ops with two outputs (sum, difference) only."""
+    code, _, n_out = FIELD_OPS[op]
+    a, b, out0 = _t(a, "a"), _t(b, "b"), _t(out0, "out0")
+    _need(b.numel() == a.numel() and out0.numel() == a.numel(), "a, b and out0 must have one length")
+    if n_out == 2:
+        _need(out1 is not None and _t(out1, "out1").numel() == a.numel(), f"{op} has two outputs: out1 must be as long as a")
+    _chk(_lib.lib().tf_debug_field_op_dev(code, _p(a), _p(b), _p(out0), _p(out1) if n_out == 2 else None, a.numel(), _stream(stream)),
+         "debug_field_op")
+
+
 def ntt_(x, n: int, batch: int = 1, width: int = 1, inverse: bool = False, stream=None) -> None:
     """In place on device: `batch` slices of n elements (math/ntt.rs:67-82, :109-125)."""
     x = _t(x, "x")
