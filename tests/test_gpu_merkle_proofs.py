@@ -214,6 +214,10 @@ def test_small_edge_cases(tf, oracle):
     assert p.verify(nodes[1]) and [i for i, _ in mt.indexed_leafs([3, 9])] == [3, 9]
     trivial = proof(tf, 200, [], np.zeros((0, 5)), np.zeros((0, 5)))
     assert trivial.verify(nodes[1]) and trivial.verify(np.zeros(5, dtype=np.uint64))
+    # a batch of proofs without any leaf or digest: nothing but the roots goes to the device
+    pair = [trivial, proof(tf, 3, [], np.zeros((0, 5)), np.zeros((0, 5)))]
+    got = tf.MerkleTreeInclusionProof.try_verify_batch(pair, np.vstack([nodes[1], nodes[2]]))
+    assert got.tolist() == [check(oracle, p.tree_height, [], np.zeros((0, 5)), np.zeros((0, 5)))[0] for p in pair] == [OK, OK]
     with pytest.raises(tf.MerkleTreeError) as e:
         proof(tf, 64, [0], nodes[16:17], np.zeros((0, 5))).try_verify(nodes[1])
     assert e.value.variant == "TreeTooHigh"

@@ -262,6 +262,9 @@ def test_hash_varlen_rows(tf, oracle, row_len):
         assert np.array_equal(got, oracle.hash_varlen_rows(rows, row_len))
     else:
         assert np.array_equal(got, np.concatenate([oracle.hash_varlen(np.zeros(0, np.uint64))] * 3))
+        rows3 = np.zeros(15, dtype=np.uint64)  # three empty rows in ONE call, no input pointer
+        assert tf.lib().tf_tip5_hash_varlen_rows(None, 0, 3, rows3.ctypes.data) == 0
+        assert np.array_equal(rows3, got)
 
 
 # ------------------------------------------------------------------ Merkle
@@ -723,6 +726,9 @@ def test_every_entry_point_validates_its_arguments(tf):
     assert lib.tf_poly_square_bfe(NULL, 3, out, 1) == 7
     assert lib.tf_poly_batch_evaluate_bfe(NULL, 3, buf, 2, out) == 7 and lib.tf_poly_batch_evaluate_xfe(buf, 3, buf, 2, NULL) == 7
     assert lib.tf_poly_batch_evaluate_bfe(NULL, 0, buf, 2, out) == 0 and lib.tf_poly_batch_evaluate_bfe(buf, 3, NULL, 0, out) == 0
+    for fn, w in ((lib.tf_poly_batch_evaluate_bfe, 1), (lib.tf_poly_batch_evaluate_xfe, 3)):  # the zero polynomial at five points
+        vals = np.full(5 * w, 77, dtype=np.uint64)
+        assert fn(NULL, 0, buf, 5, vals.ctypes.data) == 0 and not vals.any()
     # Tip5 / Merkle
     assert lib.tf_tip5_permute(NULL, 1) == 7 and lib.tf_tip5_permute(NULL, 0) == 0
     assert lib.tf_tip5_hash_pairs(NULL, out, 1) == 7 and lib.tf_tip5_hash_pairs(buf, NULL, 1) == 7

@@ -116,6 +116,13 @@ def test_add_sub_neg(tf, oracle, w):
     assert np.array_equal(_to_host(out), ref.neg(a, w))
     d.poly_add(_to_dev(a), 5, _empty(0), 0, out, width=w)
     assert np.array_equal(_to_host(out), a)
+    # the host-pointer forms, two rows against b = NULL: the empty operand takes no device words
+    a = _mix(oracle, 3 * 2 * w, 0x32FE)
+    none = np.zeros(0, dtype=np.uint64)
+    for fn, want in ((tf.lib().tf_poly_add, ref.add(a, 3, none, 0, w, 2)), (tf.lib().tf_poly_sub, ref.sub(a, 3, none, 0, w, 2))):
+        host = np.zeros_like(a)
+        assert fn(a.ctypes.data, 3, None, 0, w, host.ctypes.data, 2) == 0
+        assert np.array_equal(host, want)
     # the numpy API trims: (a + b) - b == a, a - a == 0
     pa, pb = tf.Polynomial(_mix(oracle, 70 * w, 1), width=w), tf.Polynomial(_mix(oracle, 33 * w, 2), width=w)
     assert np.array_equal(((pa + pb) - pb).coefficients, pa.coefficients) and (pa - pa).degree() == -1

@@ -125,6 +125,10 @@ def test_zero_and_trailing_zero_dividends(tf, oracle):
     a[45:] = 0  # an unnormalised dividend: the top of q is zero
     q, _ = check_bfe(tf, oracle, a, b, with_pyref=True)
     assert not q[45 - 9 + 1:].any()
+    # two dividends without a coefficient: no quotient, the zero remainder twice
+    q, r = tf.poly_divide(np.zeros(0, dtype=np.uint64), divisor(oracle, 2, 1, 5), batch=2)
+    wq, wr = oracle.naive_divide(np.zeros(0, dtype=np.uint64), divisor(oracle, 2, 1, 5))
+    assert q.size == 0 and wq.size == 0 and r.size == 2 and not r.any() and not wr.any()
 
 
 def test_words_near_p(tf, oracle):

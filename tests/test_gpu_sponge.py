@@ -260,6 +260,11 @@ def test_host_pointer_forms_match_the_dev_forms(tf, oracle):
     sp.pad_and_absorb_all(ragged)
     for i in range(count):
         assert np.array_equal(sp.state[i], ref.pad_and_absorb_all(s5[i], ragged[i]))
+    sp_before = sp.state.copy()
+    # rows without a word: only the states go to the device, every sponge absorbs the padding chunk
+    sp.pad_and_absorb_all(np.zeros((count, 0), dtype=np.uint64))
+    for i in range(count):
+        assert np.array_equal(sp.state[i], ref.pad_and_absorb_all(sp_before[i], np.zeros(0, dtype=np.uint64)))
     # Tip5::new through the host-pointer form
     raw = np.full(16 * 5, 7, dtype=np.uint64)
     assert tf.lib().tf_tip5_sponge_init(raw.ctypes.data, 5, 1) == 0

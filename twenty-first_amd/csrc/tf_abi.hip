@@ -1,5 +1,5 @@
 // tf_abi.hip -- the C ABI of libtf_hip.so (include/tf_hip.h): host-pointer wrappers and the extern "C" entry points.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "aux_kernels.h"
 
 #include <functional>
@@ -8,21 +8,6 @@
 namespace tfi {
 
 // ------------------------------------------------------------------------------------ host-pointer wrappers
-struct DevBuf {
-    u64* p = nullptr;
-    hipStream_t s;
-    explicit DevBuf(hipStream_t st) : s(st) {}
-    int alloc(size_t words) {
-        if (words == 0) return TF_OK;
-        hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&p), words * sizeof(u64), s);
-        if (e != hipSuccess) return hip_fail(e, "hipMallocAsync", __FILE__, __LINE__);
-        return TF_OK;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 // Host buffers are pageable: the runtime stages such copies, and a staged H2D chunk was observed to land
 // AFTER a kernel enqueued behind it on the same stream had already rewritten the destination in place.
 // The host-pointer entry points therefore wait for the upload before enqueueing compute.
@@ -69,16 +54,7 @@ int ntt_host(u64* x, size_t n, size_t batch, int L, int inverse) {
     TRY(check_len(n));
     if (n <= 1 || batch == 0) return TF_OK;
     if (!x) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf d(s);
-    const size_t words = n * batch * L;
-    TRY(d.alloc(words));
-    TRY(h2d(d.p, x, words, s));
-    TRY(ntt_dev(d.p, n, batch, L, inverse, s));
-    TRY(d2h(x, d.p, words, s));
-    return sync(s);
+    return host_in_place(x, n * batch * L, nullptr, 0, [&](u64* d, u64*, hipStream_t s) { return ntt_dev(d, n, batch, L, inverse, s); });
 }
 
 int coset_eval_host(const u64* coeffs, size_t n_coeffs, u64 offset_raw, u64* out, size_t order, size_t batch, int L) {
@@ -86,32 +62,9 @@ int coset_eval_host(const u64* coeffs, size_t n_coeffs, u64 offset_raw, u64* out
     TRY(check_len(order));
     if (order == 0 || batch == 0) return TF_OK;
     if (!out || (n_coeffs && !coeffs)) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf din(s), dout(s);
-    TRY(din.alloc(n_coeffs * batch * L));
-    TRY(dout.alloc(order * batch * L));
-    TRY(h2d(din.p, coeffs, n_coeffs * batch * L, s));
-    TRY(coset_eval_dev(din.p, n_coeffs, offset_raw, dout.p, order, batch, L, s));
-    TRY(d2h(out, dout.p, order * batch * L, s));
-    return sync(s);
-}
-
-template <class F>
-int host_roundtrip(const uint64_t* in1, size_t w1, const uint64_t* in2, size_t w2, uint64_t* out, size_t wo, F&& body) {
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf d1(s), d2(s), dout(s);
-    TRY(d1.alloc(w1));
-    TRY(d2.alloc(w2));
-    TRY(dout.alloc(wo));
-    TRY(h2d(d1.p, in1, w1, s));
-    TRY(h2d(d2.p, in2, w2, s));
-    TRY(body(d1.p, d2.p, dout.p, s));
-    TRY(d2h(out, dout.p, wo, s));
-    return sync(s);
+    return host_roundtrip(coeffs, n_coeffs * batch * L, nullptr, 0, out, order * batch * L, [&](u64* c, u64*, u64* o, hipStream_t s) {
+        return coset_eval_dev(c, n_coeffs, offset_raw, o, order, batch, L, s);
+    });
 }
 
 // Host flavour of the inclusion-proof calls (tf_proof.hip): uploads the ranges the offsets use, runs the batch, copies the verdicts
@@ -130,7 +83,7 @@ int merkle_proofs_host(const uint32_t* heights, size_t n, const uint64_t* loff, 
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    DevBuf di(s), dd(s), da(s), dr(s), dst(s), dp(s);
+    DevTemp di(s), dd(s), da(s), dr(s), dst(s), dp(s);
     TRY(di.alloc(nk));
     TRY(dd.alloc(5 * nk));
     TRY(da.alloc(5 * na));
@@ -428,7 +381,7 @@ int tf_tip5_trace(uint64_t* states, uint64_t* trace, size_t count) try {
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    DevBuf d(s), t(s);
+    DevTemp d(s), t(s);
     TRY(d.alloc(count * 16));
     TRY(t.alloc(count * 96));
     TRY(h2d(d.p, states, count * 16, s));
@@ -440,30 +393,13 @@ int tf_tip5_trace(uint64_t* states, uint64_t* trace, size_t count) try {
 int tf_tip5_permute(uint64_t* states, size_t count) try {
     if (count == 0) return TF_OK;
     if (!states) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf d(s);
-    TRY(d.alloc(count * 16));
-    TRY(h2d(d.p, states, count * 16, s));
-    TRY(tip5_permute_dev(d.p, count, s));
-    TRY(d2h(states, d.p, count * 16, s));
-    return sync(s);
+    return host_in_place(states, count * 16, nullptr, 0, [&](u64* d, u64*, hipStream_t s) { return tip5_permute_dev(d, count, s); });
 } TF_ABI_CATCH
 
 int tf_tip5_hash_pairs(const uint64_t* in, uint64_t* out, size_t count) try {
     if (count == 0) return TF_OK;
     if (!in || !out) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf din(s), dout(s);
-    TRY(din.alloc(count * 10));
-    TRY(dout.alloc(count * 5));
-    TRY(h2d(din.p, in, count * 10, s));
-    TRY(tip5_hash_pairs_dev(din.p, dout.p, count, s));
-    TRY(d2h(out, dout.p, count * 5, s));
-    return sync(s);
+    return host_roundtrip(in, count * 10, nullptr, 0, out, count * 5, [&](u64* i, u64*, u64* o, hipStream_t s) { return tip5_hash_pairs_dev(i, o, count, s); });
 } TF_ABI_CATCH
 
 int tf_tip5_hash_varlen_rows(const uint64_t* rows, size_t row_len, size_t n_rows, uint64_t* out) try {
@@ -472,7 +408,7 @@ int tf_tip5_hash_varlen_rows(const uint64_t* rows, size_t row_len, size_t n_rows
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    DevBuf din(s), dout(s);
+    DevTemp din(s), dout(s);
     TRY(din.alloc(std::max<size_t>(1, n_rows * row_len)));
     TRY(dout.alloc(n_rows * 5));
     TRY(h2d(din.p, rows, n_rows * row_len, s));
@@ -492,7 +428,7 @@ static int prepare_run(size_t in_words, size_t out_words, const std::function<in
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    DevBuf a(s), b(s);
+    DevTemp a(s), b(s);
     if (a.alloc(in_words) || b.alloc(out_words)) return TF_ERR_OUT_OF_MEMORY;
     if (in_words) HIPCHK(hipMemsetAsync(a.p, 0, in_words * sizeof(u64), s));
     TRY(body(a.p, b.p, s));
@@ -525,15 +461,9 @@ int tf_merkle_build(const uint64_t* leaves, size_t n, uint64_t* nodes_out, size_
     TRY(check_leaves(n));
     if (batch == 0) return TF_OK;
     if (!leaves || !nodes_out) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf din(s), dout(s);
-    if (din.alloc(n * batch * 5) || dout.alloc(n * batch * 10)) return TF_ERR_TREE_TOO_HIGH;  // merkle_tree.rs:405-410
-    TRY(h2d(din.p, leaves, n * batch * 5, s));
-    TRY(merkle_build_dev(din.p, n, dout.p, batch, s));
-    TRY(d2h(nodes_out, dout.p, n * batch * 10, s));
-    return sync(s);
+    return host_roundtrip(
+        leaves, n * batch * 5, nullptr, 0, nodes_out, n * batch * 10, [&](u64* l, u64*, u64* o, hipStream_t s) { return merkle_build_dev(l, n, o, batch, s); },
+        TF_ERR_TREE_TOO_HIGH, TF_ERR_TREE_TOO_HIGH);  // merkle_tree.rs:405-410
 } TF_ABI_CATCH
 
 }  // extern "C"  (closed for one internal helper of tf_multi.hip that needs this unit's host-pointer plumbing)
@@ -549,7 +479,7 @@ int merkle_subtree_host(const u64* leaves_sub, size_t m, u64* nodes_tree, size_t
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    DevBuf din(s), dout(s);
+    DevTemp din(s), dout(s);
     if (din.alloc(m * 5)) return TF_ERR_TREE_TOO_HIGH;
     TRY(h2d(din.p, leaves_sub, m * 5, s));
     if (!nodes_tree) {
@@ -574,16 +504,9 @@ int tf_merkle_root(const uint64_t* leaves, size_t n, uint64_t* root_out, size_t 
     TRY(check_leaves(n));
     if (batch == 0) return TF_OK;
     if (!leaves || !root_out) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    DevBuf din(s), dout(s);
-    if (din.alloc(n * batch * 5)) return TF_ERR_TREE_TOO_HIGH;
-    TRY(dout.alloc(batch * 5));
-    TRY(h2d(din.p, leaves, n * batch * 5, s));
-    TRY(merkle_root_dev(din.p, n, dout.p, batch, s));
-    TRY(d2h(root_out, dout.p, batch * 5, s));
-    return sync(s);
+    return host_roundtrip(
+        leaves, n * batch * 5, nullptr, 0, root_out, batch * 5, [&](u64* l, u64*, u64* o, hipStream_t s) { return merkle_root_dev(l, n, o, batch, s); },
+        TF_ERR_TREE_TOO_HIGH);
 } TF_ABI_CATCH
 
 // ---- SURVEY 8(f1)-(f3) ---------------------------------------------------------------------------
@@ -727,15 +650,7 @@ static int tree_new_any(const uint64_t* domain, size_t n, int L, bool on_device,
         rc = tree_handle_new(domain, n, L, stream, &H);
     } else {
         if (n && !domain) return TF_ERR_NULL_POINTER;
-        DeviceCtx* ctx = nullptr;
-        rc = current_ctx(&ctx);
-        if (rc) return rc;
-        hipStream_t s = host_stream();
-        DevBuf d(s);
-        rc = d.alloc(n * L);
-        if (!rc) rc = h2d(d.p, domain, n * L, s);
-        if (!rc) rc = tree_handle_new(d.p, n, L, s, &H);
-        if (!rc) rc = sync(s);
+        rc = host_roundtrip(domain, n * L, nullptr, 0, nullptr, 0, [&](u64* d, u64*, u64*, hipStream_t s) { return tree_handle_new(d, n, L, s, &H); });
     }
     if (rc) return rc;
     *tree = reinterpret_cast<tf_zerofier_tree*>(H);
@@ -1088,7 +1003,7 @@ int tf_merkle_authentication_structure_dev(const uint64_t* d_nodes, size_t num_l
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    DevBuf didx(s), dout(s);
+    DevTemp didx(s), dout(s);
     TRY(didx.alloc(idx.size()));
     TRY(dout.alloc(idx.size() * 5));
     TRY(h2d(didx.p, reinterpret_cast<const u64*>(idx.data()), idx.size(), s));

@@ -1,7 +1,7 @@
 // tf_algebra.hip -- Add / Sub / Neg, scalar_mul, scale, formal_derivative, degree (math/polynomial.rs), the XFieldElement x
 // BFieldElement pointwise product and the weighted sum of columns: argument checks, the launchers over algebra_kernels.h and the
 // device / host flavours behind the entry points of include/tf_hip.h (which has the contract).
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "algebra_kernels.h"
 
 namespace tfi {
@@ -26,32 +26,6 @@ tfk::AlgScalar scalar_of(const u64* s, int width) {
     for (int k = 0; k < width; ++k) r.v[k] = s[k];
     return r;
 }
-
-// device memory for a host-pointer call: one block of the library's stream-ordered pool, handed out in pieces and given back (in
-// stream order) when the call returns
-struct Stage {
-    hipStream_t s;
-    u64* base = nullptr;
-    size_t used = 0;
-    explicit Stage(hipStream_t st) : s(st) {}
-    int get(size_t words) {
-        hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&base), std::max<size_t>(words, 1) * sizeof(u64), s);
-        if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(poly algebra)", __FILE__, __LINE__);
-        return TF_OK;
-    }
-    u64* take(size_t words) {
-        u64* p = base + used;
-        used += words;
-        return p;
-    }
-    int upload(const u64* h, size_t words, u64** d) {
-        *d = take(words);
-        return words ? h2d(*d, h, words, s) : TF_OK;
-    }
-    ~Stage() {
-        if (base) (void)hipFreeAsync(base, s);
-    }
-};
 
 // ---------------------------------------------------------------------------------------------- launchers (device pointers, sizes checked)
 int launch_addsub(const u64* a, size_t na, const u64* b, size_t nb, int w, u64* out, size_t batch, bool sub, hipStream_t s) {
@@ -170,17 +144,9 @@ int poly_addsub(const u64* a, size_t na, const u64* b, size_t nb, int width, u64
     if (nmax > kMaxLen) return TF_ERR_LEN_TOO_LARGE;
     TRY(need_device());
     if (!host) return launch_addsub(a, na, b, nb, width, out, batch, sub, static_cast<hipStream_t>(stream));
-    hipStream_t s = host_stream();
-    const size_t wa = na * width * batch, wb = nb * width * batch, wo = nmax * width * batch;
-    Stage d(s);
-    TRY(d.get(wa + wb + wo));
-    u64 *da, *db;
-    TRY(d.upload(a, wa, &da));
-    TRY(d.upload(b, wb, &db));
-    u64* dout = d.take(wo);
-    TRY(launch_addsub(da, na, db, nb, width, dout, batch, sub, s));
-    TRY(d2h(out, dout, wo, s));
-    return sync(s);
+    // (an empty operand is a null pointer on the device too, as the _dev form takes it: the kernel reads no word of it)
+    return host_roundtrip(a, na * width * batch, b, nb * width * batch, out, nmax * width * batch,
+                          [&](u64* da, u64* db, u64* dout, hipStream_t s) { return launch_addsub(da, na, db, nb, width, dout, batch, sub, s); });
 }
 
 int poly_neg(const u64* a, size_t na, int width, u64* out, size_t batch, bool host, void* stream) {
@@ -191,14 +157,7 @@ int poly_neg(const u64* a, size_t na, int width, u64* out, size_t batch, bool ho
     TRY(need_device());
     const size_t words = na * width * batch;
     if (!host) return launch_neg(a, out, words, static_cast<hipStream_t>(stream));
-    hipStream_t s = host_stream();
-    Stage d(s);
-    TRY(d.get(words));
-    u64* da;
-    TRY(d.upload(a, words, &da));
-    TRY(launch_neg(da, da, words, s));
-    TRY(d2h(out, da, words, s));
-    return sync(s);
+    return host_roundtrip(a, words, nullptr, 0, out, words, [&](u64* da, u64*, u64* dout, hipStream_t s) { return launch_neg(da, dout, words, s); });
 }
 
 // scale = false: scalar_mul (every coefficient times `scalar`); scale = true: coefficient j times scalar^j
@@ -214,16 +173,7 @@ int poly_scalar_mul(const u64* a, size_t na, int width_a, const u64* scalar, int
         return scale ? launch_scale(da, na, width_a, sc, width_s, dout, batch, s) : launch_scalar_mul(da, na * batch, width_a, sc, width_s, dout, s);
     };
     if (!host) return run(a, out, static_cast<hipStream_t>(stream));
-    hipStream_t s = host_stream();
-    const size_t win = na * width_a * batch, wout = na * wo * batch;
-    Stage d(s);
-    TRY(d.get(win + wout));
-    u64* da;
-    TRY(d.upload(a, win, &da));
-    u64* dout = d.take(wout);
-    TRY(run(da, dout, s));
-    TRY(d2h(out, dout, wout, s));
-    return sync(s);
+    return host_roundtrip(a, na * width_a * batch, nullptr, 0, out, na * wo * batch, [&](u64* da, u64*, u64* dout, hipStream_t s) { return run(da, dout, s); });
 }
 
 int poly_derivative(const u64* a, size_t na, int width, u64* out, size_t batch, bool host, void* stream) {
@@ -233,16 +183,8 @@ int poly_derivative(const u64* a, size_t na, int width, u64* out, size_t batch, 
     if (na > kMaxLen) return TF_ERR_LEN_TOO_LARGE;
     TRY(need_device());
     if (!host) return launch_derivative(a, na, width, out, batch, static_cast<hipStream_t>(stream));
-    hipStream_t s = host_stream();
-    const size_t win = na * width * batch, wout = (na - 1) * width * batch;
-    Stage d(s);
-    TRY(d.get(win + wout));
-    u64* da;
-    TRY(d.upload(a, win, &da));
-    u64* dout = d.take(wout);
-    TRY(launch_derivative(da, na, width, dout, batch, s));
-    TRY(d2h(out, dout, wout, s));
-    return sync(s);
+    return host_roundtrip(a, na * width * batch, nullptr, 0, out, (na - 1) * width * batch,
+                          [&](u64* da, u64*, u64* dout, hipStream_t s) { return launch_derivative(da, na, width, dout, batch, s); });
 }
 
 int poly_degree(const u64* a, size_t na, int width, size_t batch, long long* degrees, bool host, void* stream) {
@@ -256,16 +198,9 @@ int poly_degree(const u64* a, size_t na, int width, size_t batch, long long* deg
     }
     TRY(need_device());
     if (!host) return launch_degree(a, na, width, batch, degrees, static_cast<hipStream_t>(stream));
-    hipStream_t s = host_stream();
-    const size_t win = na * width * batch;
-    Stage d(s);
-    TRY(d.get(win + batch));
-    u64* da;
-    TRY(d.upload(a, win, &da));
-    u64* ddeg = d.take(batch);
-    TRY(launch_degree(da, na, width, batch, reinterpret_cast<long long*>(ddeg), s));
-    TRY(d2h(reinterpret_cast<u64*>(degrees), ddeg, batch, s));
-    return sync(s);
+    return host_roundtrip(a, na * width * batch, nullptr, 0, reinterpret_cast<u64*>(degrees), batch, [&](u64* da, u64*, u64* ddeg, hipStream_t s) {
+        return launch_degree(da, na, width, batch, reinterpret_cast<long long*>(ddeg), s);
+    });
 }
 
 int hadamard_xfe_bfe_dev(const u64* a, const u64* b, u64* out, size_t count, void* stream) {
@@ -289,18 +224,17 @@ int poly_lincomb(const u64* polys, size_t n, int width_p, size_t stride, size_t 
     hipStream_t s = host_stream();
     // the columns are packed on the way up (the words between n * width_p and stride are never read, on the host either)
     const size_t col = n * width_p, wp = k * col, ww = k * width_w, wo = n * std::max(width_p, width_w);
-    Stage d(s);
-    TRY(d.get(wp + ww + wo));
-    u64* dp = d.take(wp);
+    DevTemp dp(s), dw(s), dout(s);  // (k = 0: no columns and no weights, two null pointers that launch_lincomb never passes on)
+    TRY(dp.alloc(wp, "poly algebra"));
+    TRY(dw.alloc(ww, "poly algebra"));
+    TRY(dout.alloc(wo, "poly algebra"));
     if (k) {
-        HIPCHK(hipMemcpy2DAsync(dp, col * sizeof(u64), polys, stride * sizeof(u64), col * sizeof(u64), k, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(dp.p, col * sizeof(u64), polys, stride * sizeof(u64), col * sizeof(u64), k, hipMemcpyHostToDevice, s));
         TRY(sync(s));  // pageable host memory: the caller may reuse it when the call returns
     }
-    u64* dw;
-    TRY(d.upload(weights, ww, &dw));
-    u64* dout = d.take(wo);
-    TRY(launch_lincomb(dp, n, width_p, col, k, dw, width_w, dout, s));
-    TRY(d2h(out, dout, wo, s));
+    TRY(h2d(dw.p, weights, ww, s));
+    TRY(launch_lincomb(dp.p, n, width_p, col, k, dw.p, width_w, dout.p, s));
+    TRY(d2h(out, dout.p, wo, s));
     return sync(s);
 }
 

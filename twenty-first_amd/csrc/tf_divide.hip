@@ -1,8 +1,10 @@
 // tf_divide.hip -- polynomial division with remainder (Polynomial::divide / naive_divide, Div, Rem, reduce / fast_reduce;
 // math/polynomial.rs:539-600, :989-1048, :2502-2524) and formal_power_series_inverse_newton (:1281-1366): the planner over
 // divide_kernels.h and the library's transforms (run_ntt), and the entry points of include/tf_hip.h.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "divide_kernels.h"
+
+#include <deque>
 
 namespace tfi {
 namespace {
@@ -17,19 +19,17 @@ size_t next_pow2(size_t v) {
     return n;
 }
 
-// stream-ordered work space of one call, given back (in stream order) when the call has enqueued its work
-struct Temp {
+// stream-ordered work space of one call: one DevTemp per block, all given back (in stream order) when the call has enqueued its work.
+// An empty piece is still a block of one word, so every kernel gets a valid pointer for it.
+struct WorkSpace {
     hipStream_t s;
-    std::vector<void*> ps;
-    explicit Temp(hipStream_t st) : s(st) {}
+    std::deque<DevTemp> blocks;
+    explicit WorkSpace(hipStream_t st) : s(st) {}
     int get(u64** p, size_t words) {
-        hipError_t e = pool_malloc_async(reinterpret_cast<void**>(p), std::max<size_t>(words, 1) * sizeof(u64), s);
-        if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(divide)", __FILE__, __LINE__);
-        ps.push_back(*p);
+        blocks.emplace_back(s);
+        TRY(blocks.back().alloc(std::max<size_t>(words, 1), "divide"));
+        *p = blocks.back().p;
         return TF_OK;
-    }
-    ~Temp() {
-        for (void* p : ps) (void)hipFreeAsync(p, s);
     }
 };
 
@@ -60,7 +60,7 @@ int xform(DeviceCtx* ctx, const u64* in, long long in_bs, long long n_coeffs, u6
 // dst (batch x N elements) = the rows of src (len elements each, src_bs words apart) folded modulo x^N - 1; long rows fold in steps
 // of at most 64 terms per thread, so the first step fills the chip however short the modulus is
 template <int L>
-int fold(const u64* src, size_t len, long long src_bs, u64* dst, size_t N, size_t batch, hipStream_t s, Temp& tmp) {
+int fold(const u64* src, size_t len, long long src_bs, u64* dst, size_t N, size_t batch, hipStream_t s, WorkSpace& tmp) {
     if (len <= N) return copy_pad(src, src_bs, (long long)(len * L), dst, (long long)(N * L), (long long)(N * L), (long long)batch, s);
     const u64* cur = src;
     size_t cur_len = len;
@@ -96,7 +96,7 @@ int launch_newton_lds(DeviceCtx* ctx, tfk::NewtonArgs A, hipStream_t s) {
 // H (k elements) = rev(b)^-1 mod x^k, b of m + 1 coefficients.  Doublings up to NewtonMax<L>::PMAX in one launch of
 // newton_lds_kernel, each further one as two forward transforms, newton_point_kernel and an inverse transform.
 template <int L>
-int inverse_of_reversed(DeviceCtx* ctx, const u64* b, size_t m, size_t k, u64* H, int* status, hipStream_t s, Temp& tmp) {
+int inverse_of_reversed(DeviceCtx* ctx, const u64* b, size_t m, size_t k, u64* H, int* status, hipStream_t s, WorkSpace& tmp) {
     using G = tfk::NewtonMax<L>;
     tfk::NewtonArgs A{};
     A.b = b;
@@ -151,7 +151,7 @@ template <int L>
 int divide_dev_t(const u64* a, size_t na, size_t batch, const u64* b, size_t nb, u64* q, u64* r, hipStream_t s, int* status) {
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
-    Temp tmp(s);
+    WorkSpace tmp(s);
     const size_t m = nb - 1;
     if (na < nb) {  // (zero, self): polynomial.rs:560-563
         if (status) TRY(launch(tfk::head_inverse_kernel<L>, 1, s, b + m * L, (const u64*)nullptr, (u64*)nullptr, status, 17, 0));
@@ -239,7 +239,7 @@ int divide_host(const u64* a, size_t na, size_t batch, const u64* b, size_t nb, 
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    Temp tmp(s);
+    WorkSpace tmp(s);
     u64 *da = nullptr, *db = nullptr, *dq = nullptr, *dr = nullptr;
     TRY(tmp.get(&da, wa));
     TRY(tmp.get(&db, nb * L));
@@ -282,7 +282,7 @@ int fps_dev_t(const u64* f, size_t nf, size_t precision, u64* out, hipStream_t s
     const int R = ilog2(next_pow2(std::max<size_t>(precision, 1)));
     const size_t F = next_pow2(len);
     TRY(check_len(F));
-    Temp tmp(s);
+    WorkSpace tmp(s);
     u64 *Gh = nullptr, *X = nullptr, *Y = nullptr;
     TRY(tmp.get(&Gh, F * L));
     TRY(tmp.get(&X, F * L));
@@ -327,17 +327,7 @@ int fps_host(const u64* f, size_t nf, size_t precision, u64* out, int L) {
     if (is_zero(f, L)) return TF_ERR_INVERSE_OF_ZERO;
     if (is_zero(f + (nf - 1) * L, L)) return TF_ERR_INVALID_ARGUMENT;
     const size_t len = fps_len(nf, precision);
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    Temp tmp(s);
-    u64 *df = nullptr, *dout = nullptr;
-    TRY(tmp.get(&df, nf * L));
-    TRY(tmp.get(&dout, len * L));
-    TRY(h2d(df, f, nf * L, s));
-    TRY(fps_dev(df, nf, precision, dout, s, nullptr, L));
-    TRY(d2h(out, dout, len * L, s));
-    return sync(s);
+    return host_roundtrip(f, nf * L, nullptr, 0, out, len * L, [&](u64* df, u64*, u64* dout, hipStream_t s) { return fps_dev(df, nf, precision, dout, s, nullptr, L); });
 }
 
 }  // namespace tfi

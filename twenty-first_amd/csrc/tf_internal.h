@@ -12,6 +12,8 @@
 //   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
 //   tf_algebra.hip add / sub / neg, scalar_mul, scale, formal_derivative, degree and weighted sums of columns (algebra_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
+//   tf_temp.h     (header, included by the units above) DevTemp, the one owner of a stream-ordered temporary; the staged upload, the
+//                 per-unit Tip5 constants upload and the host round trip that every unit used to spell out for itself
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,7 +99,7 @@ extern DeviceCtx g_ctx[kMaxDevices];
 // ------------------------------------------------------------------------------------ tf_ntt.hip
 int current_ctx(DeviceCtx** out);
 int device_cus();  // compute units of the calling thread's CURRENT device (cached per device; 256 if the runtime will not say)
-hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream);  // every stream-ordered temporary of the library
+hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream);  // every stream-ordered temporary of the library: taken through DevTemp (tf_temp.h)
 int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx::ScratchBlock* out);
 void scratch_release(DeviceCtx* ctx, DeviceCtx::ScratchBlock blk, hipStream_t stream);
 int release_caches(DeviceCtx* ctx);
@@ -119,7 +121,9 @@ extern unsigned long long* g_dbg_buf;
 enum : u64 { TAG_INNER = 1, TAG_POST = 2, TAG_TINY = 3, TAG_BLOCK1 = 4, TAG_BLOCK2 = 5, TAG_LAT = 6 };
 inline u64 make_key(u64 tag, u64 a, u64 b, u64 c, u64 d) { return (tag << 56) | (a << 40) | (b << 24) | (c << 8) | d; }
 int upload_table(const std::vector<u64>& host, u64** dev);
-int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, bool* temp);
+class DevTemp;  // tf_temp.h
+// (a table too large to cache is a stream-ordered temporary: *own takes it and gives it back after the passes that read it)
+int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, DevTemp* own);
 
 int check_len(size_t n);
 int pass_count(int log_n);

@@ -1,7 +1,7 @@
 // tf_inverse.hip -- FiniteField::batch_inversion (math/traits.rs:93-121) and Inverse::inverse_or_zero (:39-45) over a vector of
 // BFieldElements / XFieldElements: the launcher over inverse_kernels.h and the device / host flavours behind the entry points of
 // include/tf_hip.h.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "inverse_kernels.h"
 
 namespace tfi {
@@ -34,21 +34,6 @@ int launch(const u64* in, size_t n, u64* out, int L, bool or_zero, int* status, 
     return or_zero ? launch_inverse<3, true>(in, n, out, status, s) : launch_inverse<3, false>(in, n, out, status, s);
 }
 
-// words of the library's stream-ordered pool, given back (in stream order) when the call has enqueued its work
-struct PoolWords {
-    hipStream_t s;
-    u64* p = nullptr;
-    explicit PoolWords(hipStream_t st) : s(st) {}
-    int get(size_t words) {
-        hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&p), words * sizeof(u64), s);
-        if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(batch_inversion)", __FILE__, __LINE__);
-        return TF_OK;
-    }
-    ~PoolWords() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 // zero the flag word, run, copy the flag back and wait: TF_ERR_INVERSE_OF_ZERO when some element is zero (traits.rs:106)
 int run_checked(const u64* in, size_t n, u64* out, int L, int* flag, hipStream_t s) {
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s));
@@ -71,9 +56,9 @@ int batch_inverse_dev(const u64* in, size_t n, u64* out, int L, bool or_zero, vo
     TRY(current_ctx(&ctx));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (or_zero || d_status) return launch(in, n, out, L, or_zero, d_status, s);
-    PoolWords flag(s);
-    TRY(flag.get(1));
-    return run_checked(in, n, out, L, reinterpret_cast<int*>(flag.p), s);
+    DevTemp flag(s);
+    TRY(flag.alloc(1, "batch_inversion"));
+    return run_checked(in, n, out, L, flag.as<int>(), s);
 }
 
 // host pointers: one upload, the inversion in place on the device, one download (in == out is fine)
@@ -84,8 +69,8 @@ int batch_inverse_host(const u64* in, size_t n, u64* out, int L, bool or_zero) {
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     const size_t words = n * L;
-    PoolWords d(s);  // the elements, then the flag word
-    TRY(d.get(words + 1));
+    DevTemp d(s);  // the elements, then the flag word
+    TRY(d.alloc(words + 1, "batch_inversion"));
     TRY(h2d(d.p, in, words, s));
     int rc = TF_OK;
     if (or_zero) {

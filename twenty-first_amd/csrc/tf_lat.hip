@@ -2,7 +2,7 @@
 // calls with little work, and the one-launch-per-level kernels of the zerofier-tree walks and build.  The planner (tf_ntt.hip:
 // run_ntt) and the tree orchestration (tf_poly.hip) decide WHEN; the thresholds they ask for live here (lat_wanted, lat2_wanted,
 // tree_level_wanted, tree_build_level_wanted) next to the measurements they come from.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "lat_kernels.h"
 
 namespace tfi {
@@ -299,17 +299,12 @@ int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long l
     const int a1 = (log_n + 1) / 2, a2 = log_n - a1;
     const long long N1 = 1ll << a1, N2 = 1ll << a2, n = 1ll << log_n;
     const u64 *tw1 = nullptr, *tw2 = nullptr, *post = nullptr;
-    bool post_temp = false;
-    int rc = get_lat_table(ctx, a1, inverse, &tw1, 0);
-    if (!rc) rc = get_lat_table(ctx, a2, inverse, &tw2, inverse ? log_n : 0);
-    if (!rc) rc = get_post_table(ctx, log_n, a1, inverse, stream, &post, &post_temp);
-    if (rc) return rc;
+    DevTemp post_own(stream);  // (a table too large to cache goes back behind the passes)
+    TRY(get_lat_table(ctx, a1, inverse, &tw1, 0));
+    TRY(get_lat_table(ctx, a2, inverse, &tw2, inverse ? log_n : 0));
+    TRY(get_post_table(ctx, log_n, a1, inverse, stream, &post, &post_own));
     DeviceCtx::ScratchBlock sblk;
-    rc = scratch_acquire(ctx, batch * (size_t)n * L * sizeof(u64), stream, &sblk);
-    if (rc) {
-        if (post_temp) (void)hipFreeAsync(const_cast<u64*>(post), stream);
-        return rc;
-    }
+    TRY(scratch_acquire(ctx, batch * (size_t)n * L * sizeof(u64), stream, &sblk));
     tfk::NttLat2Args c{};  // column pass: the caller's input -> scratch
     c.in = in;
     c.out = sblk.p;
@@ -328,7 +323,7 @@ int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long l
     c.scale_es = N2;
     c.L = L;
     c.cfast = 1;
-    rc = inverse ? launch_lat2_dir<true, false>(a1, c, batch, stream) : launch_lat2_dir<false, false>(a1, c, batch, stream);
+    int rc = inverse ? launch_lat2_dir<true, false>(a1, c, batch, stream) : launch_lat2_dir<false, false>(a1, c, batch, stream);
     if (!rc) {
         tfk::NttLat2Args r{};  // last pass: rows of the scratch -> natural order in the caller's output
         r.in = sblk.p;
@@ -350,7 +345,6 @@ int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long l
         rc = inverse ? launch_lat2_dir<true, true>(a2, r, batch, stream) : launch_lat2_dir<false, true>(a2, r, batch, stream);
     }
     scratch_release(ctx, sblk, stream);
-    if (post_temp) (void)hipFreeAsync(const_cast<u64*>(post), stream);
     return rc;
 }
 

@@ -13,7 +13,7 @@
 //   leaf level    wanted leafs are read from the caller's array (a tree that is narrow from its leafs is all top block).
 // The plan (node -> slot, per level) is built on the host from the host's leaf indices and reaches the device through pinned staging, so
 // the _dev form never waits for its stream.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "merkle_open_kernels.h"
 
 namespace tfi {
@@ -61,16 +61,6 @@ size_t open_workspace_bytes(size_t n, size_t batch, size_t k_nodes) {
     }
     return digests * 5 * sizeof(u64) + k_nodes * sizeof(OpenEntry);
 }
-
-struct Temp {  // stream-ordered device work space
-    u64* p = nullptr;
-    hipStream_t s;
-    explicit Temp(hipStream_t st) : s(st) {}
-    hipError_t alloc(size_t bytes) { return bytes ? pool_malloc_async(reinterpret_cast<void**>(&p), bytes, s) : hipSuccess; }
-    ~Temp() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
 
 int emit(const u64* level, long long level_ts, const OpenEntry* plan, size_t count, size_t batch, u64* out, long long out_ts, hipStream_t s) {
     if (count == 0) return TF_OK;
@@ -159,25 +149,14 @@ int open_run(const u64* d_leafs, size_t n, size_t batch, const std::vector<unsig
         return run_end[level] - *first;
     };
 
-    Temp ws(s);
-    if (const hipError_t e = ws.alloc(open_workspace_bytes(n, batch, count)); e != hipSuccess) {
-        hip_fail(e, "pool_malloc_async(merkle open)", __FILE__, __LINE__);
-        return TF_ERR_TREE_TOO_HIGH;  // as merkle_root_dev: merkle_tree.rs:405-410
-    }
+    DevTemp ws(s);
+    if (ws.alloc_bytes(open_workspace_bytes(n, batch, count), "merkle open")) return TF_ERR_TREE_TOO_HIGH;  // as merkle_root_dev: merkle_tree.rs:405-410
     u64* a = ws.p;
     u64* b = a + 5 * lay.a;
     u64* top = b + 5 * lay.b;
     // (the plan sits behind the digests of the REQUEST, which may be more than this batch uses: open_workspace_bytes)
     const OpenEntry* d_plan = reinterpret_cast<const OpenEntry*>(reinterpret_cast<const char*>(ws.p) + open_workspace_bytes(n, batch, 0));
-    if (count) {
-        const size_t bytes = count * sizeof(OpenEntry);
-        Staging stg;
-        TRY(stage_acquire(dev, bytes, &stg));
-        std::memcpy(stg.p, plan.data(), bytes);
-        const hipError_t e = hipMemcpyAsync(const_cast<OpenEntry*>(d_plan), stg.p, bytes, hipMemcpyHostToDevice, s);
-        stage_release(dev, stg, s);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(merkle open plan)", __FILE__, __LINE__);
-    }
+    TRY(StagedUpload::copy_to(dev, const_cast<OpenEntry*>(d_plan), plan.data(), count * sizeof(OpenEntry), s, "merkle open plan"));
 
     const u64* level = d_leafs;  // the level the top block starts from, w digests per tree
     long long w = N, level_ts = 5 * N;
@@ -225,16 +204,11 @@ int merkle_open_host(const u64* leafs, size_t n, size_t batch, const uint64_t* l
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    Temp din(s), dout(s), droots(s);
+    DevTemp din(s), dout(s), droots(s);
     const size_t out_words = batch * idx.size() * 5;
-    hipError_t e = din.alloc(n * batch * 5 * sizeof(u64));
-    if (e != hipSuccess) {
-        hip_fail(e, "pool_malloc_async(merkle open leafs)", __FILE__, __LINE__);
-        return TF_ERR_TREE_TOO_HIGH;
-    }
-    e = dout.alloc(out_words * sizeof(u64));
-    if (e == hipSuccess && roots) e = droots.alloc(batch * 5 * sizeof(u64));
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(merkle open output)", __FILE__, __LINE__);
+    if (din.alloc(n * batch * 5, "merkle open leafs")) return TF_ERR_TREE_TOO_HIGH;
+    TRY(dout.alloc(out_words, "merkle open output"));
+    TRY(droots.alloc(roots ? batch * 5 : 0, "merkle open output"));
     TRY(h2d(din.p, leafs, n * batch * 5, s));
     TRY(open_run(din.p, n, batch, idx, dout.p, droots.p, s));
     TRY(d2h(out, dout.p, out_words, s));

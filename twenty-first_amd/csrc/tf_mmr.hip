@@ -1,6 +1,6 @@
 // tf_mmr.hip -- planner and launchers of the batched Merkle Mountain Range operations (mmr_kernels.h), with their host flavours:
 // util_types/mmr/mmr_accumulator.rs, mmr_membership_proof.rs, shared_basic.rs.
-#include "tf_internal.h"
+#include "tf_temp.h"
 
 #include <unordered_map>
 
@@ -15,71 +15,8 @@ namespace {
 using tfm::tfk::MmrChain;
 constexpr u64 kMaxLeafs = 1ull << 63;  // mmr.rs:12-13
 
-std::mutex g_consts_mu;
-bool g_consts_ready[kMaxDevices];
-
-int ensure_mmr_consts(int dev) {
-    std::lock_guard<std::mutex> lk(g_consts_mu);
-    if (g_consts_ready[dev]) return TF_OK;
-    tfm::tfk::Tip5Consts c;
-    for (int i = 0; i < 80; ++i) c.rc[i] = gl::to_mont(kRoundConstants[i]);
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(tfm::tfk::g_tip5), &c, sizeof(c)));
-    tfm::tfk::Tip5MxConsts mx;
-    tfm::tfk::fill_tip5_mx(mx, c.rc);
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(tfm::tfk::g_tip5_mx), &mx, sizeof(mx)));
-    HIPCHK(hipDeviceSynchronize());
-    g_consts_ready[dev] = true;
-    return TF_OK;
-}
-
-int ctx_dev(int* dev) {
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    *dev = (int)(ctx - g_ctx);
-    return ensure_mmr_consts(*dev);
-}
-
-// Host-built words (descriptors, move lists) reach the device through pinned staging: the _dev forms never wait for their stream.
-// The device copy is freed on the stream when the Upload goes out of scope, after the launches that read it are enqueued.
-struct Upload {
-    void* d = nullptr;
-    hipStream_t s = nullptr;
-    ~Upload() {
-        if (d) (void)hipFreeAsync(d, s);
-    }
-    int put(int dev, const void* host, size_t bytes, hipStream_t st) {
-        s = st;
-        if (!bytes) return TF_OK;
-        Staging stg;
-        TRY(stage_acquire(dev, bytes, &stg));
-        std::memcpy(stg.p, host, bytes);
-        hipError_t e = pool_malloc_async(&d, bytes, s);
-        if (e != hipSuccess) {
-            stage_release(dev, stg, s);
-            d = nullptr;
-            return hip_fail(e, "pool_malloc_async(mmr descriptors)", __FILE__, __LINE__);
-        }
-        e = hipMemcpyAsync(d, stg.p, bytes, hipMemcpyHostToDevice, s);
-        stage_release(dev, stg, s);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(mmr descriptors)", __FILE__, __LINE__);
-        return TF_OK;
-    }
-};
-
-struct Temp {  // stream-ordered device work space
-    u64* p = nullptr;
-    hipStream_t s;
-    explicit Temp(hipStream_t st) : s(st) {}
-    int alloc(size_t words) {
-        if (!words) return TF_OK;
-        const hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&p), words * sizeof(u64), s);
-        if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(mmr work space)", __FILE__, __LINE__);
-        return TF_OK;
-    }
-    ~Temp() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
+Tip5ConstsOnce g_consts;
+int ctx_dev(int* dev) { return g_consts.ensure(dev, tfm::tfk::g_tip5, tfm::tfk::g_tip5_mx); }
 
 inline unsigned grid_for(long long threads, int per_block) { return (unsigned)((threads + per_block - 1) / per_block); }
 
@@ -214,10 +151,10 @@ int mmr_sweep(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_
                 if ((N >> g) & 1) moves.insert(moves.end(), {at(S_OLD, old_at(g)), at(D_PEAKS, new_at(g))});
     }
     moves_at[top + 1] = moves.size() / 2;
-    Upload up;
-    TRY(up.put(dev, moves.data(), moves.size() * sizeof(unsigned long long), s));
-    const auto* dm = static_cast<const unsigned long long*>(up.d);
-    Temp even(s), odd(s);
+    StagedUpload up(s);
+    TRY(up.put(dev, moves.data(), moves.size() * sizeof(unsigned long long), "mmr move list"));
+    const auto* dm = up.as<unsigned long long>();
+    DevTemp even(s), odd(s);
     TRY(even.alloc(5 * even_words));
     TRY(odd.alloc(5 * odd_words));
     const MmrMoveArrays arrays{{leafs, old_peaks, even.p, odd.p}, {wants.empty() ? proofs : wanted, new_peaks, even.p, odd.p}};
@@ -255,9 +192,9 @@ int mmr_bag_peaks_dev(const uint64_t* leaf_counts, size_t n_acc, const u64* peak
     std::stable_sort(ch.begin(), ch.end(), [](const MmrChain& x, const MmrChain& y) { return __builtin_popcountll(x.a) > __builtin_popcountll(y.a); });
     int dev = 0;
     TRY(ctx_dev(&dev));
-    Upload up;
-    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), s));
-    return launch_chains<tfm::tfk::kMmrBag>(static_cast<const MmrChain*>(up.d), (long long)n_acc, nullptr, peaks, nullptr, out, nullptr, 0, 0,
+    StagedUpload up(s);
+    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), "mmr chains"));
+    return launch_chains<tfm::tfk::kMmrBag>(up.as<MmrChain>(), (long long)n_acc, nullptr, peaks, nullptr, out, nullptr, 0, 0,
                                             nullptr, s);
 }
 
@@ -275,9 +212,9 @@ int mmr_verify_dev(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, c
     std::stable_sort(ch.begin(), ch.end(), [](const MmrChain& x, const MmrChain& y) { return x.c > y.c; });
     int dev = 0;
     TRY(ctx_dev(&dev));
-    Upload up;
-    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), s));
-    return launch_chains<tfm::tfk::kMmrVerify>(static_cast<const MmrChain*>(up.d), (long long)n, digests, paths, peaks, nullptr, idx, leaf_count,
+    StagedUpload up(s);
+    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), "mmr chains"));
+    return launch_chains<tfm::tfk::kMmrVerify>(up.as<MmrChain>(), (long long)n, digests, paths, peaks, nullptr, idx, leaf_count,
                                                (long long)n_peaks, statuses, s);
 }
 
@@ -377,10 +314,10 @@ int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, c
         }
     }
     const size_t n_fixes = (words.size() - fixes_at) / 3;
-    Upload up;
-    TRY(up.put(dev, words.data(), words.size() * sizeof(unsigned long long), s));
-    const auto* dw = static_cast<const unsigned long long*>(up.d);
-    Temp A(s);
+    StagedUpload up(s);
+    TRY(up.put(dev, words.data(), words.size() * sizeof(unsigned long long), "mmr mutation plan"));
+    const auto* dw = up.as<unsigned long long>();
+    DevTemp A(s);
     TRY(A.alloc(5 * M * (Lmax + 1)));
     TRY(launch_moves(leafs, dw + leaf_moves_at, (long long)M, A.p, s));
     for (u64 l = 0; l < Lmax; ++l) {
@@ -470,10 +407,10 @@ int mmr_successor_verify_dev(size_t P, const uint64_t* old_counts, const uint64_
     std::stable_sort(ch.begin(), ch.end(), [](const auto& x, const auto& y) { return x.steps > y.steps; });
     int dev = 0;
     TRY(ctx_dev(&dev));
-    Upload up;
-    TRY(up.put(dev, ch.data(), ch.size() * sizeof(ch[0]), s));
+    StagedUpload up(s);
+    TRY(up.put(dev, ch.data(), ch.size() * sizeof(ch[0]), "mmr successor chains"));
     hipLaunchKernelGGL(tfm::tfk::mmr_successor_kernel, dim3(grid_for((long long)P, 64)), dim3(256), 0, s,
-                       static_cast<const tfm::tfk::MmrSuccessorChain*>(up.d), (long long)P, old_peaks, new_peaks, paths, statuses);
+                       up.as<tfm::tfk::MmrSuccessorChain>(), (long long)P, old_peaks, new_peaks, paths, statuses);
     HIPCHK(hipGetLastError());
     return TF_OK;
 }
@@ -525,7 +462,7 @@ int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t 
     if (!sweep && !total) return TF_OK;
     int dev = 0;
     TRY(ctx_dev(&dev));
-    Temp table(s);
+    DevTemp table(s);
     if (grows) {
         TRY(table.alloc(5 * wants.size()));
         TRY(mmr_sweep(n, old_peaks, leafs, k, new_peaks, nullptr, wants, table.p, s));
@@ -536,10 +473,10 @@ int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t 
         const int h0 = top_difference(own_idx[p], n);
         desc[p] = {own_off[p] - own_base, out_off[p], H > h0 ? list_at[h0] : 0, (unsigned)h0, (unsigned)(H > h0 ? H - h0 : 0)};
     }
-    Upload up;
-    TRY(up.put(dev, desc.data(), desc.size() * sizeof(desc[0]), s));
+    StagedUpload up(s);
+    TRY(up.put(dev, desc.data(), desc.size() * sizeof(desc[0]), "mmr gather descriptors"));
     hipLaunchKernelGGL(tfm::tfk::mmr_gather_paths_kernel, dim3(grid_for(16 * (long long)P, 256)), dim3(256), 0, s,
-                       static_cast<const tfm::tfk::MmrGatherDesc*>(up.d), (long long)P, own_paths, table.p, out_paths);
+                       up.as<tfm::tfk::MmrGatherDesc>(), (long long)P, own_paths, table.p, out_paths);
     HIPCHK(hipGetLastError());
     return TF_OK;
 }
@@ -547,7 +484,7 @@ int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t 
 // ------------------------------------------------------------------------------------ host flavours
 // Upload the inputs (waiting for each upload: pageable memory), run the _dev form on the thread's stream, copy back, synchronise.
 namespace {
-int up_words(Temp& t, const u64* h, size_t words, hipStream_t s) {
+int up_words(DevTemp& t, const u64* h, size_t words, hipStream_t s) {
     TRY(t.alloc(words));
     return h && words ? h2d(t.p, h, words, s) : TF_OK;
 }
@@ -563,7 +500,7 @@ int mmr_append_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     const size_t np_old = __builtin_popcountll(n), np_new = __builtin_popcountll(n + k);
-    Temp dold(s), dl(s), dnew(s), dpr(s);
+    DevTemp dold(s), dl(s), dnew(s), dpr(s);
     TRY(up_words(dold, old_peaks, 5 * np_old, s));
     TRY(up_words(dl, leafs, 5 * k, s));
     TRY(dnew.alloc(5 * np_new));
@@ -584,15 +521,8 @@ int mmr_bag_peaks_host(const uint64_t* leaf_counts, size_t n_acc, const u64* pea
         np += __builtin_popcountll(leaf_counts[a]);
     }
     if (np && !peaks) return TF_ERR_NULL_POINTER;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    Temp dp(s), dout(s);
-    TRY(up_words(dp, peaks, 5 * np, s));
-    TRY(dout.alloc(5 * n_acc));
-    TRY(mmr_bag_peaks_dev(leaf_counts, n_acc, dp.p, dout.p, s));
-    TRY(d2h(out, dout.p, 5 * n_acc, s));
-    return sync(s);
+    return host_roundtrip(peaks, 5 * np, nullptr, 0, out, 5 * n_acc,
+                          [&](u64* dp, u64*, u64* o, hipStream_t s) { return mmr_bag_peaks_dev(leaf_counts, n_acc, dp, o, s); });
 }
 
 int mmr_verify_host(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, const u64* idx, const u64* digests, const uint64_t* offsets,
@@ -606,13 +536,13 @@ int mmr_verify_host(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, 
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    Temp dpk(s), di(s), dd(s), dpa(s), dst(s);
+    DevTemp dpk(s), di(s), dd(s), dpa(s), dst(s);
     TRY(up_words(dpk, peaks, 5 * n_peaks, s));
     TRY(up_words(di, idx, n, s));
     TRY(up_words(dd, digests, 5 * n, s));
     TRY(up_words(dpa, na ? paths + 5 * offsets[0] : nullptr, 5 * na, s));
     TRY(dst.alloc((n + 1) / 2));
-    TRY(mmr_verify_dev(leaf_count, dpk.p, n_peaks, n, di.p, dd.p, offsets, dpa.p, reinterpret_cast<int*>(dst.p), offsets[0], s));
+    TRY(mmr_verify_dev(leaf_count, dpk.p, n_peaks, n, di.p, dd.p, offsets, dpa.p, dst.as<int>(), offsets[0], s));
     HIPCHK(hipMemcpyAsync(statuses, dst.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
     return sync(s);
 }
@@ -625,7 +555,7 @@ int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, 
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    Temp dpk(s), dl(s), dm(s), dq(s), dmod(s);
+    DevTemp dpk(s), dl(s), dm(s), dq(s), dmod(s);
     TRY(up_words(dpk, peaks, 5 * np, s));
     TRY(up_words(dl, leafs, 5 * M, s));
     TRY(up_words(dm, nm ? mpaths + 5 * moff[0] : nullptr, 5 * nm, s));
@@ -633,7 +563,7 @@ int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, 
     TRY(dmod.alloc((P + 1) / 2));
     u64 dummy = 0;
     TRY(mmr_mutate_dev(leaf_count, peaks ? (np ? dpk.p : &dummy) : nullptr, M, midx, dl.p, moff, dm.p, P, pidx, poff, dq.p,
-                       reinterpret_cast<int*>(dmod.p), M ? moff[0] : 0, P ? poff[0] : 0, s));
+                       dmod.as<int>(), M ? moff[0] : 0, P ? poff[0] : 0, s));
     if (np) TRY(d2h(peaks, dpk.p, 5 * np, s));
     if (nq) TRY(d2h(ppaths + 5 * poff[0], dq.p, 5 * nq, s));
     if (P) HIPCHK(hipMemcpyAsync(modified, dmod.p, P * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -649,7 +579,7 @@ int mmr_successor_new_host(u64 n, const u64* old_peaks, const u64* leafs, size_t
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     const size_t np_old = new_peaks ? __builtin_popcountll(n) : 0, np_new = new_peaks ? __builtin_popcountll(n + k) : 0;
-    Temp dold(s), dl(s), dnew(s), dpa(s);
+    DevTemp dold(s), dl(s), dnew(s), dpa(s);
     TRY(up_words(dold, old_peaks, 5 * np_old, s));
     TRY(up_words(dl, leafs, 5 * k, s));
     TRY(dnew.alloc(5 * np_new));
@@ -676,14 +606,14 @@ int mmr_successor_verify_host(size_t P, const uint64_t* old_counts, const uint64
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    Temp dold(s), dnew(s), dpa(s), dst(s);
+    DevTemp dold(s), dnew(s), dpa(s), dst(s);
     TRY(up_words(dold, no ? old_peaks + 5 * old_off[0] : nullptr, 5 * no, s));
     TRY(up_words(dnew, nn ? new_peaks + 5 * new_off[0] : nullptr, 5 * nn, s));
     TRY(up_words(dpa, na ? paths + 5 * path_off[0] : nullptr, 5 * na, s));
     TRY(dst.alloc((P + 1) / 2));
     u64 dummy = 0;
     TRY(mmr_successor_verify_dev(P, old_counts, new_counts, old_off, no ? dold.p : &dummy, new_off, nn ? dnew.p : &dummy, path_off, na ? dpa.p : &dummy,
-                                 reinterpret_cast<int*>(dst.p), old_off[0], new_off[0], path_off[0], s));
+                                 dst.as<int>(), old_off[0], new_off[0], path_off[0], s));
     HIPCHK(hipMemcpyAsync(statuses, dst.p, P * sizeof(int), hipMemcpyDeviceToHost, s));
     return sync(s);
 }
@@ -704,7 +634,7 @@ int mmr_update_proofs_host(u64 n, const u64* old_peaks, const u64* leafs, size_t
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     const size_t np_old = sweep ? __builtin_popcountll(n) : 0, np_new = new_peaks ? __builtin_popcountll(n + k) : 0;
-    Temp dold(s), dl(s), dq(s), dout(s), dnew(s);
+    DevTemp dold(s), dl(s), dq(s), dout(s), dnew(s);
     TRY(up_words(dold, old_peaks, 5 * np_old, s));
     TRY(up_words(dl, sweep ? leafs : nullptr, sweep ? 5 * k : 0, s));
     TRY(up_words(dq, nq ? own_paths + 5 * own_off[0] : nullptr, 5 * nq, s));

@@ -3,7 +3,7 @@
 // One process drives one or more MI355X devices; all state is per HIP device and guarded by a mutex,
 // kernels are enqueued on the caller's stream, and nothing here synchronises the device except the
 // one-off construction of a twiddle table.  There is no CPU fallback anywhere in this library.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "ntt_kernels.h"
 
 namespace tfi {
@@ -400,8 +400,8 @@ int get_inner_table(DeviceCtx* ctx, int a, bool inverse, int scale_log_n, const 
 
 // T[k*B + b] = w_M^(+-k*b), k < R = 2^a, b < B = M / R
 // Inter-pass twiddles T[k * B + b] = w_M^(k * b), M = 2^log_m = R * B.  Tables up to 2^28 entries (2 GiB) are built once
-// and cached; larger ones (single transforms of 2^29 .. 2^31 points) are stream-ordered temporaries: *temp = true and
-// the caller releases them with hipFreeAsync after the pass that reads them.
+// and cached; larger ones (single transforms of 2^29 .. 2^31 points) are stream-ordered temporaries:
+// *own takes them and gives them back after the passes that read them.
 constexpr int kMaxCachedPostLog = 28;
 // Tables of up to 2^22 words (32 MiB) are cached whatever the budget says: round 6 found that a process which had once transformed
 // 2^27 / 2^28 points (two tables of 1-2 GiB) ran every LATER shape on temporaries -- each call then built its table, and the builder of
@@ -409,17 +409,17 @@ constexpr int kMaxCachedPostLog = 28;
 // evaluation in tests/test_gpu_parity.py::test_one_host_thread_round_robin_never_blocks).  Temporaries are now built entirely on the
 // caller's stream (their split tables by square-and-multiply on the device) and nothing waits.
 constexpr int kAlwaysCachedPostLog = 22;
-int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, bool* temp) {
-    *temp = log_m > kMaxCachedPostLog;
+int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, DevTemp* own) {
+    bool temp = log_m > kMaxCachedPostLog;
     const u64 key = make_key(TAG_POST, log_m, a, inverse, 0);
     std::unique_lock<std::mutex> lk(ctx->mu);
-    if (!*temp) {
+    if (!temp) {
         auto it = ctx->tables.find(key);
         if (it != ctx->tables.end()) {
             *out = it->second;
             return TF_OK;
         }
-        if (log_m > kAlwaysCachedPostLog && ctx->cached_post_bytes + (sizeof(u64) << log_m) > kPostCacheBudget) *temp = true;  // over budget: temporary
+        if (log_m > kAlwaysCachedPostLog && ctx->cached_post_bytes + (sizeof(u64) << log_m) > kPostCacheBudget) temp = true;  // over budget: temporary
     }
     u64 w = root_of_unity_mont(log_m);
     if (inverse) w = gl::mont_inverse(w);
@@ -427,7 +427,7 @@ int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t s
     const int threads = 256;
     const long long blocks = (M + threads - 1) / threads;
     u64* d = nullptr;
-    if (*temp) {
+    if (temp) {
         lk.unlock();
         // hi[i] = w^(i << h), lo[i] = w^i (split_powers), computed ON the device and freed behind the build, all on the caller's stream
         const int h = (log_m + 1) / 2;
@@ -448,6 +448,7 @@ int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t s
             (void)hipFreeAsync(d, stream);
             return hip_fail(e, "build_post_tw_kernel (temporary)", __FILE__, __LINE__);
         }
+        own->adopt(d);
         *out = d;
         return TF_OK;
     }
@@ -677,10 +678,9 @@ void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t 
 // The inter-pass table of a forward first pass with the COLUMN part of a coset evaluation's scaling folded in: T'[k B + b] =
 // w_M^(k b) * offset^b (ntt_col2048_kernel: the factor is constant along a column, so it commutes with the column pass).  One table per
 // (offset, M, R); at most four / kScaledPostBudget bytes stay cached (a prover evaluates on one coset), anything beyond is a
-// stream-ordered temporary the caller frees after the pass.  Built on `stream`; the first build of a cached table synchronises it once.
+// stream-ordered temporary that *own gives back after the pass.  Built on `stream`; the first build of a cached table synchronises it once.
 constexpr size_t kScaledPostBudget = size_t(512) << 20;
-int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipStream_t stream, const u64** out, bool* temp) {
-    *temp = false;
+int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipStream_t stream, const u64** out, DevTemp* own) {
     const auto key = std::make_pair(offset_raw, (u64(log_m) << 8) | u64(a));
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
@@ -692,16 +692,11 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
     }
     const long long M = 1ll << log_m, B = M >> a;
     const u64* T = nullptr;
-    bool t_temp = false;
-    int rc = get_post_table(ctx, log_m, a, false, stream, &T, &t_temp);
-    if (rc) return rc;
+    DevTemp t_own(stream);  // (given back behind the build below)
+    TRY(get_post_table(ctx, log_m, a, false, stream, &T, &t_own));
     const u64* S = nullptr;
     bool s_temp = false;
-    rc = get_pow_table(ctx, offset_raw, (size_t)B, stream, &S, &s_temp);
-    if (rc) {
-        if (t_temp) (void)hipFreeAsync(const_cast<u64*>(T), stream);
-        return rc;
-    }
+    TRY(get_pow_table(ctx, offset_raw, (size_t)B, stream, &S, &s_temp));
     bool cache;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
@@ -714,7 +709,6 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
         e = hipGetLastError();
         if (e == hipSuccess && cache) e = hipStreamSynchronize(stream);  // other streams may use the cached table from now on
     }
-    if (t_temp) (void)hipFreeAsync(const_cast<u64*>(T), stream);
     release_pow_table(ctx, S, s_temp, stream);
     if (e != hipSuccess) {
         if (d) { if (cache) (void)hipFree(d); else (void)hipFreeAsync(d, stream); }
@@ -731,7 +725,7 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
             ctx->cached_scaled_post_bytes += size_t(M) * sizeof(u64);
         }
     } else {
-        *temp = true;
+        own->adopt(d);
     }
     *out = d;
     return TF_OK;
@@ -1609,27 +1603,18 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
         if (rc) return rc;
     }
     const u64* post[3] = {nullptr, nullptr, nullptr};
-    bool post_temp[3] = {false, false, false};
     const u64* post_u = nullptr;  // the plain table beside a scaled post[0] (one-workgroup scaling first pass)
-    bool post_u_temp = false;
-    auto release_tables = [&]() {
-        for (int i = 0; i < 3; ++i)
-            if (post_temp[i] && post[i]) (void)hipFreeAsync(const_cast<u64*>(post[i]), stream);
-        if (post_u_temp && post_u) (void)hipFreeAsync(const_cast<u64*>(post_u), stream);
-    };
+    // tables too large to cache: given back on the caller's stream when the call returns, behind the join of the tile streams
+    DevTemp post_own[3] = {DevTemp(stream), DevTemp(stream), DevTemp(stream)}, post_u_own(stream);
     {
         int rest = log_n;
         for (int i = 0; i + 1 < P; ++i) {
             if (i == 0 && c8 && pre_scale) {
                 // the scaled table for every thread's own row, the plain one for the rows all threads share (ntt_col2048_kernel, TF_C8_UV)
-                rc = get_scaled_post_table(ctx, rest, a[i], *coset_offset, stream, &post[i], &post_temp[i]);
-                if (!rc) rc = get_post_table(ctx, rest, a[i], inverse, stream, &post_u, &post_u_temp);
+                TRY(get_scaled_post_table(ctx, rest, a[i], *coset_offset, stream, &post[i], &post_own[i]));
+                TRY(get_post_table(ctx, rest, a[i], inverse, stream, &post_u, &post_u_own));
             } else {
-                rc = get_post_table(ctx, rest, a[i], inverse, stream, &post[i], &post_temp[i]);
-            }
-            if (rc) {
-                release_tables();
-                return rc;
+                TRY(get_post_table(ctx, rest, a[i], inverse, stream, &post[i], &post_own[i]));
             }
             rest -= a[i];
         }
@@ -1667,11 +1652,7 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
     u64* scratch = nullptr;
     DeviceCtx::ScratchBlock sblk;
     {
-        rc = scratch_acquire(ctx, size_t(K) * tb * poly_bytes, stream, &sblk);
-        if (rc) {
-            release_tables();
-            return rc;
-        }
+        TRY(scratch_acquire(ctx, size_t(K) * tb * poly_bytes, stream, &sblk));
         scratch = sblk.p;
     }
     if (K > 1) {
@@ -1685,7 +1666,6 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
             for (int i = 0; i < K; ++i)
                 if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
             scratch_release(ctx, sblk, stream);
-            release_tables();
             return hip_fail(e, "fork into the tile streams", __FILE__, __LINE__);
         }
     }
@@ -1802,14 +1782,11 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
         if (je != hipSuccess) {
             (void)hipDeviceSynchronize();  // cannot order the release after the side streams any other way
             scratch_release(ctx, sblk, stream);
-            release_tables();
             return hip_fail(je, "join of the tile streams", __FILE__, __LINE__);
         }
     }
     scratch_release(ctx, sblk, stream);
-    release_tables();
-    if (rc) return rc;
-    return TF_OK;
+    return rc;
 }
 
 int ntt_dev(u64* d_x, size_t n, size_t batch, int L, int inverse, void* stream) {

@@ -1,6 +1,6 @@
 // tf_poly.hip -- the callers on either side of the hot path: orchestration over poly_kernels.h and the
 // transforms of tf_ntt.hip.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "poly_kernels.h"
 
 namespace tfi {
@@ -80,41 +80,38 @@ int poly_mul_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out, siz
     rc = current_ctx(&ctx);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    u64* tmp = nullptr;
     const size_t half = batch * order * size_t(L);
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), 2 * half * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(poly_mul)", __FILE__, __LINE__);
+    DevTemp work(s);
+    TRY(work.alloc(2 * half, "poly_mul"));
+    u64* const tmp = work.p;
     static const bool no_fuse = ab_env("TF_POLY_MUL_NO_FUSE") != nullptr;  // A/B switch
     bool copied = false;
     if (order > 16 && !no_fuse) {
         // zero padding happens in the first pass of each forward transform (rows beyond the coefficients read as zero);
         // over BFieldElement the pointwise product rides on the inverse transform's first load
-        rc = run_ntt(ctx, a, tmp, a_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s);
-        if (!rc) rc = run_ntt(ctx, b, tmp + half, b_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)nb, s);
+        TRY(run_ntt(ctx, a, tmp, a_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s));
+        TRY(run_ntt(ctx, b, tmp + half, b_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)nb, s));
         const bool trunc = can_truncate(order, L);  // the inverse's last pass writes the n_out coefficients straight to `out`
         u64* dst = trunc ? out : tmp;
         const long long dst_bs = trunc ? (long long)n_out * L : (long long)order * L;
-        if (!rc && L == 1) {
-            rc = run_ntt(ctx, tmp, dst, (long long)order, dst_bs, order, batch, 1, true, nullptr, -1, s, nullptr, 1, tmp + half,
-                         trunc ? (long long)n_out : -1);
-        } else if (!rc) {
-            rc = hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s);
-            if (!rc) rc = run_ntt(ctx, tmp, dst, (long long)order * L, dst_bs, order, batch, L, true, nullptr, -1, s, nullptr, 1, nullptr,
-                                  trunc ? (long long)n_out : -1);
+        if (L == 1) {
+            TRY(run_ntt(ctx, tmp, dst, (long long)order, dst_bs, order, batch, 1, true, nullptr, -1, s, nullptr, 1, tmp + half,
+                        trunc ? (long long)n_out : -1));
+        } else {
+            TRY(hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s));
+            TRY(run_ntt(ctx, tmp, dst, (long long)order * L, dst_bs, order, batch, L, true, nullptr, -1, s, nullptr, 1, nullptr,
+                        trunc ? (long long)n_out : -1));
         }
         copied = trunc;
     } else {
-        rc = pad_copy(a, tmp, (long long)na * L, (long long)order * L, (long long)batch, s, a_bs);
-        if (!rc) rc = pad_copy(b, tmp + half, (long long)nb * L, (long long)order * L, (long long)batch, s, b_bs);
-        if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, 2 * batch, L, false, nullptr, -1, s);
-        if (!rc) rc = hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s);
-        if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s);
+        TRY(pad_copy(a, tmp, (long long)na * L, (long long)order * L, (long long)batch, s, a_bs));
+        TRY(pad_copy(b, tmp + half, (long long)nb * L, (long long)order * L, (long long)batch, s, b_bs));
+        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, 2 * batch, L, false, nullptr, -1, s));
+        TRY(hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s));
+        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s));
     }
-    if (!rc && !copied) rc = pad_copy(tmp, out, (long long)order * L, (long long)n_out * L, (long long)batch, s);
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    if (!copied) TRY(pad_copy(tmp, out, (long long)order * L, (long long)n_out * L, (long long)batch, s));
+    return work.release();
 }
 
 // fast_multiply of `batch` polynomials by ONE polynomial b (a table of numerators times the same zerofier; polynomial.rs:900-932
@@ -135,23 +132,20 @@ int poly_mul_shared_dev(const u64* a, size_t na, size_t batch, const u64* b, siz
     rc = current_ctx(&ctx);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    u64* tmp = nullptr;  // batch transforms of a, one of b
     const size_t row = order * size_t(L);
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), (batch + 1) * row * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(poly_mul_shared)", __FILE__, __LINE__);
+    DevTemp work(s);  // batch transforms of a, one of b
+    TRY(work.alloc((batch + 1) * row, "poly_mul_shared"));
+    u64* const tmp = work.p;
     u64* bh = tmp + batch * row;
-    rc = run_ntt(ctx, a, tmp, (long long)na * L, (long long)row, order, batch, L, false, nullptr, (long long)na, s);
-    if (!rc) rc = run_ntt(ctx, b, bh, (long long)nb * L, (long long)row, order, 1, L, false, nullptr, (long long)nb, s);
-    if (!rc) rc = L == 1 ? launch_1d<1>(tfk::product_bcast_kernel<1>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)bh, tmp, (long long)order,
-                                        (long long)(batch * order))
-                         : launch_1d<3>(tfk::product_bcast_kernel<3>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)bh, tmp, (long long)order,
-                                        (long long)(batch * order));
-    if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)row, (long long)row, order, batch, L, true, nullptr, -1, s);
-    if (!rc) rc = pad_copy(tmp, out, (long long)row, (long long)(n_out * L), (long long)batch, s);
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    TRY(run_ntt(ctx, a, tmp, (long long)na * L, (long long)row, order, batch, L, false, nullptr, (long long)na, s));
+    TRY(run_ntt(ctx, b, bh, (long long)nb * L, (long long)row, order, 1, L, false, nullptr, (long long)nb, s));
+    TRY(L == 1 ? launch_1d<1>(tfk::product_bcast_kernel<1>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)bh, tmp, (long long)order,
+                              (long long)(batch * order))
+               : launch_1d<3>(tfk::product_bcast_kernel<3>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)bh, tmp, (long long)order,
+                              (long long)(batch * order)));
+    TRY(run_ntt(ctx, tmp, tmp, (long long)row, (long long)row, order, batch, L, true, nullptr, -1, s));
+    TRY(pad_copy(tmp, out, (long long)row, (long long)(n_out * L), (long long)batch, s));
+    return work.release();
 }
 
 // Polynomial::fast_square (polynomial.rs:780-798): one forward transform instead of two.
@@ -167,37 +161,33 @@ int poly_square_dev(const u64* a, size_t na, u64* out, size_t batch, int L, void
     rc = current_ctx(&ctx);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    u64* tmp = nullptr;
-    const size_t words = batch * order * size_t(L);
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), words * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(poly_square)", __FILE__, __LINE__);
+    DevTemp work(s);
+    TRY(work.alloc(batch * order * size_t(L), "poly_square"));
+    u64* const tmp = work.p;
     static const bool no_fuse = ab_env("TF_POLY_MUL_NO_FUSE") != nullptr;  // A/B switch
     bool copied = false;
     if (order > 16 && !no_fuse) {
-        rc = run_ntt(ctx, a, tmp, (long long)na * L, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s);
+        TRY(run_ntt(ctx, a, tmp, (long long)na * L, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s));
         const bool trunc = can_truncate(order, L);
         u64* dst = trunc ? out : tmp;
         const long long dst_bs = trunc ? (long long)n_out * L : (long long)order * L;
-        if (!rc && L == 1) {
-            rc = run_ntt(ctx, tmp, dst, (long long)order, dst_bs, order, batch, 1, true, nullptr, -1, s, nullptr, 1, tmp,
-                         trunc ? (long long)n_out : -1);
-        } else if (!rc) {
-            rc = hadamard_dev(tmp, tmp, tmp, batch * order, L, s);
-            if (!rc) rc = run_ntt(ctx, tmp, dst, (long long)order * L, dst_bs, order, batch, L, true, nullptr, -1, s, nullptr, 1, nullptr,
-                                  trunc ? (long long)n_out : -1);
+        if (L == 1) {
+            TRY(run_ntt(ctx, tmp, dst, (long long)order, dst_bs, order, batch, 1, true, nullptr, -1, s, nullptr, 1, tmp,
+                        trunc ? (long long)n_out : -1));
+        } else {
+            TRY(hadamard_dev(tmp, tmp, tmp, batch * order, L, s));
+            TRY(run_ntt(ctx, tmp, dst, (long long)order * L, dst_bs, order, batch, L, true, nullptr, -1, s, nullptr, 1, nullptr,
+                        trunc ? (long long)n_out : -1));
         }
         copied = trunc;
     } else {
-        rc = pad_copy(a, tmp, (long long)na * L, (long long)order * L, (long long)batch, s);
-        if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, false, nullptr, -1, s);
-        if (!rc) rc = hadamard_dev(tmp, tmp, tmp, batch * order, L, s);
-        if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s);
+        TRY(pad_copy(a, tmp, (long long)na * L, (long long)order * L, (long long)batch, s));
+        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, false, nullptr, -1, s));
+        TRY(hadamard_dev(tmp, tmp, tmp, batch * order, L, s));
+        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s));
     }
-    if (!rc && !copied) rc = pad_copy(tmp, out, (long long)order * L, (long long)n_out * L, (long long)batch, s);
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    if (!copied) TRY(pad_copy(tmp, out, (long long)order * L, (long long)n_out * L, (long long)batch, s));
+    return work.release();
 }
 
 // Low-degree extension: values on {offset_in * w_n^i} -> values on {offset_out * w_m^i}, m >= n
@@ -214,15 +204,11 @@ int lde_dev(const u64* values, size_t n, u64 offset_in, u64* out, size_t m, u64 
         HIPCHK(hipMemsetAsync(out, 0, m * batch * size_t(L) * sizeof(u64), s));
         return TF_OK;
     }
-    u64* coeffs = nullptr;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&coeffs), batch * n * size_t(L) * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(lde)", __FILE__, __LINE__);
-    rc = coset_interp_dev(values, n, offset_in, coeffs, batch, L, s);
-    if (!rc) rc = coset_eval_dev(coeffs, n, offset_out, out, m, batch, L, s);
-    hipError_t e2 = hipFreeAsync(coeffs, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    DevTemp coeffs(s);
+    TRY(coeffs.alloc(batch * n * size_t(L), "lde"));
+    TRY(coset_interp_dev(values, n, offset_in, coeffs.p, batch, L, s));
+    TRY(coset_eval_dev(coeffs.p, n, offset_out, out, m, batch, L, s));
+    return coeffs.release();
 }
 
 
@@ -527,29 +513,25 @@ int tree_batch_evaluate(DeviceCtx* ctx, const ZerofierTree& T, const u64* points
     static const size_t slab_elems = [] { const char* e = ab_env("TF_TREE_UNIT_SLAB"); const long long v = e ? atoll(e) : 0; return v > 0 ? (size_t)v : (size_t(1) << 25); }();
     const size_t slab = std::max<size_t>(1, std::min<size_t>(units, slab_elems / (size_t)M));
     // padded coefficients (units M) + values (units M) + walk work (8 slab M)
-    u64* tmp = nullptr;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), (2 * units + (size_t)kTreeWorkArrays * slab) * ML * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(zerofier tree walk)", __FILE__, __LINE__);
-    u64* padded = tmp;
+    DevTemp tmp(s);
+    TRY(tmp.alloc((2 * units + (size_t)kTreeWorkArrays * slab) * ML, "zerofier tree walk"));
+    u64* padded = tmp.p;
     u64* vals = padded + units * ML;
     u64* work = vals + units * ML;
-    int rc = pad_copy(coeffs, padded, (long long)(n_coeffs * L), (long long)(chunks * ML), (long long)batch, s, (long long)poly_stride);
-    for (size_t u0 = 0; u0 < units && !rc; u0 += slab) {
+    TRY(pad_copy(coeffs, padded, (long long)(n_coeffs * L), (long long)(chunks * ML), (long long)batch, s, (long long)poly_stride));
+    for (size_t u0 = 0; u0 < units; u0 += slab) {
         const size_t nu = std::min(slab, units - u0);
-        rc = zerofier_tree_evaluate<L>(ctx, T, padded + u0 * ML, points, (long long)n_points, vals + u0 * ML, work, s, (long long)nu);
+        TRY(zerofier_tree_evaluate<L>(ctx, T, padded + u0 * ML, points, (long long)n_points, vals + u0 * ML, work, s, (long long)nu));
     }
     int log_m = 0;
     while ((1ll << log_m) < M) ++log_m;
-    for (size_t b0 = 0; b0 < batch && !rc; b0 += 65535) {  // grid.y = polynomial
+    for (size_t b0 = 0; b0 < batch; b0 += 65535) {  // grid.y = polynomial
         const unsigned nb = (unsigned)std::min<size_t>(65535, batch - b0);
         hipLaunchKernelGGL(tfk::chunk_combine_kernel<L>, dim3((unsigned)((n_points + 255) / 256), nb), dim3(256), 0, s, (const u64*)(vals + b0 * chunks * ML),
                            M, (int)chunks, points, (long long)n_points, log_m, out + b0 * n_points * L);
-        if (hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
+        if (hipGetLastError() != hipSuccess) return TF_ERR_HIP;
     }
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    return tmp.release();
 }
 
 template <int L>
@@ -565,18 +547,13 @@ int batch_evaluate_tree_t(const u64* coeffs, size_t n_coeffs, size_t poly_stride
     T.h = h;
     // the tree (6 h M) and the build's work space (8 M); the walks bring their own
     const size_t words = (size_t)(kTreeLevelArrays * h + kTreeWorkArrays) * (size_t)M * L;
-    u64* arena = nullptr;
     DeviceCtx* ctx = nullptr;
-    int rc = current_ctx(&ctx);
-    if (rc) return rc;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&arena), words * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(zerofier tree)", __FILE__, __LINE__);
-    rc = zerofier_tree_build<L>(ctx, points, (long long)n_points, &T, arena, arena + (size_t)(kTreeLevelArrays * h) * M * L, s);
-    if (!rc) rc = tree_batch_evaluate<L>(ctx, T, points, n_points, coeffs, n_coeffs, poly_stride, batch, out, s);
-    hipError_t e2 = hipFreeAsync(arena, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    TRY(current_ctx(&ctx));
+    DevTemp arena(s);
+    TRY(arena.alloc(words, "zerofier tree"));
+    TRY(zerofier_tree_build<L>(ctx, points, (long long)n_points, &T, arena.p, arena.p + (size_t)(kTreeLevelArrays * h) * M * L, s));
+    TRY(tree_batch_evaluate<L>(ctx, T, points, n_points, coeffs, n_coeffs, poly_stride, batch, out, s));
+    return arena.release();
 }
 
 // ------------------------------------------------------------------------------------ batch evaluation
@@ -695,19 +672,15 @@ int padded_tree_build(const u64* points, size_t n_points, size_t extra_words, Pa
         return TF_OK;
     }
     DeviceCtx* ctx = nullptr;
-    int rc = current_ctx(&ctx);
-    if (rc) return rc;
-    u64* work = nullptr;
-    e = pool_malloc_async(reinterpret_cast<void**>(&work), work_words * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(zerofier tree build)", __FILE__, __LINE__);
-    rc = zerofier_tree_build<L>(ctx, points, (long long)n_points, &pt->T, pt->arena, work, s);
+    TRY(current_ctx(&ctx));
+    DevTemp work(s);
+    TRY(work.alloc(work_words, "zerofier tree build"));
+    TRY(zerofier_tree_build<L>(ctx, points, (long long)n_points, &pt->T, pt->arena, work.p, s));
     // the root from the transforms of the two nodes of level h - 1 (d = M / 2, order M)
     const long long d = M / 2;
-    if (!rc) rc = launch_1d<L>(tfk::zerofier_pointwise_kernel<L>, 2 * d, s, (const u64*)pt->T.That[h - 1], pt->root_tail, d, (long long)1);
-    if (!rc) rc = run_ntt(ctx, pt->root_tail, pt->root_tail, 2 * d * L, 2 * d * L, (size_t)(2 * d), 1, L, true, nullptr, -1, s);
-    hipError_t e2 = hipFreeAsync(work, s);
-    if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return rc;
+    TRY(launch_1d<L>(tfk::zerofier_pointwise_kernel<L>, 2 * d, s, (const u64*)pt->T.That[h - 1], pt->root_tail, d, (long long)1));
+    TRY(run_ntt(ctx, pt->root_tail, pt->root_tail, 2 * d * L, 2 * d * L, (size_t)(2 * d), 1, L, true, nullptr, -1, s));
+    return work.release();
 }
 
 int padded_tree_free(PaddedTree* pt, hipStream_t s, int rc) {
@@ -747,34 +720,28 @@ int tree_inverse_weights(DeviceCtx* ctx, const PaddedTree& pt, const u64* domain
                          int* sticky = nullptr) {
     const long long M = pt.T.M;
     const size_t ML = (size_t)M * L, n = pt.n;
-    u64* tmp = nullptr;  // derivative (M), its values (M), walk work (8 M), flag
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), ((2 + kTreeWorkArrays) * ML + 2) * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(interpolation weights)", __FILE__, __LINE__);
-    u64* deriv = tmp;
+    DevTemp tmp(s);  // derivative (M), its values (M), walk work (8 M), flag
+    TRY(tmp.alloc((2 + kTreeWorkArrays) * ML + 2, "interpolation weights"));
+    u64* deriv = tmp.p;
     u64* dz = deriv + ML;
     u64* work = dz + ML;
     int* flag = reinterpret_cast<int*>(work + (size_t)kTreeWorkArrays * ML);
-    int rc = launch_1d<L>(tfk::zerofier_derivative_kernel<L>, M, s, (const u64*)pt.root_tail, M, (long long)n, deriv);
-    if (!rc) rc = zerofier_tree_evaluate<L>(ctx, pt.T, deriv, domain, (long long)n, dz, work, s);
-    if (!rc) {
-        e = hipMemsetAsync(flag, 0, sizeof(int), s);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync", __FILE__, __LINE__);
-    }
-    if (!rc) rc = launch_1d<L>(tfk::fe_inverse_kernel<L>, (long long)n, s, (const u64*)dz, (long long)n, winv, flag);
-    if (!rc && d_status) {
+    TRY(launch_1d<L>(tfk::zerofier_derivative_kernel<L>, M, s, (const u64*)pt.root_tail, M, (long long)n, deriv));
+    TRY(zerofier_tree_evaluate<L>(ctx, pt.T, deriv, domain, (long long)n, dz, work, s));
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s));
+    TRY(launch_1d<L>(tfk::fe_inverse_kernel<L>, (long long)n, s, (const u64*)dz, (long long)n, winv, flag));
+    if (d_status) {
         hipLaunchKernelGGL(tfk::status_merge_kernel, dim3(1), dim3(1), 0, s, (const int*)flag, d_status, (int)TF_ERR_INVERSE_OF_ZERO, (int)TF_ERR_INVERSE_OF_ZERO);
         if (sticky) hipLaunchKernelGGL(tfk::status_merge_kernel, dim3(1), dim3(1), 0, s, (const int*)flag, sticky, 1, 1);
-        if (hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
-    } else if (!rc) {
+        if (hipGetLastError() != hipSuccess) return TF_ERR_HIP;
+    } else {
         int host_flag = 0;
-        e = hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s);
+        hipError_t e = hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = hip_fail(e, "interpolate: weight check", __FILE__, __LINE__);
-        else if (host_flag) rc = TF_ERR_INVERSE_OF_ZERO;  // Z'(x_i) = 0: a repeated domain point
+        if (e != hipSuccess) return hip_fail(e, "interpolate: weight check", __FILE__, __LINE__);
+        if (host_flag) return TF_ERR_INVERSE_OF_ZERO;  // Z'(x_i) = 0: a repeated domain point
     }
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return rc;
+    return tmp.release();
 }
 
 // The walk up: `rows` value rows -> rows x n coefficients, given the tree and the inverse weights.
@@ -787,10 +754,9 @@ int tree_interpolate_rows(DeviceCtx* ctx, const PaddedTree& pt, const u64* domai
     const int h = pt.T.h;
     // rows go up the tree in slabs: targets, two interpolant levels and the children's transforms (2 M) per row
     const size_t slab = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(rows, 32768), (size_t(1) << 26) / ML));
-    u64* tmp = nullptr;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), 5 * slab * ML * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(interpolation rows)", __FILE__, __LINE__);
-    u64* targets = tmp;
+    DevTemp tmp(s);
+    TRY(tmp.alloc(5 * slab * ML, "interpolation rows"));
+    u64* targets = tmp.p;
     u64* na = targets + slab * ML;
     u64* nb = na + slab * ML;
     u64* Nh = nb + slab * ML;
@@ -862,9 +828,8 @@ int tree_interpolate_rows(DeviceCtx* ctx, const PaddedTree& pt, const u64* domai
             if (hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
         }
     }
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return rc;
+    if (rc) return rc;
+    return tmp.release();
 }
 
 template <int L>
@@ -1132,12 +1097,10 @@ int barycentric_dev(const u64* codewords, size_t n, size_t batch, int cw_width, 
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long per_chunk = (long long)tfk::kBaryPerThread * 256, n_chunks = ((long long)n + per_chunk - 1) / per_chunk;
-    u64* tmp = nullptr;  // weights (3 n) + partial sums ((batch + 1) n_chunks 3)
-    const size_t words = 3 * n + 3 * (batch + 1) * (size_t)n_chunks;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), words * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(barycentric)", __FILE__, __LINE__);
-    u64* w = tmp;
-    u64* partial = tmp + 3 * n;
+    DevTemp tmp(s);  // weights (3 n) + partial sums ((batch + 1) n_chunks 3)
+    TRY(tmp.alloc(3 * n + 3 * (batch + 1) * (size_t)n_chunks, "barycentric"));
+    u64* w = tmp.p;
+    u64* partial = tmp.p + 3 * n;
     const int log_n = ilog2(n);
     const u64 omega = root_of_unity_mont(log_n);
     hipLaunchKernelGGL(tfk::barycentric_weights_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, (long long)n, log_n, omega, gl::mont_pow(omega, 256),
@@ -1146,23 +1109,18 @@ int barycentric_dev(const u64* codewords, size_t n, size_t batch, int cw_width, 
         static const int rows_env = [] { const char* e = ab_env("TF_BARY_ROWS"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= tfk::kBaryRows) ? v : 0; }();
         const int rpb = rows_env ? rows_env : 2;  // rows per block (A/B: tools/barycentric_bench.py; 1 / 2 / 4 within 3 % of each other)
         const long long row_groups = ((long long)batch + 1 + rpb - 1) / rpb;  // the denominator is row `batch`
-        if (row_groups > 65535) rc = TF_ERR_LEN_TOO_LARGE;  // more than 65 534 codewords in one call
-        else if (cw_width == 1)
+        if (row_groups > 65535) return TF_ERR_LEN_TOO_LARGE;  // more than 65 534 codewords in one call
+        if (cw_width == 1)
             hipLaunchKernelGGL(tfk::barycentric_partial_kernel<1>, dim3((unsigned)n_chunks, (unsigned)row_groups), dim3(256), 0, s, codewords,
                                (const u64*)w, (long long)n, (long long)batch, partial, rpb);
         else
             hipLaunchKernelGGL(tfk::barycentric_partial_kernel<3>, dim3((unsigned)n_chunks, (unsigned)row_groups), dim3(256), 0, s, codewords,
                                (const u64*)w, (long long)n, (long long)batch, partial, rpb);
-        if (!rc && hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
+        if (hipGetLastError() != hipSuccess) return TF_ERR_HIP;
     }
-    if (!rc) {
-        hipLaunchKernelGGL(tfk::barycentric_finish_kernel, dim3((unsigned)batch), dim3(64), 0, s, (const u64*)partial, n_chunks, (long long)batch, out);
-        if (hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
-    }
-    hipError_t e2 = hipFreeAsync(tmp, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    hipLaunchKernelGGL(tfk::barycentric_finish_kernel, dim3((unsigned)batch), dim3(64), 0, s, (const u64*)partial, n_chunks, (long long)batch, out);
+    if (hipGetLastError() != hipSuccess) return TF_ERR_HIP;
+    return tmp.release();
 }
 
 // Polynomial::<BFieldElement>::clean_divide (polynomial.rs:2358-2411): a / b for b | a, by pointwise division on the coset
@@ -1186,10 +1144,10 @@ int clean_divide_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out,
     rc = current_ctx(&ctx);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    u64* tmp = nullptr;  // rows 0 .. batch-1: the dividends, row `batch`: the divisor; order XFieldElements each
     const size_t half = order * 3;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&tmp), ((batch + 1) * half + 2) * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(clean_divide)", __FILE__, __LINE__);
+    DevTemp work(s);  // rows 0 .. batch-1: the dividends, row `batch`: the divisor; order XFieldElements each
+    TRY(work.alloc((batch + 1) * half + 2, "clean_divide"));
+    u64* const tmp = work.p;
     u64* div = tmp + batch * half;
     int* flag = reinterpret_cast<int*>(tmp + (batch + 1) * half);
     // The division coset is X * <w_order> with X = x, the reference's choice (:2383).  A divisor with a root ON that coset (e.g.
@@ -1205,7 +1163,7 @@ int clean_divide_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out,
         rc = TF_OK;
     }
     const unsigned blocks = (unsigned)((order + 255) / 256);
-    e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync", __FILE__, __LINE__);
     if (!rc) {
         hipLaunchKernelGGL(tfk::lift_scale_kernel, dim3(blocks, (unsigned)batch), dim3(256), 0, s, a, (long long)na, (long long)order, tmp, X[0], X[1], X[2]);
@@ -1238,10 +1196,8 @@ int clean_divide_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out,
     }
     if (rc != TF_ERR_INVERSE_OF_ZERO || d_status) break;         // (the asynchronous variant cannot look at the flag: one coset)
     }
-    hipError_t e2 = hipFreeAsync(tmp, s);
     if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    return work.release();
 }
 
 // Polynomial::{coset_extrapolate, batch_coset_extrapolate} (polynomial.rs:2117-2331): the values, at `points`, of the
@@ -1260,15 +1216,11 @@ int coset_extrapolate_dev(u64 offset_raw, const u64* codewords, size_t n, size_t
     DeviceCtx* ctx = nullptr;
     rc = current_ctx(&ctx);
     if (rc) return rc;
-    u64* coeffs = nullptr;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&coeffs), batch * n * size_t(L) * sizeof(u64), s);
-    if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(coset_extrapolate)", __FILE__, __LINE__);
-    rc = coset_interp_dev(codewords, n, offset_raw, coeffs, batch, L, s);
-    if (!rc) rc = batch_evaluate_dev(coeffs, n, n * size_t(L), batch, points, n_points, out, L, s);
-    hipError_t e2 = hipFreeAsync(coeffs, s);
-    if (rc) return rc;
-    if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    DevTemp coeffs(s);
+    TRY(coeffs.alloc(batch * n * size_t(L), "coset_extrapolate"));
+    TRY(coset_interp_dev(codewords, n, offset_raw, coeffs.p, batch, L, s));
+    TRY(batch_evaluate_dev(coeffs.p, n, n * size_t(L), batch, points, n_points, out, L, s));
+    return coeffs.release();
 }
 
 // ------------------------------------------------------------------------------------ authentication structures

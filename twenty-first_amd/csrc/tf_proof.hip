@@ -1,12 +1,12 @@
 // tf_proof.hip -- launcher of the batched Merkle inclusion-proof verifier (proof_kernels.h): MerkleTreeInclusionProof::try_verify /
 // into_authentication_paths, util_types/merkle_tree.rs:683-931.
-#include "tf_internal.h"
+#include "tf_temp.h"
 
 #include <type_traits>
 
 // The kernels read the Tip5 round constants from __constant__ memory, and every translation unit is its own code object with its own
 // copy of tip5_kernels.h's constants: this unit includes the device functions in a namespace of its own (no second host-side symbol
-// tfp::tfk::g_tip5) and uploads its copy once per device (ensure_proof_consts).
+// tfp::tfk::g_tip5) and uploads its copy once per device (Tip5ConstsOnce).
 namespace tfp {
 #include "proof_kernels.h"
 }
@@ -55,19 +55,7 @@ void stage_release(int dev, Staging st, hipStream_t s) {
 }
 
 namespace {
-std::mutex g_consts_mu;
-bool g_consts_ready[kMaxDevices];
-
-int ensure_proof_consts(int dev) {
-    std::lock_guard<std::mutex> lk(g_consts_mu);
-    if (g_consts_ready[dev]) return TF_OK;
-    tfp::tfk::Tip5Consts c;
-    for (int i = 0; i < 80; ++i) c.rc[i] = gl::to_mont(kRoundConstants[i]);
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(tfp::tfk::g_tip5), &c, sizeof(c)));
-    HIPCHK(hipDeviceSynchronize());
-    g_consts_ready[dev] = true;
-    return TF_OK;
-}
+Tip5ConstsOnce g_consts;
 
 // threads of an LDS-route workgroup: a row per distinct leaf at the widest level, 256 .. 1024
 int lds_threads(long long max_k) {
@@ -91,10 +79,8 @@ int merkle_proofs_dev(const uint32_t* heights, size_t n, const uint64_t* leaf_of
     if (auth_offsets[n] > auth_offsets[0] && !d_auth) return TF_ERR_NULL_POINTER;
     if (paths ? (path_words && !d_paths) : !d_roots) return TF_ERR_NULL_POINTER;
 
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    const int dev = (int)(ctx - g_ctx);
-    TRY(ensure_proof_consts(dev));
+    int dev = 0;
+    TRY(g_consts.ensure(&dev, tfp::tfk::g_tip5));
 
     // descriptors: LDS-route proofs first, then the scratch route
     std::vector<tfp::tfk::ProofDesc> small, large;
@@ -127,35 +113,17 @@ int merkle_proofs_dev(const uint32_t* heights, size_t n, const uint64_t* leaf_of
             small.push_back(dsc);
         }
     }
-    const size_t desc_bytes = n * sizeof(tfp::tfk::ProofDesc);
-
-    Staging st;
-    TRY(stage_acquire(dev, desc_bytes, &st));
-    std::memcpy(st.p, small.data(), small.size() * sizeof(tfp::tfk::ProofDesc));
-    std::memcpy(static_cast<char*>(st.p) + small.size() * sizeof(tfp::tfk::ProofDesc), large.data(), large.size() * sizeof(tfp::tfk::ProofDesc));
-    tfp::tfk::ProofDesc* d_desc = nullptr;
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&d_desc), desc_bytes, s);
-    if (e != hipSuccess) {
-        stage_release(dev, st, s);
-        return hip_fail(e, "pool_malloc_async(proof descriptors)", __FILE__, __LINE__);
-    }
-    e = hipMemcpyAsync(d_desc, st.p, desc_bytes, hipMemcpyHostToDevice, s);
-    stage_release(dev, st, s);
-    if (e != hipSuccess) {
-        (void)hipFreeAsync(d_desc, s);
-        return hip_fail(e, "hipMemcpyAsync(proof descriptors)", __FILE__, __LINE__);
-    }
-    u64* d_scratch = nullptr;
-    if (scratch_words) {
-        e = pool_malloc_async(reinterpret_cast<void**>(&d_scratch), scratch_words * sizeof(u64), s);
-        if (e != hipSuccess) {
-            (void)hipFreeAsync(d_desc, s);
-            return hip_fail(e, "pool_malloc_async(proof work space)", __FILE__, __LINE__);
-        }
-    }
-    if (!small.empty()) {
+    const size_t n_small = small.size();
+    small.insert(small.end(), large.begin(), large.end());
+    StagedUpload up(s);
+    TRY(up.put(dev, small.data(), n * sizeof(tfp::tfk::ProofDesc), "proof descriptors"));
+    const tfp::tfk::ProofDesc* d_desc = up.as<tfp::tfk::ProofDesc>();
+    DevTemp scratch(s);
+    TRY(scratch.alloc(scratch_words, "proof work space"));
+    u64* const d_scratch = scratch.p;
+    if (n_small) {
         const size_t lds = (size_t)tfp::tfk::proof_words(max_small_k) * sizeof(u64);
-        const dim3 grid((unsigned)small.size()), block((unsigned)lds_threads(max_small_k));
+        const dim3 grid((unsigned)n_small), block((unsigned)lds_threads(max_small_k));
         if (paths)
             hipLaunchKernelGGL((tfp::tfk::merkle_proof_kernel<true, true>), grid, block, lds, s, d_desc, d_leaf_indices, d_leaf_digests, d_auth,
                                d_roots, nullptr, d_statuses, d_paths);
@@ -166,15 +134,13 @@ int merkle_proofs_dev(const uint32_t* heights, size_t n, const uint64_t* leaf_of
     if (!large.empty()) {
         const dim3 grid((unsigned)large.size()), block(1024);
         if (paths)
-            hipLaunchKernelGGL((tfp::tfk::merkle_proof_kernel<false, true>), grid, block, 0, s, d_desc + small.size(), d_leaf_indices, d_leaf_digests,
+            hipLaunchKernelGGL((tfp::tfk::merkle_proof_kernel<false, true>), grid, block, 0, s, d_desc + n_small, d_leaf_indices, d_leaf_digests,
                                d_auth, d_roots, d_scratch, d_statuses, d_paths);
         else
-            hipLaunchKernelGGL((tfp::tfk::merkle_proof_kernel<false, false>), grid, block, 0, s, d_desc + small.size(), d_leaf_indices,
+            hipLaunchKernelGGL((tfp::tfk::merkle_proof_kernel<false, false>), grid, block, 0, s, d_desc + n_small, d_leaf_indices,
                                d_leaf_digests, d_auth, d_roots, d_scratch, d_statuses, d_paths);
     }
     const hipError_t le = hipGetLastError();
-    if (d_scratch) (void)hipFreeAsync(d_scratch, s);
-    (void)hipFreeAsync(d_desc, s);
     if (le != hipSuccess) return hip_fail(le, "merkle_proof_kernel launch", __FILE__, __LINE__);
     return TF_OK;
 }

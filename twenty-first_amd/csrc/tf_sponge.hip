@@ -1,6 +1,6 @@
 // tf_sponge.hip -- batches of device-resident Tip5 sponges (sponge_kernels.h): Tip5::new, Sponge::absorb / squeeze /
 // pad_and_absorb_all, Tip5::sample_scalars / sample_indices (tip5/mod.rs:511-526, :636-698; util_types/sponge.rs:41-55), one launch per call.
-#include "tf_internal.h"
+#include "tf_temp.h"
 
 // As tf_proof.hip and tf_mmr.hip: this unit has its own copy of the Tip5 constants, in a namespace of its own, uploaded once per device.
 namespace tfs {
@@ -15,41 +15,20 @@ using tfs::tfk::kSpongeAbsorb;
 using tfs::tfk::kSpongeIndices;
 using tfs::tfk::kSpongeSqueeze;
 
-std::mutex g_consts_mu;
-bool g_consts_ready[kMaxDevices];
-
-int ensure_sponge_consts(int dev) {
-    std::lock_guard<std::mutex> lk(g_consts_mu);
-    if (g_consts_ready[dev]) return TF_OK;
-    tfs::tfk::Tip5Consts c;
-    for (int i = 0; i < 80; ++i) c.rc[i] = gl::to_mont(kRoundConstants[i]);
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(tfs::tfk::g_tip5), &c, sizeof(c)));
-    tfs::tfk::Tip5MxConsts mx;
-    tfs::tfk::fill_tip5_mx(mx, c.rc);
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(tfs::tfk::g_tip5_mx), &mx, sizeof(mx)));
-    HIPCHK(hipDeviceSynchronize());
-    g_consts_ready[dev] = true;
-    return TF_OK;
-}
-
-int ctx_dev(int* dev) {
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    *dev = (int)(ctx - g_ctx);
-    return ensure_sponge_consts(*dev);
-}
+Tip5ConstsOnce g_consts;
+int ctx_dev(int* dev) { return g_consts.ensure(dev, tfs::tfk::g_tip5, tfs::tfk::g_tip5_mx); }
 
 // The offsets of a ragged absorb reach the device through the pinned staging of tf_proof.hip / tf_mmr.hip, and the _dev form never
 // waits for its stream.  The kernel reads them where they are: page-locked host memory is mapped into the device's address space
 // (hipHostGetDevicePointer), every offset is read once, and a copy into device memory in front of the launch cost more than the
-// reads over the link (T3 of DESIGN 4.7: 27 us against the 91 us of the kernel).  The block goes back to the pool when the Upload
-// goes out of scope, after the launch that reads it is enqueued; it is handed out again once that launch has completed.
-struct Upload {
+// reads over the link (T3 of DESIGN 4.7: 27 us against the 91 us of the kernel).  The block goes back to the pool when the MappedWords
+// go out of scope, after the launch that reads it is enqueued; it is handed out again once that launch has completed.
+struct MappedWords {
     const void* d = nullptr;  // what the kernel reads
     int dev = 0;
     Staging stg;
     hipStream_t s = nullptr;
-    ~Upload() {
+    ~MappedWords() {
         if (stg.p) stage_release(dev, stg, s);
     }
     int put(int device, const void* host, size_t bytes, hipStream_t st) {
@@ -61,25 +40,6 @@ struct Upload {
         HIPCHK(hipHostGetDevicePointer(&mapped, stg.p, 0));
         d = mapped;
         return TF_OK;
-    }
-};
-
-struct Temp {  // stream-ordered device work space of the host-pointer forms
-    u64* p = nullptr;
-    hipStream_t s;
-    explicit Temp(hipStream_t st) : s(st) {}
-    int alloc(size_t words) {
-        if (!words) return TF_OK;
-        const hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&p), words * sizeof(u64), s);
-        if (e != hipSuccess) return hip_fail(e, "pool_malloc_async(sponge work space)", __FILE__, __LINE__);
-        return TF_OK;
-    }
-    int upload(const u64* h, size_t words) {
-        TRY(alloc(words));
-        return h2d(p, h, words, s);
-    }
-    ~Temp() {
-        if (p) (void)hipFreeAsync(p, s);
     }
 };
 
@@ -165,7 +125,7 @@ int sponge_absorb_dev(u64* states, size_t count, const u64* in, size_t len, cons
     g.in = in ? in - in_base : nullptr;
     g.len = (long long)len;
     g.pad = pad ? 1 : 0;
-    Upload up;
+    MappedWords up;
     if (offsets) {
         TRY(up.put(dev, offsets, (count + 1) * sizeof(uint64_t), s));
         g.offsets = static_cast<const unsigned long long*>(up.d);
@@ -209,14 +169,8 @@ int sponge_init_host(u64* states, size_t count, int fixed_length) {
     if (count == 0) return TF_OK;
     if (!states) return TF_ERR_NULL_POINTER;
     if (too_many(count, 16)) return TF_ERR_INVALID_ARGUMENT;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
-    Temp st(s);
-    TRY(st.alloc(16 * count));
-    TRY(sponge_init_dev(st.p, count, fixed_length, s));
-    TRY(d2h(states, st.p, 16 * count, s));
-    return sync(s);
+    return host_roundtrip(nullptr, 0, nullptr, 0, states, 16 * count,
+                          [&](u64*, u64*, u64* st, hipStream_t s) { return sponge_init_dev(st, count, fixed_length, s); });
 }
 
 int sponge_absorb_host(u64* states, size_t count, const u64* in, size_t len, const uint64_t* offsets, bool pad) {
@@ -224,16 +178,9 @@ int sponge_absorb_host(u64* states, size_t count, const u64* in, size_t len, con
     size_t in_words;
     TRY(check_absorb(states, count, in, len, offsets, pad, &noop, &in_words));
     if (noop) return TF_OK;
-    DeviceCtx* ctx = nullptr;
-    TRY(current_ctx(&ctx));
-    hipStream_t s = host_stream();
     const uint64_t base = offsets ? offsets[0] : 0;
-    Temp st(s), din(s);
-    TRY(st.upload(states, 16 * count));
-    if (in_words) TRY(din.upload(in + base, in_words));
-    TRY(sponge_absorb_dev(st.p, count, din.p, len, offsets, pad, base, s));
-    TRY(d2h(states, st.p, 16 * count, s));
-    return sync(s);
+    return host_in_place(states, 16 * count, in_words ? in + base : nullptr, in_words,
+                         [&](u64* st, u64* din, hipStream_t s) { return sponge_absorb_dev(st, count, din, len, offsets, pad, base, s); });
 }
 
 int sponge_squeeze_host(u64* states, size_t count, size_t per_sponge, size_t words_each, u64* out) {
@@ -244,8 +191,9 @@ int sponge_squeeze_host(u64* states, size_t count, size_t per_sponge, size_t wor
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     const size_t out_words = count * per_sponge * words_each;
-    Temp st(s), dout(s);
-    TRY(st.upload(states, 16 * count));
+    DevTemp st(s), dout(s);
+    TRY(st.alloc(16 * count));
+    TRY(h2d(st.p, states, 16 * count, s));
     TRY(dout.alloc(out_words));
     TRY(sponge_squeeze_dev(st.p, count, per_sponge, words_each, dout.p, s));
     TRY(d2h(out, dout.p, out_words, s));
@@ -260,10 +208,11 @@ int sponge_indices_host(u64* states, size_t count, uint32_t upper_bound, size_t 
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
-    Temp st(s), dout(s);
-    TRY(st.upload(states, 16 * count));
+    DevTemp st(s), dout(s);
+    TRY(st.alloc(16 * count));
+    TRY(h2d(st.p, states, 16 * count, s));
     TRY(dout.alloc((count * num + 1) / 2));
-    TRY(sponge_indices_dev(st.p, count, upper_bound, num, reinterpret_cast<uint32_t*>(dout.p), s));
+    TRY(sponge_indices_dev(st.p, count, upper_bound, num, dout.as<uint32_t>(), s));
     HIPCHK(hipMemcpyAsync(out, dout.p, count * num * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     TRY(d2h(states, st.p, 16 * count, s));
     return sync(s);

@@ -1,5 +1,5 @@
 // tf_tip5.hip -- Tip5 / Merkle launchers of libtf_hip.so (tip5_kernels.h) and the authentication structures.
-#include "tf_internal.h"
+#include "tf_temp.h"
 #include "tip5_kernels.h"
 
 #include <utility>
@@ -425,33 +425,25 @@ int merkle_root_dev(const u64* d_leaves, size_t n, u64* d_root, size_t batch, vo
     const long long N = (long long)n, leaves_ts = 5 * N;
     if (N <= kTopWidth) return merkle_narrow_levels(d_leaves, leaves_ts, N, nullptr, 0, d_root, nullptr, batch, false, s);
     // ping-pong level buffers: n/2 + n/4 digests per tree
-    u64* buf = nullptr;
-    const size_t words = size_t(batch) * size_t(5) * size_t(N / 2 + N / 4);
-    hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&buf), words * sizeof(u64), s);
-    if (e != hipSuccess) {
-        hip_fail(e, "pool_malloc_async(merkle levels)", __FILE__, __LINE__);
-        return TF_ERR_TREE_TOO_HIGH;
-    }
+    DevTemp buf(s);
+    if (buf.alloc(size_t(batch) * size_t(5) * size_t(N / 2 + N / 4), "merkle levels")) return TF_ERR_TREE_TOO_HIGH;
     if (narrow_from(N, batch)) {  // subtrees from the leaf level on
-        rc = merkle_narrow_levels(d_leaves, leaves_ts, N, nullptr, 0, d_root, buf, batch, false, s);
+        TRY(merkle_narrow_levels(d_leaves, leaves_ts, N, nullptr, 0, d_root, buf.p, batch, false, s));
     } else {
-        u64* a = buf;
-        u64* b = buf + size_t(batch) * 5 * size_t(N / 2);
+        u64* a = buf.p;
+        u64* b = buf.p + size_t(batch) * 5 * size_t(N / 2);
         long long w = N / 2;
-        rc = launch_hash_pairs(d_leaves, a, nullptr, w * (long long)batch, w, leaves_ts, 5 * w, 0, s);
-        while (rc == TF_OK && !narrow_from(w, batch)) {
+        TRY(launch_hash_pairs(d_leaves, a, nullptr, w * (long long)batch, w, leaves_ts, 5 * w, 0, s));
+        while (!narrow_from(w, batch)) {
             const long long nw = w / 2;
-            rc = launch_hash_pairs(a, b, nullptr, nw * (long long)batch, nw, 5 * w, 5 * nw, 0, s);
+            TRY(launch_hash_pairs(a, b, nullptr, nw * (long long)batch, nw, 5 * w, 5 * nw, 0, s));
             std::swap(a, b);
             w = nw;
         }
         // `a` holds the level of w digests per tree; the other buffer (>= w / 2 digests per tree) is free for the subtree roots
-        if (rc == TF_OK) rc = merkle_narrow_levels(a, 5 * w, w, nullptr, 0, d_root, b, batch, false, s);
+        TRY(merkle_narrow_levels(a, 5 * w, w, nullptr, 0, d_root, b, batch, false, s));
     }
-    e = hipFreeAsync(buf, s);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
-    return TF_OK;
+    return buf.release();
 }
 
 
