@@ -746,6 +746,65 @@ int tf_poly_linear_combination_dev(const uint64_t *d_polys, size_t n, int width_
                                    int width_w, uint64_t *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Points, powers and gathers: what a FRI query round does between sampling its indices and checking a fold.  replaces
+ *   Polynomial::get_colinear_y   math/polynomial.rs:386-394        get_colinear_y   out[i] = (dy (p2x - x0) + dx y0) / dx,
+ *                                                                                   dx = x0[i] - x1[i], dy = y0[i] - y1[i]
+ *   Polynomial::are_colinear     math/polynomial.rs:348-364        are_colinear     flags[g] = 1 or 0 per group of k points
+ *   BFieldElement::mod_pow b_field_element.rs:340-353, ModPowU32 / ModPowU64 :650, :809, x_field_element.rs:654-680
+ *                                                                  mod_pow          out[i] = bases[i]^exps[i], element by element
+ *   CyclicGroupGenerator::get_cyclic_group_elements b_field_element.rs:656-668, x_field_element.rs:423-435, the powers inside
+ *   Polynomial::scale, the points of an evaluation domain          powers           out[i] = first * ratio^i
+ *   (indexing a Vec)                                               gather_elements  out[i] = src[indices[i]]
+ * `width` is 1 for BFieldElement and 3 for XFieldElement [c0, c1, c2]; lengths count ELEMENTS.  Words are canonical raw Montgomery
+ * words in and out.  Each call has a host form (host pointers, blocking) and a _dev form (device pointers, enqueued on `stream`;
+ * it never synchronises and copies nothing back); the gather has the _dev form only.  out may not overlap an input.
+ *   widths           get_colinear_y and are_colinear take width_x for the x-coordinates and width_y for the y-coordinates (p2x and out
+ *                    included).  The valid pairs are (1, 1), (3, 3) and (1, 3); in the mixed form a BFieldElement x stands for its
+ *                    lift (x_field_element.rs:491-556) and the result is word for word that of (3, 3) on the lifted x-coordinates.
+ *   get_colinear_y   structure of arrays: x0, y0, x1, y1 hold n elements each; p2x holds n_p2x = 1 (one point for all triples, the
+ *                    folding challenge) or n_p2x = n elements.  A triple with x0 == x1 is where the reference panics (assert_ne!, :387):
+ *                    it raises TF_ERR_INVERSE_OF_ZERO -- the host form returns it, the _dev form writes it to *d_status, one int of
+ *                    device memory in which the first non-zero code wins and which is never cleared (the contract of the division
+ *                    calls above).  The outputs of the other triples of such a call are still correct, in both forms; only the
+ *                    offending triple's slot is unspecified.
+ *   are_colinear     xs and ys hold n_groups groups of exactly k points each, group after group; flags holds one int per group.  In the
+ *                    reference's order: k < 3 gives 0; two equal x-coordinates anywhere in the group give 0 (an XFieldElement is
+ *                    compared on all three limbs); otherwise 1 exactly when every point from the third on lies on the line through
+ *                    the first two.  No data-dependent error, so no status word.  k <= 1024 (the uniqueness test is pairwise).  The
+ *                    host form answers k < 3 without a device.
+ *   mod_pow          bases holds n_bases = 1 or n elements, exps n_exps = 1 or n uint64_t words; a count of 1 is broadcast.  x^0 = 1
+ *                    for every x, zero included, as the reference's loop gives.  One base for all elements (g^index, offset^j) is
+ *                    served from a table of its repeated squares.
+ *   powers           first and ratio are HOST arrays of `width` words in both forms (the _dev form passes them to the kernel by
+ *                    value).  With first = 1 this is get_cyclic_group_elements for n = the order of ratio (or its `max`); the
+ *                    reference's data-dependent stop -- back at 1 -- is the caller's: it knows the order it asked a root of unity
+ *                    for, and n is a fixed length here.
+ *   gather_elements  an element is `width` words, 1 <= width <= 16: field elements and 5-word digests alike.  indices is the
+ *                    uint32_t array a sponge's index sampler writes.  An index >= src_len is not read: it writes
+ *                    TF_ERR_INVALID_ARGUMENT to *d_status and leaves its slot of d_out as it was; the other outputs are correct.
+ *                    The second half of a fold (index + n / 2) is a pointer offset on d_src.
+ *   empty calls      n == 0 (are_colinear: n_groups == 0): TF_OK, nothing touched, NULL pointers allowed.
+ *   errors           returned before any HIP call, in this order: TF_ERR_NULL_POINTER (a pointer the call would use, d_status
+ *                    included; xs / ys may be NULL when k == 0, d_src when src_len == 0); TF_ERR_INVALID_ARGUMENT (a width or width
+ *                    pair not listed above, n_p2x / n_bases / n_exps neither 1 nor n); TF_ERR_LEN_TOO_LARGE (n, n_groups, n_groups * k
+ *                    or src_len above 2^30, k above 1024); then TF_ERR_NO_DEVICE on a machine without a GPU.
+ * get_colinear_y divides by Montgomery's trick per wave, in the field of the x-coordinates (csrc/points_kernels.h). */
+int tf_get_colinear_y(const uint64_t *x0, const uint64_t *y0, const uint64_t *x1, const uint64_t *y1, size_t n, const uint64_t *p2x,
+                      size_t n_p2x, int width_x, int width_y, uint64_t *out);
+int tf_get_colinear_y_dev(const uint64_t *d_x0, const uint64_t *d_y0, const uint64_t *d_x1, const uint64_t *d_y1, size_t n,
+                          const uint64_t *d_p2x, size_t n_p2x, int width_x, int width_y, uint64_t *d_out, void *stream, int *d_status);
+int tf_are_colinear(const uint64_t *xs, const uint64_t *ys, size_t n_groups, size_t k, int width_x, int width_y, int *flags);
+int tf_are_colinear_dev(const uint64_t *d_xs, const uint64_t *d_ys, size_t n_groups, size_t k, int width_x, int width_y, int *d_flags,
+                        void *stream);
+int tf_mod_pow(const uint64_t *bases, size_t n_bases, const uint64_t *exps, size_t n_exps, int width, uint64_t *out, size_t n);
+int tf_mod_pow_dev(const uint64_t *d_bases, size_t n_bases, const uint64_t *d_exps, size_t n_exps, int width, uint64_t *d_out, size_t n,
+                   void *stream);
+int tf_powers(const uint64_t *first, const uint64_t *ratio, int width, uint64_t *out, size_t n);
+int tf_powers_dev(const uint64_t *first, const uint64_t *ratio, int width, uint64_t *d_out, size_t n, void *stream);
+int tf_gather_elements_dev(const uint64_t *d_src, size_t src_len, int width, const uint32_t *d_indices, size_t n, uint64_t *d_out,
+                           void *stream, int *d_status);
+
+/* ---------------------------------------------------------------------------------------------
  * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the
  * first call); every other TF_* switch of DESIGN_HISTORY.md exists in the laboratory build alone (TF_AB_BUILD, below).
  *   TF_NTT_TILE_BYTES : bytes of batch processed between the passes of a multi-pass NTT (scratch size),

@@ -26,7 +26,7 @@ import numpy as np
 from . import _lib
 
 __all__ = [
-    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "linear_combination", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
+    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "linear_combination", "get_colinear_y", "are_colinear", "mod_pow", "powers", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
     "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "set_device", "get_device", "shard_range",
 ]
 
@@ -348,6 +348,77 @@ def linear_combination(columns: np.ndarray, weights: np.ndarray, n: int, width: 
     out = np.empty(n * max(width, width_w), dtype=np.uint64)
     if n:
         _check(lib().tf_poly_linear_combination(_ptr(c), n, width, stride, k, _ptr(w), width_w, _ptr(out)), "linear_combination")
+    return out
+
+
+def _width_pair(width_x: int, width_y: int) -> None:
+    if (width_x, width_y) not in ((1, 1), (3, 3), (1, 3)):
+        raise ValueError("(width_x, width_y) must be (1, 1), (3, 3) or (1, 3)")
+
+
+def get_colinear_y(x0, y0, x1, y1, p2x, width_x: int = 1, width_y: int = 1) -> np.ndarray:
+    """Polynomial::get_colinear_y (math/polynomial.rs:386-394) over n triples at once: out[i] is the y-coordinate at p2x of the line
+    through (x0[i], y0[i]) and (x1[i], y1[i]).  p2x holds one element (the same point for every triple) or n.  The x-coordinates have
+    width_x words, the y-coordinates, p2x and the result width_y; (1, 3) takes BFieldElement x-coordinates as their lifts.  A triple
+    with x0 == x1 panics (NttPanic code 12, the reference's assert_ne! at :387)."""
+    _width_pair(width_x, width_y)
+    x0, x1 = _elements(x0, width_x, "x0"), _elements(x1, width_x, "x1")
+    y0, y1, p2x = _elements(y0, width_y, "y0"), _elements(y1, width_y, "y1"), _elements(p2x, width_y, "p2x")
+    n = x0.size // width_x
+    if x1.size != x0.size or y0.size != n * width_y or y1.size != y0.size:
+        raise ValueError("x0, y0, x1 and y1 must hold the same number of elements")
+    n_p2x = p2x.size // width_y
+    if n and n_p2x not in (1, n):
+        raise ValueError("p2x must hold one element or one per triple")
+    out = np.empty(n * width_y, dtype=np.uint64)
+    if n:
+        _check(lib().tf_get_colinear_y(_ptr(x0), _ptr(y0), _ptr(x1), _ptr(y1), n, _ptr(p2x), n_p2x, width_x, width_y, _ptr(out)), "get_colinear_y")
+    return out
+
+
+def are_colinear(xs, ys, k: int, width_x: int = 1, width_y: int = 1) -> np.ndarray:
+    """Polynomial::are_colinear (math/polynomial.rs:348-364) over groups of exactly k points: xs and ys hold the groups one after the
+    other; the result is one bool per group (False for k < 3 and for a group with a repeated x-coordinate).  k <= 1024."""
+    _width_pair(width_x, width_y)
+    xs, ys = _elements(xs, width_x, "xs"), _elements(ys, width_y, "ys")
+    k = int(k)
+    if k <= 0:
+        raise ValueError("k must be positive (a group without points has no array layout)")
+    if (xs.size // width_x) % k or ys.size // width_y != xs.size // width_x:
+        raise ValueError("xs and ys must hold the same whole number of groups of k points")
+    n_groups = xs.size // width_x // k
+    flags = np.zeros(n_groups, dtype=np.int32)
+    if n_groups:
+        _check(lib().tf_are_colinear(_ptr(xs), _ptr(ys), n_groups, k, width_x, width_y, C.c_void_p(flags.ctypes.data)), "are_colinear")
+    return flags.astype(bool)
+
+
+def mod_pow(bases, exps, width: int = 1) -> np.ndarray:
+    """mod_pow (b_field_element.rs:340-353, ModPowU64 for both fields) element by element: out[i] = bases[i] ^ exps[i].  Either side
+    may be a single element (or an int exponent), which is then used for every element of the other.  x^0 = 1, also for x = 0."""
+    bases = _elements(bases, width, "bases")
+    exps = np.ascontiguousarray(np.atleast_1d(np.asarray(exps, dtype=np.uint64)).reshape(-1))
+    n_bases = bases.size // width
+    n = max(n_bases, exps.size) if n_bases and exps.size else 0
+    if n and (n_bases not in (1, n) or exps.size not in (1, n)):
+        raise ValueError("bases and exps must hold one element or the same number of elements")
+    out = np.empty(n * width, dtype=np.uint64)
+    if n:
+        _check(lib().tf_mod_pow(_ptr(bases), n_bases, _ptr(exps), exps.size, width, _ptr(out), n), "mod_pow")
+    return out
+
+
+def powers(first, ratio, n: int, width: int = 1) -> np.ndarray:
+    """The geometric sequence out[i] = first * ratio^i for i < n: the elements of a cyclic group (first = 1, n = the order of ratio;
+    b_field_element.rs:656-668, x_field_element.rs:423-435), the powers inside Polynomial::scale, the points of an evaluation
+    domain (first = the offset, ratio = the generator)."""
+    f, r = _scalar(first, width, "first"), _scalar(ratio, width, "ratio")
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    out = np.empty(n * width, dtype=np.uint64)
+    if n:
+        _check(lib().tf_powers(_ptr(f), _ptr(r), width, _ptr(out), n), "powers")
     return out
 
 

@@ -130,6 +130,15 @@ SIGNATURES = {
     "tf_hadamard_xfe_bfe_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "tf_poly_linear_combination": (C.c_int, [_vp, _sz, C.c_int, _sz, _sz, _vp, C.c_int, _vp]),
     "tf_poly_linear_combination_dev": (C.c_int, [_vp, _sz, C.c_int, _sz, _sz, _vp, C.c_int, _vp, _vp]),
+    "tf_get_colinear_y": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, C.c_int, C.c_int, _vp]),
+    "tf_get_colinear_y_dev": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "tf_are_colinear": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int, C.c_int, _vp]),
+    "tf_are_colinear_dev": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _vp]),
+    "tf_mod_pow": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _sz]),
+    "tf_mod_pow_dev": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _sz, _vp]),
+    "tf_powers": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz]),
+    "tf_powers_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _vp]),
+    "tf_gather_elements_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp]),
     "tf_zerofier_tree_new_bfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_xfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_bfe_dev": (C.c_int, [_vp, _sz, _vp, C.POINTER(C.c_void_p)]),

@@ -936,6 +936,37 @@ int tf_poly_linear_combination_dev(const uint64_t* polys, size_t n, int width_p,
                                    uint64_t* out, void* stream) try {
     return poly_lincomb(polys, n, width_p, stride, k, weights, width_w, out, false, stream);
 } TF_ABI_CATCH
+// get_colinear_y / are_colinear, element-wise mod_pow, geometric sequences and index gathers (tf_points.hip)
+int tf_get_colinear_y(const uint64_t* x0, const uint64_t* y0, const uint64_t* x1, const uint64_t* y1, size_t n, const uint64_t* p2x, size_t n_p2x,
+                      int width_x, int width_y, uint64_t* out) try {
+    return get_colinear_y(x0, y0, x1, y1, n, p2x, n_p2x, width_x, width_y, out, true, nullptr, nullptr);
+} TF_ABI_CATCH
+int tf_get_colinear_y_dev(const uint64_t* x0, const uint64_t* y0, const uint64_t* x1, const uint64_t* y1, size_t n, const uint64_t* p2x, size_t n_p2x,
+                          int width_x, int width_y, uint64_t* out, void* stream, int* d_status) try {
+    return get_colinear_y(x0, y0, x1, y1, n, p2x, n_p2x, width_x, width_y, out, false, stream, d_status);
+} TF_ABI_CATCH
+int tf_are_colinear(const uint64_t* xs, const uint64_t* ys, size_t n_groups, size_t k, int width_x, int width_y, int* flags) try {
+    return are_colinear(xs, ys, n_groups, k, width_x, width_y, flags, true, nullptr);
+} TF_ABI_CATCH
+int tf_are_colinear_dev(const uint64_t* xs, const uint64_t* ys, size_t n_groups, size_t k, int width_x, int width_y, int* flags, void* stream) try {
+    return are_colinear(xs, ys, n_groups, k, width_x, width_y, flags, false, stream);
+} TF_ABI_CATCH
+int tf_mod_pow(const uint64_t* bases, size_t n_bases, const uint64_t* exps, size_t n_exps, int width, uint64_t* out, size_t n) try {
+    return mod_pow(bases, n_bases, exps, n_exps, width, out, n, true, nullptr);
+} TF_ABI_CATCH
+int tf_mod_pow_dev(const uint64_t* bases, size_t n_bases, const uint64_t* exps, size_t n_exps, int width, uint64_t* out, size_t n, void* stream) try {
+    return mod_pow(bases, n_bases, exps, n_exps, width, out, n, false, stream);
+} TF_ABI_CATCH
+int tf_powers(const uint64_t* first, const uint64_t* ratio, int width, uint64_t* out, size_t n) try {
+    return powers(first, ratio, width, out, n, true, nullptr);
+} TF_ABI_CATCH
+int tf_powers_dev(const uint64_t* first, const uint64_t* ratio, int width, uint64_t* out, size_t n, void* stream) try {
+    return powers(first, ratio, width, out, n, false, stream);
+} TF_ABI_CATCH
+int tf_gather_elements_dev(const uint64_t* src, size_t src_len, int width, const uint32_t* indices, size_t n, uint64_t* out, void* stream,
+                           int* d_status) try {
+    return gather_elements_dev(src, src_len, width, indices, n, out, stream, d_status);
+} TF_ABI_CATCH
 static int coset_extrapolate_host(uint64_t offset, const uint64_t* cw, size_t n, size_t batch, const uint64_t* pts, size_t np,
                                   uint64_t* out, int L) {
     if (n == 0) return TF_ERR_LEN_NOT_POWER_OF_TWO;

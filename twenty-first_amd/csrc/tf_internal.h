@@ -11,6 +11,7 @@
 //   tf_divide.hip division with remainder and the power-series inverse (divide_kernels.h), with their entry points
 //   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
 //   tf_algebra.hip add / sub / neg, scalar_mul, scale, formal_derivative, degree and weighted sums of columns (algebra_kernels.h)
+//   tf_points.hip get_colinear_y / are_colinear, element-wise mod_pow, geometric sequences and index gathers (points_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 //   tf_temp.h     (header, included by the units above) DevTemp, the one owner of a stream-ordered temporary; the staged upload, the
 //                 per-unit Tip5 constants upload and the host round trip that every unit used to spell out for itself
@@ -309,6 +310,16 @@ int poly_derivative(const u64* a, size_t na, int width, u64* out, size_t batch, 
 int poly_degree(const u64* a, size_t na, int width, size_t batch, long long* degrees, bool host, void* stream);
 int hadamard_xfe_bfe_dev(const u64* a, const u64* b, u64* out, size_t count, void* stream);
 int poly_lincomb(const u64* polys, size_t n, int width_p, size_t stride, size_t k, const u64* weights, int width_w, u64* out, bool host, void* stream);
+
+// ------------------------------------------------------------------------------------ tf_points.hip
+// the point, power and gather calls of include/tf_hip.h ("Points, powers and gathers"): host = false takes device pointers and only
+// enqueues on `stream`, host = true takes host pointers and blocks.  Lengths count elements of `width` words.
+int get_colinear_y(const u64* x0, const u64* y0, const u64* x1, const u64* y1, size_t n, const u64* p2x, size_t n_p2x, int wx, int wy, u64* out,
+                   bool host, void* stream, int* d_status);
+int are_colinear(const u64* xs, const u64* ys, size_t n_groups, size_t k, int wx, int wy, int* flags, bool host, void* stream);
+int mod_pow(const u64* bases, size_t n_bases, const uint64_t* exps, size_t n_exps, int width, u64* out, size_t n, bool host, void* stream);
+int powers(const u64* first, const u64* ratio, int width, u64* out, size_t n, bool host, void* stream);
+int gather_elements_dev(const u64* src, size_t src_len, int width, const uint32_t* indices, size_t n, u64* out, void* stream, int* d_status);
 
 // ------------------------------------------------------------------------------------ tf_poly.hip
 extern std::atomic<int> g_batch_eval_route;

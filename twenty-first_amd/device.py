@@ -572,6 +572,106 @@ def inverse_or_zero(x, out, width: int = 1, stream=None) -> None:
     _chk(fn(_p(x), n, _p(out), _stream(stream)), "inverse_or_zero")
 
 
+def _width_pair(width_x: int, width_y: int) -> None:
+    _need((width_x, width_y) in ((1, 1), (3, 3), (1, 3)), "(width_x, width_y) must be (1, 1), (3, 3) or (1, 3)")
+
+
+def _own_status(status, like):
+    """the status word of a call: the caller's (see _status; nothing is synchronised) or one of the wrapper's own, which
+    _raise_own_status reads back after waiting for the stream"""
+    import torch
+
+    return torch.zeros(1, dtype=torch.int32, device=like.device) if status is None else status
+
+
+def _raise_own_status(st, stream, where: str) -> None:
+    import torch
+
+    (stream or torch.cuda.current_stream()).synchronize()
+    _chk(int(st.item()), where)
+
+
+def get_colinear_y(x0, y0, x1, y1, p2x, out, width_x: int = 1, width_y: int = 1, stream=None, status=None) -> None:
+    """Polynomial::get_colinear_y (math/polynomial.rs:386-394) over n triples on device buffers: out[i] = the y-coordinate at p2x of
+    the line through (x0[i], y0[i]) and (x1[i], y1[i]); p2x holds one element (one point for all triples) or n; out may not overlap
+    an input.  (width_x, width_y) is (1, 1), (3, 3) or (1, 3).  Without status a triple with x0 == x1 raises NttPanic (code 12)
+    after the call has synchronised once to read its flag; with status (see _status) nothing is synchronised and such a triple
+    writes 12 there.  Either way the outputs of the other triples are correct."""
+    x0, y0, x1, y1, p2x, out = _t(x0, "x0"), _t(y0, "y0"), _t(x1, "x1"), _t(y1, "y1"), _t(p2x, "p2x"), _t(out, "out")
+    _width_pair(width_x, width_y)
+    _need(x0.numel() % width_x == 0, "x0 must hold whole elements")
+    n = x0.numel() // width_x
+    _need(x1.numel() == x0.numel() and y0.numel() == n * width_y and y1.numel() == y0.numel() and out.numel() == y0.numel(),
+          "x0, y0, x1, y1 and out must hold the same number of elements")
+    _need(p2x.numel() in (width_y, n * width_y), "p2x must hold one element or one per triple")
+    for a in (x0, y0, x1, y1, p2x):
+        _apart(a, out, "out must not overlap an input")
+    st = _own_status(status, out)
+    _chk(_lib.lib().tf_get_colinear_y_dev(_p(x0), _p(y0), _p(x1), _p(y1), n, _p(p2x), p2x.numel() // width_y, width_x, width_y, _p(out),
+                                          _stream(stream), _status(st)), "get_colinear_y")
+    if status is None and n:
+        _raise_own_status(st, stream, "get_colinear_y")
+
+
+def are_colinear(xs, ys, k: int, flags, width_x: int = 1, width_y: int = 1, stream=None) -> None:
+    """Polynomial::are_colinear (math/polynomial.rs:348-364) over groups of exactly k points on device buffers: flags (int32, one
+    entry per group) receives 1 or 0.  Only enqueues."""
+    import torch
+
+    xs, ys = _t(xs, "xs"), _t(ys, "ys")
+    _width_pair(width_x, width_y)
+    _need(isinstance(flags, torch.Tensor) and flags.is_cuda and flags.is_contiguous() and flags.dtype == torch.int32,
+          "flags must be a contiguous CUDA int32 tensor")
+    n_groups = flags.numel()
+    _need(0 <= k <= 1024, "k must be in [0, 1024]")
+    _need(xs.numel() == n_groups * k * width_x and ys.numel() == n_groups * k * width_y, "xs and ys must hold flags.numel() groups of k points")
+    _chk(_lib.lib().tf_are_colinear_dev(_p(xs), _p(ys), n_groups, k, width_x, width_y, _p(flags), _stream(stream)), "are_colinear")
+
+
+def mod_pow(bases, exps, out, width: int = 1, stream=None) -> None:
+    """mod_pow (b_field_element.rs:340-353, ModPowU64 of both fields) element by element on device buffers: out[i] = bases[i] ^
+    exps[i]; exps holds uint64 words; bases and exps hold one element (used for every output) or as many as out.  One base for all
+    elements is served from a table of its repeated squares.  Only enqueues."""
+    bases, exps, out = _t(bases, "bases"), _t(exps, "exps"), _t(out, "out")
+    _width(width)
+    _need(bases.numel() % width == 0 and out.numel() % width == 0, "bases and out must hold whole elements")
+    n, n_bases = out.numel() // width, bases.numel() // width
+    _need(n == 0 or (n_bases in (1, n) and exps.numel() in (1, n)), "bases and exps must hold one element or one per element of out")
+    _apart(bases, out, "out must not overlap an input")
+    _apart(exps, out, "out must not overlap an input")
+    _chk(_lib.lib().tf_mod_pow_dev(_p(bases), n_bases, _p(exps), exps.numel(), width, _p(out), n, _stream(stream)), "mod_pow")
+
+
+def powers(first, ratio, out, width: int = 1, stream=None) -> None:
+    """out[i] = first * ratio^i on a device buffer; first and ratio are HOST scalars (an int or `width` raw words).  The elements of
+    a cyclic group, the powers of Polynomial::scale, the points of an evaluation domain.  Only enqueues."""
+    out = _t(out, "out")
+    f, r = _scalar_words(first, width, "first"), _scalar_words(ratio, width, "ratio")
+    _need(out.numel() % width == 0, "out must hold whole elements")
+    _chk(_lib.lib().tf_powers_dev(C.c_void_p(f.ctypes.data), C.c_void_p(r.ctypes.data), width, _p(out), out.numel() // width, _stream(stream)),
+         "powers")
+
+
+def gather_elements(src, indices, out, width: int = 1, stream=None, status=None) -> None:
+    """out[i] = src[indices[i]] for elements of `width` words (1..16: field elements, digests); indices is a CUDA tensor of 32-bit
+    words, as Tip5 sponges sample them.  Without status an index beyond src raises TwentyFirstError (code 17) after the call has
+    synchronised once; with status (see _status) nothing is synchronised and such an index writes 17 there.  Such an index is never
+    read and leaves its slot of out as it was."""
+    import torch
+
+    src, out = _t(src, "src"), _t(out, "out")
+    _need(1 <= width <= 16, "width must be in [1, 16]")
+    _need(isinstance(indices, torch.Tensor) and indices.is_cuda and indices.is_contiguous() and indices.dtype in (torch.int32, torch.uint32),
+          "indices must be a contiguous CUDA tensor of 32-bit words")
+    _need(src.numel() % width == 0 and out.numel() == indices.numel() * width, "src must hold whole elements and out one element per index")
+    _apart(src, out, "out must not overlap src")
+    st = _own_status(status, out)
+    _chk(_lib.lib().tf_gather_elements_dev(_p(src), src.numel() // width, width, _p(indices), indices.numel(), _p(out), _stream(stream), _status(st)),
+         "gather_elements")
+    if status is None and indices.numel():
+        _raise_own_status(st, stream, "gather_elements")
+
+
 def zerofier(roots, out, width: int = 1, stream=None) -> None:
     """Polynomial::zerofier (math/polynomial.rs:1435-1441) on device buffers: out = the n + 1 coefficients of prod (x - roots[i])."""
     roots, out = _t(roots, "roots"), _t(out, "out")

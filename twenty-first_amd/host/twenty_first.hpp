@@ -158,6 +158,32 @@ inline std::vector<XFieldElement> inverse_or_zero(std::vector<XFieldElement> inp
     return input;
 }
 
+// ---- element-wise powers and geometric sequences ----------------------------------------------------------------------------
+// mod_pow_u64 (b_field_element.rs:340-353, :809; x_field_element.rs:654-680): out[i] = bases[i] ^ exps[i]; either vector may hold a
+// single element, which then serves every element of the other.  x^0 = 1, zero included.
+template <class FF>
+inline std::vector<FF> mod_pow_u64(const std::vector<FF>& bases, const std::vector<uint64_t>& exps) {
+    const size_t n = bases.empty() || exps.empty() ? 0 : std::max(bases.size(), exps.size());
+    std::vector<FF> out(n);
+    check(tf_mod_pow(reinterpret_cast<const uint64_t*>(bases.data()), bases.size(), exps.data(), exps.size(), sizeof(FF) / 8,
+                     reinterpret_cast<uint64_t*>(out.data()), n), "mod_pow_u64");
+    return out;
+}
+// mod_pow_u32 (b_field_element.rs:650; x_field_element.rs:654-667)
+template <class FF>
+inline std::vector<FF> mod_pow_u32(const std::vector<FF>& bases, const std::vector<uint32_t>& exps) {
+    return mod_pow_u64(bases, std::vector<uint64_t>(exps.begin(), exps.end()));
+}
+// first * ratio^i for i < n: the elements of a cyclic group (first = 1, n = the order of ratio; b_field_element.rs:656-668,
+// x_field_element.rs:423-435), the powers inside Polynomial::scale, the points of an evaluation domain
+template <class FF>
+inline std::vector<FF> powers(FF first, FF ratio, size_t n) {
+    std::vector<FF> out(n);
+    check(tf_powers(reinterpret_cast<const uint64_t*>(&first), reinterpret_cast<const uint64_t*>(&ratio), sizeof(FF) / 8,
+                    reinterpret_cast<uint64_t*>(out.data()), n), "powers");
+    return out;
+}
+
 // the field a product of an A and a B lives in (x_field_element.rs:491-556): the extension field if either is
 template <class A, class B>
 using ProductField = std::conditional_t<(sizeof(A) >= sizeof(B)), A, B>;
@@ -266,6 +292,24 @@ struct Polynomial {
         check(tf_poly_formal_derivative(reinterpret_cast<const uint64_t*>(coefficients.data()), coefficients.size(), sizeof(FF) / 8,
                                         reinterpret_cast<uint64_t*>(out.data()), 1), "formal_derivative");
         return Polynomial(std::move(out));
+    }
+    // are_colinear (polynomial.rs:348-364): fewer than three points, or two equal x-coordinates, are not colinear
+    static bool are_colinear(const std::vector<std::pair<FF, FF>>& points) {
+        std::vector<FF> xs, ys;
+        for (const auto& p : points) xs.push_back(p.first), ys.push_back(p.second);
+        int flag = 0;
+        check(tf_are_colinear(reinterpret_cast<const uint64_t*>(xs.data()), reinterpret_cast<const uint64_t*>(ys.data()), 1, points.size(),
+                              sizeof(FF) / 8, sizeof(FF) / 8, &flag), "are_colinear");
+        return flag != 0;
+    }
+    // get_colinear_y (polynomial.rs:386-394); panics if p0 and p1 share their x-coordinate (NttPanic, code 12, :387)
+    static FF get_colinear_y(std::pair<FF, FF> p0, std::pair<FF, FF> p1, FF p2_x) {
+        FF out{};
+        check(tf_get_colinear_y(reinterpret_cast<const uint64_t*>(&p0.first), reinterpret_cast<const uint64_t*>(&p0.second),
+                                reinterpret_cast<const uint64_t*>(&p1.first), reinterpret_cast<const uint64_t*>(&p1.second), 1,
+                                reinterpret_cast<const uint64_t*>(&p2_x), 1, sizeof(FF) / 8, sizeof(FF) / 8, reinterpret_cast<uint64_t*>(&out)),
+              "get_colinear_y");
+        return out;
     }
     // batch_evaluate (polynomial.rs:1840-1852): f at every point of `domain`
     std::vector<FF> batch_evaluate(const std::vector<FF>& domain) const {
