@@ -920,6 +920,29 @@ enum {
 };
 int tf_debug_field_op_dev(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out0, uint64_t *d_out1, size_t count, void *stream);
 
+/* Test helper: ONE composition of the shift-only register networks of the NTT kernels (csrc/ntt_network.h: dit_half, dit_level,
+ * DitRange, class_fused, leftover_fused, tw_operand) and of the glue that hands words to their first level (csrc/ntt_kernels.h:
+ * pre2_combine8, pre2_shift, c8_combine8), instantiated with the template arguments of its call sites.  Thread t loads the block
+ * x[q] = d_x[B t + q], q < 32, runs the form and stores x[0 .. 31] back in place; nothing else is written.  B = 32, except for the
+ * PRE2 and C8 forms: B = 64 there, the second 32 words of a block being the partner words w (read only; w[q] pairs with x[q]).
+ *   form (INV = form & 1 everywhere)       what runs                                                        input contract
+ *   NET32   0 + 2 v + INV                  dit_half<0>, dit_half<16>, dit_level<5>; v = 0 lazy, 1 lazy with  lazy: even slots any word,
+ *                                          two products per block (WIDE = 2), 2 canonical                   odd slots < p; canonical:
+ *   LEVELS  6 + 4 (p2 - 1) + 2 LAZY + INV  dit_level<1> .. dit_level<p2>, p2 = 1 .. 5                       every word < p
+ *   TAIL5   26 + INV                       canonical dit_half<0>, dit_half<16>, then the partial ranges     every word < p
+ *                                          DitRange<5, Q0, Q0 + 4>, Q0 = 0, 4, 8, 12
+ *   LAT     28 + 2 (LOGR - 1) + INV        canonical DitRange<l, 0, 4>, l = 1 .. LOGR <= 3 (slots 0 .. 7)    every word < p
+ *   PRE2    34 + 2 half + INV              pre2_combine8 x 4, pre2_shift where half = 1, lazy NET32         x and w < p
+ *   C8      38 + 2 half + INV              c8_combine8 x 4, pre2_shift where half = 1, lazy levels 1 .. 5   x and w < p
+ * A lazy form leaves words that are only congruent to the elements (the kernels follow it with a Montgomery product); with TF_LAZY = 0
+ * every form is canonical.  TF_ERR_INVALID_ARGUMENT -- before any launch -- for an unknown form, a count that is not a multiple of B
+ * or above 2^32; a count of 0 is TF_OK. */
+enum { TF_NTT_NETWORK_FORM_COUNT = 42 };
+int tf_debug_ntt_network_dev(int form, uint64_t *d_x, size_t count, void *stream);
+/* The compile-time switches of the loaded library that decide what the forms above compute: TF_LAZY, TF_ASM_BFLY, TF_ASM_POW2 and
+ * TF_POW2_WIDE (null pointers are skipped). */
+void tf_debug_ntt_network_config(int *lazy, int *asm_bfly, int *asm_pow2, int *pow2_wide);
+
 #ifdef __cplusplus
 }
 #endif

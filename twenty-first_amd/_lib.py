@@ -230,6 +230,8 @@ SIGNATURES = {
     "tf_debug_fill_random_dev": (C.c_int, [_vp, _sz, C.c_uint64, C.c_uint64, _vp]),
     "tf_debug_mul_pow2_dev": (C.c_int, [_vp, _sz, C.c_int, _vp]),
     "tf_debug_field_op_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tf_debug_ntt_network_dev": (C.c_int, [C.c_int, _vp, _sz, _vp]),
+    "tf_debug_ntt_network_config": (None, [C.POINTER(C.c_int)] * 4),
 }
 
 

@@ -266,6 +266,22 @@ int tf_debug_field_op_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint
     return TF_OK;
 } TF_ABI_CATCH
 
+// test helper (not part of the drop-in boundary): one composition of the NTT register networks over blocks of 32 (or 64) words
+int tf_debug_ntt_network_dev(int form, uint64_t* d_x, size_t count, void* stream) try {
+    if (form < 0 || form >= TF_NTT_NETWORK_FORM_COUNT || count > (size_t(1) << 32)) return TF_ERR_INVALID_ARGUMENT;
+    if (count % (size_t)debug_ntt_network_words(form)) return TF_ERR_INVALID_ARGUMENT;
+    if (count == 0) return TF_OK;
+    if (!d_x) return TF_ERR_NULL_POINTER;
+    DeviceCtx* ctx = nullptr;
+    int rc = current_ctx(&ctx);
+    if (rc) return rc;
+    debug_ntt_network_dev(form, reinterpret_cast<u64*>(d_x), count, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+} TF_ABI_CATCH
+
+void tf_debug_ntt_network_config(int* lazy, int* asm_bfly, int* asm_pow2, int* pow2_wide) { debug_ntt_network_config(lazy, asm_bfly, asm_pow2, pow2_wide); }
+
 #ifdef TF_AB_BUILD
 // measurement helper (not part of the drop-in boundary): allocate / fetch the MODE-3 stamp buffer
 int tf_debug_stamps(unsigned long long* host_out, size_t words) try {

@@ -188,6 +188,10 @@ constexpr int field_op_width(int op) {
 }
 constexpr bool field_op_two_outputs(int op) { return op == TF_FIELD_OP_ADD_SUB || op == TF_FIELD_OP_ADD_SUB2 || op == TF_FIELD_OP_ADD_SUB_LAZY2; }
 void debug_field_op_dev(int op, const u64* d_a, const u64* d_b, u64* d_out0, u64* d_out1, size_t count, hipStream_t s);
+// tf_debug_ntt_network_dev / _config: the forms are instantiated in tf_ntt.hip, the unit that sees ntt_kernels.h and its switches
+int debug_ntt_network_words(int form);  // words per block of the form: 32, or 64 for the forms with a partner block
+void debug_ntt_network_dev(int form, u64* d_x, size_t count, hipStream_t s);
+void debug_ntt_network_config(int* lazy, int* asm_bfly, int* asm_pow2, int* pow2_wide);
 extern const u64 kRoundConstants[80];  // ROUND_CONSTANTS, tip5/mod.rs:68-149 (canonical values; tf_tip5.hip)
 // the planner's rules for a launch of `count` permutation chains (tf_tip5.hip has the measurements behind them)
 constexpr long long kCoopMaxCount = 1ll << 13;

@@ -1857,4 +1857,128 @@ int coset_eval_dev(const u64* d_coeffs, size_t n_coeffs, u64 offset_raw, u64* d_
 }
 
 
+// ------------------------------------------------------------------------------------ tf_debug_ntt_network_dev
+// ONE composition of the register networks of ntt_network.h (and of the glue of ntt_kernels.h that hands words to level 1), with the
+// template arguments of its call sites, over blocks of 32 consecutive words: thread t loads x[q] = d_x[B t + q], runs the form and
+// stores x[0 .. 31] back in place.  B = 32, or 64 for the PRE2 / C8 forms, whose second 32 words are the partner block w (read, never
+// written).  The forms and their input contracts (what the call sites guarantee; the caller of this entry point keeps to them):
+//   NET32   dit_half<INV,0>, dit_half<INV,16>, dit_level<INV,5>; variant 0: lazy, WIDE = TF_POW2_WIDE (ntt_pass_kernel step 1, the
+//           R = 32 / 1024 passes), 1: lazy, WIDE = 2 (ntt_block_kernel stages A and B, LOGP3 = 4), 2: canonical (ntt_rows32_kernel forward)
+//   LEVELS  dit_level<INV,1> .. dit_level<INV,p2>, lazy or canonical (the column pass's run-time p2 step, step 2 of the two-pass and
+//           eight-column kernels, rows32_network, the canonical LOGP3 tail of ntt_block_kernel)
+//   TAIL5   canonical dit_half<INV,0>, dit_half<INV,16>, then DitRange<INV,5,Q0,Q0+4,false> for Q0 = 0, 4, 8, 12 (tail_p5)
+//   LAT     DitRange<INV,l,0,4,false> for l = 1 .. LOGR on slots 0 .. 7 (lat_dft); slots 8 .. 31 pass through
+//   PRE2    pre2_combine8<INV,0/8/16/24>(x, w, half), pre2_shift where ntt_pass_kernel applies it, then the lazy NET32
+//   C8      c8_combine8<INV,0/8/16/24>(x, w, half), pre2_shift<INV> when half, then lazy levels 1 .. 5 (the eight-column kernel)
+// lazy forms: even slots any 64-bit word, odd slots (second operands of level 1) < p; canonical forms: every word < p; PRE2 / C8: both
+// blocks canonical (loaded words or Montgomery products).
+constexpr int kNetLevels = 6, kNetTail5 = 26, kNetLat = 28, kNetPre2 = 34, kNetC8 = 38;
+static_assert(kNetC8 + 4 == TF_NTT_NETWORK_FORM_COUNT, "include/tf_hip.h lists the forms");
+constexpr int net_form_words(int form) { return form >= kNetPre2 ? 64 : 32; }
+
+template <bool INV, bool LAZY, int WIDE>
+__device__ __forceinline__ void net32_form(u64 (&x)[32]) {
+    tfk::dit_half<INV, 0, LAZY, WIDE>(x);
+    tfk::dit_half<INV, 16, LAZY, WIDE>(x);
+    tfk::dit_level<INV, 5, LAZY, WIDE>(x);
+}
+template <bool INV, bool LAZY, int P2, int LVL = 1>
+__device__ __forceinline__ void levels_form(u64 (&x)[32]) {
+    if constexpr (LVL <= P2) {
+        tfk::dit_level<INV, LVL, LAZY>(x);
+        levels_form<INV, LAZY, P2, LVL + 1>(x);
+    }
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(256) ntt_network_form_kernel(u64* d, unsigned long long blocks, int half) {
+    constexpr int B = net_form_words(FORM);
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= blocks) return;
+    u64* const p = d + t * B;
+    u64 x[32];
+#pragma unroll
+    for (int q = 0; q < 32; ++q) x[q] = p[q];
+    if constexpr (FORM < kNetLevels) {
+        constexpr bool INV = (FORM & 1) != 0;
+        constexpr int V = FORM >> 1;
+        if constexpr (V == 0) net32_form<INV, true, TF_POW2_WIDE>(x);
+        else if constexpr (V == 1) net32_form<INV, true, 2>(x);
+        else net32_form<INV, false, TF_POW2_WIDE>(x);
+    } else if constexpr (FORM < kNetTail5) {
+        constexpr int K = FORM - kNetLevels;
+        levels_form<(K & 1) != 0, ((K >> 1) & 1) != 0, (K >> 2) + 1>(x);
+    } else if constexpr (FORM < kNetLat) {
+        constexpr bool INV = ((FORM - kNetTail5) & 1) != 0;
+        tfk::dit_half<INV, 0>(x);
+        tfk::dit_half<INV, 16>(x);
+        tfk::DitRange<INV, 5, 0, 4, false>::run(x);
+        tfk::DitRange<INV, 5, 4, 8, false>::run(x);
+        tfk::DitRange<INV, 5, 8, 12, false>::run(x);
+        tfk::DitRange<INV, 5, 12, 16, false>::run(x);
+    } else if constexpr (FORM < kNetPre2) {
+        constexpr int K = FORM - kNetLat;
+        constexpr bool INV = (K & 1) != 0;
+        constexpr int LOGR = (K >> 1) + 1;
+        tfk::DitRange<INV, 1, 0, 4, false>::run(x);
+        if constexpr (LOGR >= 2) tfk::DitRange<INV, 2, 0, 4, false>::run(x);
+        if constexpr (LOGR >= 3) tfk::DitRange<INV, 3, 0, 4, false>::run(x);
+    } else {
+        constexpr bool INV = (FORM & 1) != 0;  // (kNetPre2 and kNetC8 are even)
+        u64 wa[8], wb[8];
+        if constexpr (FORM < kNetC8) {
+            // the order of ntt_pass_kernel's overlapped load: the first sixteen slots go through levels 1-4 before the last sixteen are combined
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wa[i] = p[32 + i], wb[i] = p[40 + i];
+            tfk::pre2_combine8<INV, 0>(x, wa, half != 0);
+            tfk::pre2_combine8<INV, 8>(x, wb, half != 0);
+            if (half) tfk::pre2_shift<INV, 1, 16>(x);
+            tfk::dit_half<INV, 0, true>(x);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wa[i] = p[48 + i], wb[i] = p[56 + i];
+            tfk::pre2_combine8<INV, 16>(x, wa, half != 0);
+            tfk::pre2_combine8<INV, 24>(x, wb, half != 0);
+            if (half) tfk::pre2_shift<INV, 16, 32>(x);
+            tfk::dit_half<INV, 16, true>(x);
+            tfk::dit_level<INV, 5, true>(x);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wa[i] = p[32 + i], wb[i] = p[40 + i];
+            tfk::c8_combine8<INV, 0>(x, wa, half != 0);
+            tfk::c8_combine8<INV, 8>(x, wb, half != 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wa[i] = p[48 + i], wb[i] = p[56 + i];
+            tfk::c8_combine8<INV, 16>(x, wa, half != 0);
+            tfk::c8_combine8<INV, 24>(x, wb, half != 0);
+            if (half) tfk::pre2_shift<INV>(x);
+            levels_form<INV, true, 5>(x);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 32; ++q) p[q] = x[q];
+}
+
+template <int FORM>
+void network_form_launch(u64* d_x, size_t blocks, hipStream_t s) {
+    const int half = FORM >= kNetPre2 ? ((FORM - kNetPre2) >> 1) & 1 : 0;
+    hipLaunchKernelGGL(ntt_network_form_kernel<FORM>, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, d_x, (unsigned long long)blocks, half);
+}
+template <int... FORM>
+void network_form_dispatch(int form, u64* d_x, size_t blocks, hipStream_t s, std::integer_sequence<int, FORM...>) {
+    using Fn = void (*)(u64*, size_t, hipStream_t);
+    static const Fn table[] = {&network_form_launch<FORM>...};
+    table[form](d_x, blocks, s);
+}
+int debug_ntt_network_words(int form) { return net_form_words(form); }
+void debug_ntt_network_dev(int form, u64* d_x, size_t count, hipStream_t s) {
+    network_form_dispatch(form, d_x, count / (size_t)net_form_words(form), s, std::make_integer_sequence<int, TF_NTT_NETWORK_FORM_COUNT>{});
+}
+void debug_ntt_network_config(int* lazy, int* asm_bfly, int* asm_pow2, int* pow2_wide) {
+    if (lazy) *lazy = TF_LAZY;
+    if (asm_bfly) *asm_bfly = TF_ASM_BFLY;
+    if (asm_pow2) *asm_pow2 = TF_ASM_POW2;
+    if (pow2_wide) *pow2_wide = TF_POW2_WIDE;
+}
+
+
 }  // namespace tfi

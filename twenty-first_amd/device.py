@@ -84,6 +84,40 @@ def debug_field_op(op: str, a, b, out0, out1=None, stream=None) -> None:
          "debug_field_op")
 
 
+# form name -> (code of include/tf_hip.h, words per block); INV is the lowest bit of every code
+NETWORK_FORMS = {}
+for _inv in (0, 1):
+    _d = "inv" if _inv else "fwd"
+    for _v, _name in enumerate(("lazy", "lazy_wide2", "canonical")):
+        NETWORK_FORMS[f"NET32_{_d}_{_name}"] = (0 + 2 * _v + _inv, 32)
+    for _p2 in range(1, 6):
+        for _lazy in (0, 1):
+            NETWORK_FORMS[f"LEVELS{_p2}_{_d}_{'lazy' if _lazy else 'canonical'}"] = (6 + 4 * (_p2 - 1) + 2 * _lazy + _inv, 32)
+    NETWORK_FORMS[f"TAIL5_{_d}"] = (26 + _inv, 32)
+    for _logr in (1, 2, 3):
+        NETWORK_FORMS[f"LAT{_logr}_{_d}"] = (28 + 2 * (_logr - 1) + _inv, 32)
+    for _half in (0, 1):
+        NETWORK_FORMS[f"PRE2_{_d}_half{_half}"] = (34 + 2 * _half + _inv, 64)
+        NETWORK_FORMS[f"C8_{_d}_half{_half}"] = (38 + 2 * _half + _inv, 64)
+
+
+def debug_ntt_network_(form: str, x, stream=None) -> None:
+    """Test helper, in place on device: one composition of the NTT register networks (tf_debug_ntt_network_dev; NETWORK_FORMS lists
+    the forms) over blocks of 32 consecutive words, one thread per block.  The PRE2 / C8 forms take blocks of 64 words -- 32 words x,
+    then their 32 partner words w -- and write the first 32 only."""
+    code, words = NETWORK_FORMS[form]
+    x = _t(x, "x")
+    _need(x.numel() % words == 0, f"{form} works on whole blocks of {words} words")
+    _chk(_lib.lib().tf_debug_ntt_network_dev(code, _p(x), x.numel(), _stream(stream)), "debug_ntt_network")
+
+
+def debug_ntt_network_config() -> dict:
+    """The compile-time switches of the loaded library that decide what the network forms compute."""
+    v = [C.c_int(-1) for _ in range(4)]
+    _lib.lib().tf_debug_ntt_network_config(*[C.byref(i) for i in v])
+    return dict(zip(("lazy", "asm_bfly", "asm_pow2", "pow2_wide"), (i.value for i in v)))
+
+
 def ntt_(x, n: int, batch: int = 1, width: int = 1, inverse: bool = False, stream=None) -> None:
     """In place on device: `batch` slices of n elements (math/ntt.rs:67-82, :109-125)."""
     x = _t(x, "x")
