@@ -94,9 +94,9 @@ def test_grid_stride_wrap(tf, oracle, w):
     for n in (_wrap(w) - 1, _wrap(w) + 1, _wrap(w) + _chunk(w) + 5):
         x = torch.empty(w * n, dtype=torch.int64, device="cuda")
         tf.device.fill_random(x, 0x1C00 + n)
-        y = torch.empty_like(x)
+        y = torch.full_like(x, -1)  # (outputs start as 2^64 - 1, not canonical: a word never stored shows)
         tf.device.batch_inversion(x, y, width=w)
-        prod = torch.empty_like(x)
+        prod = torch.full_like(x, -1)
         tf.device.hadamard(x, y, prod, width=w)
         assert torch.equal(prod, _to_dev(_one(w, n))), n
         xs, ys = _to_host(x), _to_host(y)
@@ -112,9 +112,9 @@ def test_large_sizes(tf, oracle, w, n):
 
     x = torch.empty(w * n, dtype=torch.int64, device="cuda")
     tf.device.fill_random(x, 0x1D00 + w)
-    y = torch.empty_like(x)
+    y = torch.full_like(x, -1)
     tf.device.batch_inversion(x, y, width=w)
-    prod = torch.empty_like(x)
+    prod = torch.full_like(x, -1)
     tf.device.hadamard(x, y, prod, width=w)
     assert torch.equal(prod, _to_dev(_one(w, n)))
     ys = _to_host(y)
@@ -126,7 +126,7 @@ def test_large_sizes(tf, oracle, w, n):
     tf.device.batch_inversion(x, x, width=w)
     assert torch.equal(x, y)
     # inverse_or_zero of an input without zeros: the same words too
-    z = torch.empty_like(x)
+    z = torch.full_like(x, -1)
     tf.device.inverse_or_zero(y, z, width=w)
     torch.cuda.synchronize()
     assert torch.equal(z, _to_dev(xs))
@@ -151,7 +151,7 @@ def test_a_zero_element_panics(tf, oracle, w):
             tf.batch_inversion(x, width=w)
         assert e.value.code == INVERSE_OF_ZERO, pos
         d = _to_dev(x)
-        out = torch.empty_like(d)
+        out = torch.full_like(d, -1)  # (not canonical: a word never stored shows)
         with pytest.raises(tf.NttPanic) as e:
             tf.device.batch_inversion(d, out, width=w)
         assert e.value.code == INVERSE_OF_ZERO, pos
@@ -169,7 +169,7 @@ def test_a_zero_element_panics(tf, oracle, w):
     # no zero: the status stays 0, and the host form's C status is TF_OK
     x = oracle.fill_random(w * n, 0x1EFF)
     st = torch.zeros(1, dtype=torch.int32, device="cuda")
-    out = torch.empty(w * n, dtype=torch.int64, device="cuda")
+    out = torch.full((w * n,), -1, dtype=torch.int64, device="cuda")
     tf.device.batch_inversion(_to_dev(x), out, width=w, status=st)
     torch.cuda.synchronize()
     assert int(st.item()) == 0
@@ -193,10 +193,10 @@ def test_async_forms_never_synchronise(tf, oracle):
     xx_zero = xx.clone()
     xx_zero[3 * 17:3 * 18] = 0
     # blocking reference runs (also warm the pool and the code objects)
-    rb, rx = torch.empty_like(xb), torch.empty_like(xx)
+    rb, rx = torch.full_like(xb, -1), torch.full_like(xx, -1)
     tf.device.batch_inversion(xb, rb)
     tf.device.batch_inversion(xx, rx, width=3)
-    rz = torch.empty_like(xx)
+    rz = torch.full_like(xx, -1)
     tf.device.inverse_or_zero(xx_zero, rz, width=3)
     big = torch.empty(256 << 20, dtype=torch.int64, device="cuda")
     tf.device.fill_random(big, 0x1F03)
@@ -206,7 +206,8 @@ def test_async_forms_never_synchronise(tf, oracle):
     s = torch.cuda.Stream()
     st = torch.zeros(1, dtype=torch.int32, device="cuda")
     st_bad = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ob, ox, oz, junk = torch.empty_like(xb), torch.empty_like(xx), torch.empty_like(xx), torch.empty_like(xx)
+    ob, ox, oz, junk = torch.full_like(xb, -1), torch.full_like(xx, -1), torch.full_like(xx, -1), torch.full_like(xx, -1)
+    s.wait_stream(torch.cuda.current_stream())  # (the fills above are on the default stream)
     with torch.cuda.stream(s):
         for _ in range(20):  # ~40 ms of queued work in front of the calls
             tf.device.ntt_(big, 1 << 20, batch=256, stream=s)

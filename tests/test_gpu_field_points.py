@@ -80,7 +80,7 @@ def _run_colinear_both(tf, ins, wx, wy, want):
 
     x0, y0, x1, y1, p2x = ins
     assert np.array_equal(tf.get_colinear_y(x0, y0, x1, y1, p2x, width_x=wx, width_y=wy), want)
-    out = torch.zeros(want.size, dtype=torch.int64, device="cuda")
+    out = torch.full((want.size,), -1, dtype=torch.int64, device="cuda")  # (not canonical: a word never stored shows)
     st = _status()
     tf.device.get_colinear_y(*[_to_dev(a) for a in ins], out, width_x=wx, width_y=wy, status=st)
     torch.cuda.synchronize()
@@ -178,7 +178,7 @@ def test_get_colinear_y_large_checked_by_are_colinear(tf):
     for i, b in enumerate(bufs):
         tf.device.fill_random(b, 0x3D00 + i)
     x0, y0, x1, y1, p2x = bufs
-    out = torch.empty_like(x0)
+    out = torch.full_like(x0, -1)  # (not canonical: a word never stored shows)
     st = _status()
     tf.device.get_colinear_y(x0, y0, x1, y1, p2x, out, status=st)
     xs = torch.stack((x0, x1, p2x), dim=1).reshape(-1).contiguous()
@@ -328,7 +328,7 @@ def test_mod_pow_past_the_grid_stride_wrap(tf, oracle):
     exps = torch.empty(n, dtype=torch.int64, device="cuda")
     tf.device.fill_random(exps, 0x5C00)
     exps &= 0xFFFFFFFF
-    out, out2 = torch.empty_like(exps), torch.empty_like(exps)
+    out, out2 = torch.full_like(exps, -1), torch.full_like(exps, -1)  # (not canonical: a word never stored shows)
     tf.device.mod_pow(base, exps, out)
     tf.device.mod_pow(base.repeat(n), exps, out2)
     torch.cuda.synchronize()
@@ -386,9 +386,9 @@ def test_powers_around_one_launch_thread_count(tf, oracle, w):
     f, r = rnd[:w], rnd[w:]
     fe, re_ = ref.elements(f, w)[0], ref.elements(r, w)[0]
     for n in (s_max - 1, s_max + 1, 2 * s_max + 5):
-        out = torch.empty(n * w, dtype=torch.int64, device="cuda")
+        out = torch.full((n * w,), -1, dtype=torch.int64, device="cuda")  # (not canonical: a word never stored shows)
         tf.device.powers(f, r, out, width=w)
-        nxt = torch.empty((n - 1) * w, dtype=torch.int64, device="cuda")
+        nxt = torch.full(((n - 1) * w,), -1, dtype=torch.int64, device="cuda")
         tf.device.poly_scalar_mul(out[:(n - 1) * w], n - 1, r, nxt, width=w, width_s=w)
         torch.cuda.synchronize()
         assert torch.equal(nxt, out[w:]), n

@@ -64,7 +64,7 @@ def open_dev(tf, d_leafs, n, idx, batch=1, with_roots=True, stream=None):
     """The device call -> (structure (batch, count, 5), roots (batch, 5) or None), read back after a synchronisation."""
     import torch
 
-    d_roots = torch.zeros(batch * 5, dtype=torch.int64, device="cuda") if with_roots else None
+    d_roots = torch.full((batch * 5,), -1, dtype=torch.int64, device="cuda") if with_roots else None  # (not canonical: a word never stored shows)
     d_out = tf.device.authentication_structure_from_leafs(d_leafs, n, idx, roots=d_roots, batch=batch, stream=stream)
     torch.cuda.synchronize()
     return host_words(d_out).reshape(batch, -1, 5), host_words(d_roots).reshape(batch, 5) if with_roots else None

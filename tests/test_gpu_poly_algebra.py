@@ -43,9 +43,11 @@ def _to_host(t):
 
 
 def _empty(words):
+    """an output buffer: every word 2^64 - 1, which no kernel stores (it is not canonical), so a word that is never stored shows --
+    torch.empty would hand back the block the previous call of the same size freed, right words included"""
     import torch
 
-    return torch.empty(words, dtype=torch.int64, device="cuda")
+    return torch.full((words,), -1, dtype=torch.int64, device="cuda")
 
 
 def _wrap():

@@ -247,8 +247,8 @@ def test_dev_matches_host(tf, oracle, na, nb, w, batch):
 
     a, b = rand(oracle, batch * na * w, na + 1), divisor(oracle, nb, w, nb + 2)
     q, r = tf.poly_divide(a, b, width=w, batch=batch)
-    dq = torch.zeros(max(q.size, 1), dtype=torch.int64, device="cuda")[:q.size]
-    dr = torch.zeros(max(r.size, 1), dtype=torch.int64, device="cuda")[:r.size]
+    dq = torch.full((max(q.size, 1),), -1, dtype=torch.int64, device="cuda")[:q.size]  # (not canonical: a word never stored shows)
+    dr = torch.full((max(r.size, 1),), -1, dtype=torch.int64, device="cuda")[:r.size]
     st = torch.zeros(1, dtype=torch.int32, device="cuda")
     tf.device.divide(_cuda(a), na, _cuda(b), dq if q.size else None, dr if r.size else None, batch=batch, width=w, status=st)
     torch.cuda.synchronize()

@@ -56,7 +56,7 @@ def gpu_squeeze(tf, k):
     def run(st, lo, hi):
         import torch
 
-        d, out = to_dev(st[lo:hi]), torch.zeros((hi - lo) * k * 10, dtype=torch.int64, device="cuda")
+        d, out = to_dev(st[lo:hi]), torch.full(((hi - lo) * k * 10,), -1, dtype=torch.int64, device="cuda")  # (not canonical: a word never stored shows)
         tf.device.tip5_sponge_squeeze(d, out)
         return to_host(d).reshape(-1, 16), to_host(out).reshape(hi - lo, k, 10)
     return run
@@ -66,7 +66,7 @@ def gpu_scalars(tf, n):
     def run(st, lo, hi):
         import torch
 
-        d, out = to_dev(st[lo:hi]), torch.zeros((hi - lo) * n * 3, dtype=torch.int64, device="cuda")
+        d, out = to_dev(st[lo:hi]), torch.full(((hi - lo) * n * 3,), -1, dtype=torch.int64, device="cuda")
         tf.device.tip5_sponge_sample_scalars(d, out)
         return to_host(d).reshape(-1, 16), to_host(out).reshape(hi - lo, n, 3)
     return run
@@ -186,10 +186,10 @@ def test_fresh_sponge_then_pad_and_absorb_all_is_hash_varlen_rows(tf, oracle, co
     import torch
 
     rows = to_dev(oracle.fill_random(count * 33, 0x560))
-    d = torch.empty(16 * count, dtype=torch.int64, device="cuda")
+    d = torch.full((16 * count,), -1, dtype=torch.int64, device="cuda")  # (not canonical: a word never stored shows)
     tf.device.tip5_sponge_init_(d)
     tf.device.tip5_sponge_pad_and_absorb_all_(d, rows)
-    digests = torch.empty(5 * count, dtype=torch.int64, device="cuda")
+    digests = torch.full((5 * count,), -1, dtype=torch.int64, device="cuda")
     tf.device.tip5_hash_varlen_rows(rows, 33, digests)
     assert np.array_equal(to_host(d).reshape(count, 16)[:, :5], to_host(digests).reshape(count, 5))
 
