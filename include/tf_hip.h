@@ -843,17 +843,17 @@ void tf_set_ntt_small_launch(int mode);
 void tf_set_ntt_two_pass(int mode);
 /* The latency-shaped kernels (8 elements per thread, radix-8 stages through LDS) instead of the 32-elements-per-thread
  * pass kernels: ntt_lat_kernel for 64 .. 4096-point transforms in calls of up to 2^22 words (BFieldElement; 3 * 2^19 words
- * XFieldElement), ntt_lat2_kernel for 2^13 .. 2^20-point transforms in calls below a per-length threshold (tf_ntt.hip:
+ * XFieldElement), ntt_lat2_kernel for 2^13 .. 2^20-point transforms in calls below a per-length threshold (tf_plan.hip:
  * lat_wanted / lat2_wanted hold the measured crossovers).  -1 = automatic (default), 0 = never, 1 = whenever the shape allows. */
 void tf_set_ntt_latency_kernel(int mode);
-/* Number of transform-kernel launches one plain tf_ntt_*_dev call enqueues for this shape, by the planner's own predicates in
- * the planner's order (tiny / rows / latency-shaped kernels, whole-transform-per-workgroup kernels, tiles x passes of
+/* Number of transform-kernel launches one plain tf_ntt_*_dev call enqueues for this shape: read from the very plan such a call
+ * executes (plan_ntt, tf_plan.hip -- tiny / rows / latency-shaped kernels, whole-transform-per-workgroup kernels, tiles x passes of
  * ntt_pass_kernel, the narrow-tile three-pass plan of small 2^21 / 2^22 calls).  Diagnostic; bench.py uses it to turn a
  * HIP-event interval into an average launch duration.  Table builders of a first call are not counted. */
 int tf_ntt_launch_count(size_t n, size_t batch, int width);
 /* Planner introspection (no device needed): number of global passes of one n-point transform (0 for lengths ntt rejects)
  * and log2 of each pass's radix in log2_radix_out[0..3] (unused entries 0).  The radices multiply to n.  This is the plan of a
- * LARGE call (enough work for 512-thread tiles); a call small enough for the narrow tiles -- e.g. ONE 2^21-point BFieldElement
+ * LARGE call (plan_ntt with the latency-shaped kernels and the narrow tiles ruled out: enough work for 512-thread tiles); a call small enough for the narrow tiles -- e.g. ONE 2^21-point BFieldElement
  * slice -- runs 2^21 / 2^22 points on the three-pass plan instead of {10, 11} / {11, 11}: tf_ntt_launch_count(n, batch, width)
  * is exact for a given batch. */
 int tf_ntt_plan(size_t n, int width, int* log2_radix_out);

@@ -270,6 +270,40 @@ def test_planner_splits_are_valid_for_every_length(tf):
     assert lib.tf_ntt_launch_count(64, 1 << 22, 1) == 1
 
 
+def test_plans_match_the_recorded_table(tf):
+    """Host logic, no device: tf_ntt_plan and tf_ntt_launch_count answer what tests/golden/ntt_plans.json recorded (written by
+    tools/make_ntt_plan_table.py) for every length, both widths, four batch sizes, by default and under each test hook -- the table
+    moves only when a plan is changed on purpose."""
+    import ctypes as C
+    import json
+    lib = tf._lib.lib()
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "ntt_plans.json")))
+    log_ns, widths, batches = table["log_n"], table["widths"], table["batches"]
+    assert log_ns == list(range(1, 32)) and widths == [1, 3] and batches == [1, 64, 4096, 1 << 22] and len(table["settings"]) == 11
+    radix = (C.c_int * 4)()
+    keep_tile = lib.tf_get_ntt_tile_bytes()
+    lib.tf_set_ntt_tile_bytes(0)  # the built-in budget, whatever TF_NTT_TILE_BYTES says
+    checked = 0
+    try:
+        for s in table["settings"]:
+            if s["hook"]:
+                getattr(lib, s["hook"])(s["arg"])
+            try:
+                for wi, width in enumerate(widths):
+                    for li, log_n in enumerate(log_ns):
+                        passes = lib.tf_ntt_plan(1 << log_n, width, radix)
+                        assert list(radix)[:passes] == s["plans"][wi][li] and all(v == 0 for v in list(radix)[passes:]), (s["hook"], s["arg"], width, log_n)
+                        got = [lib.tf_ntt_launch_count(1 << log_n, b, width) for b in batches]
+                        assert got == s["launches"][wi][li], (s["hook"], s["arg"], width, log_n, got)
+                        checked += 1 + len(batches)
+            finally:
+                if s["hook"]:
+                    getattr(lib, s["hook"])(s["restore"])
+    finally:
+        lib.tf_set_ntt_tile_bytes(keep_tile)
+    assert checked == 11 * 2 * 31 * 5
+
+
 def test_batch_evaluation_router_is_host_logic_with_the_measured_crossovers(tf):
     """tf_batch_eval_plan (host logic, no device): the router of tf_poly_batch_evaluate_* picks the zerofier tree where it measured
     faster than Horner (profiles/r03_batch_eval_fine_w*.txt) and Horner elsewhere; the test hook forces either route; a tree never

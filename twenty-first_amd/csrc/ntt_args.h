@@ -1,5 +1,6 @@
 // ntt_args.h -- the argument records of the ntt_kernels.h launchers that other translation units fill in (the zerofier-tree
-// walks of tf_poly.hip run their transforms through the latency-shaped kernels and the one-launch-per-level kernels of tf_ntt.hip).
+// walks of tf_poly.hip run their transforms through the latency-shaped kernels and the one-launch-per-level kernels of tf_lat.hip;
+// which transform route a call takes is decided in tf_plan.hip, whose ntt_plan.h holds the planner's own plain structs).
 // Plain data: no device code here.
 #pragma once
 

@@ -24,7 +24,7 @@
 // XFE slices ([c0,c1,c2] per element, x_field_element.rs:56-59) are three interleaved BFE columns
 // with the same twiddles (ntt.rs:203-207, x_field_element.rs:540-548): L = 3 words per element.
 //
-// Kernels in this file and the lengths they serve (planner: run_ntt in tf_ntt.hip):
+// Kernels in this file and the lengths they serve (planner: plan_ntt in tf_plan.hip; run_ntt in tf_ntt.hip executes the plan):
 //   ntt_tiny_kernel    n <= 16                the reference's radix-2 sweeps, one transform per thread
 //   ntt_rows32w_kernel n == 32                wave-private tiles of 64 (limb-)transforms through LDS, one per lane, no barrier
 //   ntt_pass_kernel    32 <= n <= 1024        one pass, rows of T whole transforms per workgroup

@@ -313,43 +313,22 @@ int tf_batch_eval_plan(size_t n_coeffs, size_t n_points, size_t batch, int width
 }
 int tf_ntt_plan(size_t n, int width, int* log2_radix_out) {
     if (check_len(n) || n <= 1 || (width != 1 && width != 3) || !log2_radix_out) return 0;
-    const int log_n = ilog2(n);
     for (int i = 0; i < 4; ++i) log2_radix_out[i] = 0;
-    static const bool no_block = ab_env("TF_NTT_NO_BLOCK") != nullptr;
-    static const bool no_xfe_block = ab_env("TF_NTT_NO_XFE_BLOCK") != nullptr;
-    if (log_n <= 10 || (log_n <= (width == 1 ? 14 : (no_xfe_block ? 10 : 12)) && !no_block && g_min_passes.load(std::memory_order_relaxed) == 0)) {
-        log2_radix_out[0] = log_n;
+    // a plain transform in a call with enough work for the wide tiles (a real call with little work may take a latency-shaped route instead)
+    const NttPlan plan = plan_ntt_large(n, width);
+    if (plan.route != NttRoute::Passes) {  // one pass, or the whole transform per workgroup
+        log2_radix_out[0] = ilog2(n);
         return 1;
     }
-    int P = pass_count(log_n);
-    int a[4] = {0, 0, 0, 0};
-    choose_split(log_n, P, width, a);
-    // a plain transform of 2^21 / 2^22 points with enough work for the wide tiles: two passes, 2^11 = a pass of paired 1024-point halves
-    if (pre2_plan_ok(log_n, width, n, 1, false, -1, false, false, false)) P = 2, pre2_split(log_n, a);
-    for (int i = 0; i < P; ++i) log2_radix_out[i] = a[i];
-    return P;
+    for (int i = 0; i < plan.P; ++i) log2_radix_out[i] = plan.a[i];
+    return plan.P;
 }
 
 int tf_ntt_launch_count(size_t n, size_t batch, int width) {
-    // the same predicates, in the same order, as run_ntt (tf_ntt.hip) for a plain in-place call
     if (check_len(n) || n <= 1 || batch == 0 || (width != 1 && width != 3)) return 0;
-    const int log_n = ilog2(n);
-    read_env();
-    if (log_n <= 5 || (log_n == 6 && width == 1 && batch >= 64)) return 1;                                 // ntt_rows32w_kernel (a grid-stride walk) / ntt_tiny_kernel
-    if (g_min_passes.load(std::memory_order_relaxed) == 0) {
-        if (lat_wanted(log_n, batch, width)) return (int)((batch + (size_t(1) << 22) - 1) >> 22);          // ntt_lat_kernel
-        if (lat2_wanted(log_n, batch, width)) return 2;                                                    // ntt_lat2_kernel: column pass + last pass
-    }
-    if (log_n <= 10) return (int)((batch + (size_t(1) << 24) - 1) >> 24);
-    int radix[4];
-    if (tf_ntt_plan(n, width, radix) == 1) return 1;  // whole transform per workgroup (BFE 2^11 .. 2^14, XFE 2^11 / 2^12)
-    const size_t poly_bytes = n * size_t(width) * sizeof(u64);
-    size_t tb = std::min(std::max<size_t>(1, g_tile_bytes / poly_bytes), batch);
-    const size_t tiles = (batch + tb - 1) / tb;
-    int P = pass_count(log_n);
-    if (P == 4) return (int)(tiles * 3 + batch);  // the last pass of a four-pass plan is launched per polynomial
-    if (!small_launch_for(n, 1, batch, width, -1) && pre2_plan_ok(log_n, width, n, 1, false, -1, false, false, false)) P = 2;
-    return (int)(tiles * P);
+    NttShape s;  // a plain in-place call
+    s.n = n, s.batch = batch, s.L = width;
+    return plan_ntt(s).launches;
 }
 
 int tf_ntt_bfe(uint64_t* x, size_t n, size_t batch, int inverse) try { return ntt_host(x, n, batch, 1, inverse); } TF_ABI_CATCH

@@ -1,6 +1,7 @@
 // tf_internal.h -- what the translation units of libtf_hip.so share on the host side (nothing here is part of the ABI: the
 // library is built with -fvisibility=hidden and only the tf_* functions of include/tf_hip.h are exported).
-//   tf_ntt.hip    device context, table caches, the pass planner and every launcher of ntt_kernels.h
+//   tf_plan.hip   the NTT planner (ntt_plan.h): route, passes, radices, tiles and streams of a call -- host logic only, no kernel
+//   tf_ntt.hip    device context, table caches, run_ntt (plan, then execute) and every launcher of ntt_kernels.h
 //   tf_lat.hip    the latency-shaped transforms and the one-launch-per-level kernels of the tree walks (lat_kernels.h)
 //   tf_tip5.hip   Tip5 / Merkle launchers (tip5_kernels.h), authentication structures
 //   tf_poly.hip   the callers on either side of the path, SURVEY 8(f) (poly_kernels.h)
@@ -35,6 +36,7 @@
 #pragma GCC visibility pop
 #include "gl64.h"
 #include "ntt_args.h"
+#include "ntt_plan.h"
 #include "tf_guard.h"
 
 namespace tfi {
@@ -69,7 +71,6 @@ constexpr const char* ab_env(const char*) { return nullptr; }
 #endif
 
 u64 root_of_unity_mont(int log_n);
-int ilog2(size_t v);
 
 // ------------------------------------------------------------------------------------ per-device context
 struct DeviceCtx {
@@ -97,6 +98,13 @@ struct DeviceCtx {
 constexpr int kMaxDevices = 64;
 extern DeviceCtx g_ctx[kMaxDevices];
 
+// ------------------------------------------------------------------------------------ tf_plan.hip
+// the planner's functions: ntt_plan.h.  Configuration (tf_set_* hooks of the ABI; TF_* environment variables read once by read_env):
+constexpr int kMaxPipe = 4;
+void read_env();
+extern size_t g_tile_bytes;
+extern std::atomic<int> g_pipe, g_nt, g_min_passes, g_lat_mode, g_pre2_mode, g_small_launch_mode;
+
 // ------------------------------------------------------------------------------------ tf_ntt.hip
 int current_ctx(DeviceCtx** out);
 int device_cus();  // compute units of the calling thread's CURRENT device (cached per device; 256 if the runtime will not say)
@@ -104,15 +112,10 @@ hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream);  // ev
 int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx::ScratchBlock* out);
 void scratch_release(DeviceCtx* ctx, DeviceCtx::ScratchBlock blk, hipStream_t stream);
 int release_caches(DeviceCtx* ctx);
-void read_env();
 int ensure_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done_mask);
 int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, const u64** out, bool* temp, size_t cosets = 1, int log_order = 0);
 void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t stream);  // after the launches that read a table get_pow_table returned
 
-// configuration (tf_set_* hooks of the ABI; TF_* environment variables read once by read_env)
-constexpr int kMaxPipe = 4;
-extern size_t g_tile_bytes;
-extern std::atomic<int> g_pipe, g_nt, g_min_passes, g_lat_mode, g_pre2_mode, g_small_launch_mode;
 #ifdef TF_AB_BUILD
 extern std::atomic<int> g_chain;
 extern unsigned long long* g_dbg_buf;
@@ -127,12 +130,6 @@ class DevTemp;  // tf_temp.h
 int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, DevTemp* own);
 
 int check_len(size_t n);
-int pass_count(int log_n);
-void choose_split(int log_n, int P, int L, int (&a)[4]);
-void pre2_split(int log_n, int (&a)[4]);
-void pre2_split(int log_n, int (&a)[4], bool c8);
-bool pre2_plan_ok(int log_n, int L, size_t n, size_t cosets, bool has_in2, long long n_out, bool inverse, bool load_work, bool store_scale);
-bool can_truncate(size_t n, int L);
 int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, size_t n, size_t batch, int L, bool inverse,
             const u64* pre_scale, long long n_coeffs, hipStream_t stream, const u64* post_scale = nullptr, size_t cosets = 1,
             const u64* in2 = nullptr, long long n_out = -1, const u64* coset_offset = nullptr);
@@ -140,9 +137,6 @@ int ntt_dev(u64* d_x, size_t n, size_t batch, int L, int inverse, void* stream);
 int coset_eval_dev(const u64* d_coeffs, size_t n_coeffs, u64 offset_raw, u64* d_out, size_t order, size_t batch, int L, void* stream);
 // ------------------------------------------------------------------------------------ tf_lat.hip
 // latency-shaped transforms and the one-launch-per-level kernels of the zerofier-tree walks
-bool small_launch_for(size_t n, size_t cosets, size_t batch, int L, long long n_out);
-bool lat_wanted(int log_n, size_t batch, int L);
-bool lat2_wanted(int log_n, size_t batch, int L);
 int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
                 long long n_coeffs, const u64* in2, hipStream_t stream, const u64* pre_scale = nullptr, const u64* post_scale = nullptr);
 int launch_lat(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,

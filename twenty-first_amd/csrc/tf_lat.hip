@@ -1,7 +1,7 @@
 // tf_lat.hip -- launchers of the latency-shaped kernels of libtf_hip.so (lat_kernels.h): ntt_lat_kernel / ntt_lat2_kernel for
-// calls with little work, and the one-launch-per-level kernels of the zerofier-tree walks and build.  The planner (tf_ntt.hip:
-// run_ntt) and the tree orchestration (tf_poly.hip) decide WHEN; the thresholds they ask for live here (lat_wanted, lat2_wanted,
-// tree_level_wanted, tree_build_level_wanted) next to the measurements they come from.
+// calls with little work, and the one-launch-per-level kernels of the zerofier-tree walks and build.  The planner (tf_plan.hip:
+// plan_ntt, with the thresholds lat_wanted / lat2_wanted) and the tree orchestration (tf_poly.hip) decide WHEN; the tree walks'
+// thresholds live here (tree_level_wanted, tree_build_level_wanted) next to the measurements they come from.
 #include "tf_temp.h"
 #include "lat_kernels.h"
 
@@ -63,23 +63,7 @@ int launch_lat_dir(int log_n, const tfk::NttLatArgs& a, hipStream_t s) {
     }
     return TF_ERR_HIP;
 }
-// When: the call holds too little work to fill the chip with 32-element threads (measured crossover, tools/lat_sweep.py).
-std::atomic<int> g_lat_mode{-1};  // tf_set_ntt_latency_kernel: -1 automatic (TF_NTT_NO_LAT disables), 0 never, 1 whenever the shape allows
-bool lat_wanted(int log_n, size_t batch, int L) {
-    static const bool off = ab_env("TF_NTT_NO_LAT") != nullptr;  // A/B switch
-    // measured crossover against the pass / block kernels (tools/lat_sweep.py, profiles/r03_lat_sweep_*.txt): 2.0 - 2.9 x faster up
-    // to 2^20 words per call, level at 2^22 words (BFieldElement) / 1.5 x 2^20 words (XFieldElement: its loads step 24 bytes)
-    static const long long env_limit = [] {
-        const char* e = ab_env("TF_NTT_LAT_MAX_WORDS");
-        return e ? atoll(e) : 0ll;
-    }();
-    const long long limit = env_limit ? env_limit : (L == 1 ? (1ll << 22) : (3ll << 19));
-    const int mode = g_lat_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || (mode < 0 && off)) return false;
-    if (log_n < 6 || log_n > 12) return false;
-    if (mode == 1) return true;
-    return (long long)(batch * size_t(L)) << log_n <= limit;
-}
+// (when: lat_wanted, tf_plan.hip)
 // mods (tree walks only): the load / store modifier fields of NttLatArgs; such calls are one launch (batch < 2^22)
 int launch_lat(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
                long long n_coeffs, const u64* in2, hipStream_t stream, const tfk::NttLatArgs* mods, const u64* pre_scale, const u64* post_scale) {
@@ -108,8 +92,6 @@ int launch_lat(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long lo
     }
     return rc;
 }
-
-std::atomic<int> g_min_passes{0};  // tf_set_ntt_min_passes
 
 // ---- one launch per LEVEL of a small zerofier-tree walk (tree_down_level_kernel / tree_up_level_kernel, BFieldElement)
 template <int LOGN, bool UP>
@@ -276,24 +258,7 @@ int launch_lat2_dir(int log_n, const tfk::NttLat2Args& a, size_t batch, hipStrea
     }
     return TF_ERR_HIP;
 }
-bool lat2_wanted(int log_n, size_t batch, int L) {
-    static const bool off = ab_env("TF_NTT_NO_LAT") != nullptr || ab_env("TF_NTT_NO_LAT2") != nullptr;  // A/B switches
-    static const long long env_limit = [] {
-        const char* e = ab_env("TF_NTT_LAT2_MAX_WORDS");
-        return e ? atoll(e) : 0ll;
-    }();
-    const int mode = g_lat_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || (mode < 0 && off)) return false;
-    if (log_n < 13 || log_n > 20) return false;
-    if (mode == 1) return true;
-    // measured crossover against the pass / block kernels, words per call (tools/lat_sweep.py 13 20, profiles/r03_lat2_sweep_*.txt):
-    // one 2^16-point slice 33 -> 16 us; the win ends where the chip fills, and earlier for the longest lines (a 1024-point line
-    // leaves two lines per workgroup: 16-byte segments)
-    static const long long lim1[8] = {1ll << 21, 1ll << 21, 1ll << 21, 1ll << 21, 1ll << 21, 1ll << 20, 1ll << 20, 1ll << 20};  // log_n = 13 .. 20
-    static const long long lim3[8] = {3ll << 20, 3ll << 20, 3ll << 19, 3ll << 20, 3ll << 19, 3ll << 18, 0, 0};
-    const long long limit = env_limit ? env_limit : (L == 1 ? lim1 : lim3)[log_n - 13];
-    return (long long)(batch * size_t(L)) << log_n <= limit;
-}
+// (when: lat2_wanted, tf_plan.hip)
 int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
                 long long n_coeffs, const u64* in2, hipStream_t stream, const u64* pre_scale, const u64* post_scale) {
     const int a1 = (log_n + 1) / 2, a2 = log_n - a1;

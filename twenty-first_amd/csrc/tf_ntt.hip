@@ -1,4 +1,5 @@
-// tf_ntt.hip -- device context, table caches and the NTT pass planner of libtf_hip.so: every launcher of ntt_kernels.h.
+// tf_ntt.hip -- device context, table caches and run_ntt of libtf_hip.so: every launcher of ntt_kernels.h.  What a call runs is
+// decided in tf_plan.hip (plan_ntt); run_ntt executes the plan.
 //
 // One process drives one or more MI355X devices; all state is per HIP device and guarded by a mutex,
 // kernels are enqueued on the caller's stream, and nothing here synchronises the device except the
@@ -35,13 +36,6 @@ int abi_caught(const char* what, int status) noexcept {
 // ------------------------------------------------------------------------------------ field helpers (host)
 // w_n = 7^((p-1)/n): equals every entry of PRIMITIVE_ROOTS (b_field_element.rs:43-78).
 u64 root_of_unity_mont(int log_n) { return gl::mont_pow(gl::to_mont(7), (gl::P - 1) >> log_n); }
-
-int ilog2(size_t v) {
-    int l = 0;
-    while ((size_t(1) << l) < v) ++l;
-    return l;
-}
-
 
 // ------------------------------------------------------------------------------------ per-device context
 // (struct DeviceCtx: tf_internal.h)
@@ -268,31 +262,6 @@ int release_caches(DeviceCtx* ctx) {
     if (ctx->pool) (void)hipMemPoolTrimTo(ctx->pool, 0);  // the cached stream-ordered temporaries too
     (void)hipGetLastError();
     return TF_OK;
-}
-
-size_t g_tile_bytes = 0;
-// Pipelined tiles: with g_pipe = K > 1 the batch tiles of a multi-pass transform are dealt round-robin to K side streams,
-// each with its own scratch tile, so that the column pass of tile t + 1 runs beside the transposing pass of tile t: the
-// launches' tails fill each other and a tile sized for the 256 MiB Infinity Cache is re-read out of it.  1 = one stream.
-std::atomic<int> g_pipe{0};
-std::atomic<int> g_nt{-1};  // TF_NTT_NT / tf_set_ntt_nt: bit 0 non-temporal input loads (first pass), bit 1 non-temporal output stores (last pass)
-std::once_flag g_env_once;
-void read_env() {
-    std::call_once(g_env_once, [] {
-        if (g_tile_bytes == 0) {
-            const char* s = getenv("TF_NTT_TILE_BYTES");
-            g_tile_bytes = s ? strtoull(s, nullptr, 10) : (size_t(2048) << 20);
-            if (g_tile_bytes == 0) g_tile_bytes = size_t(2048) << 20;
-        }
-        if (g_pipe.load() == 0) {  // 0 = automatic (run_ntt decides by plan); TF_NTT_PIPE / tf_set_ntt_pipe pin it
-            const char* s = getenv("TF_NTT_PIPE");
-            if (s && atoi(s) > 0) g_pipe.store(std::min(atoi(s), kMaxPipe));
-        }
-        if (g_nt.load() < 0) {
-            const char* s = ab_env("TF_NTT_NT");
-            g_nt.store(s ? (atoi(s) & 3) : 0);
-        }
-    });
 }
 
 int upload_table(const std::vector<u64>& host, u64** dev) {
@@ -603,7 +572,6 @@ int build_pow_tables(u64 offset_raw, u64 w, size_t cosets, size_t n, u64* d, hip
 // cosets = 1: out[j] = offset^j, j < n.  cosets = C > 1 (blown-up coset evaluation, see run_ntt; C <= kMaxCosetSplit): C tables
 // back to back, out[c * n + j] = (offset * w_{C * len}^c)^j with len the power-of-two transform length the n coefficients are
 // padded to.  At most 16 tables / kPowCacheBudget bytes stay cached; anything beyond is a stream-ordered temporary (*temp).
-constexpr size_t kMaxCosetSplit = 64;
 int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, const u64** out, bool* temp, size_t cosets,
                   int log_order) {
     *temp = false;
@@ -731,13 +699,15 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
     return TF_OK;
 }
 
-// ------------------------------------------------------------------------------------ NTT planner
+// ------------------------------------------------------------------------------------ NTT pass launches
+// (which passes a call runs: plan_ntt, tf_plan.hip; here a planned pass becomes kernel arguments and a launch)
 struct Launch {
     tfk::NttPassArgs a;
     unsigned tiles;
     unsigned threads;
     size_t lds_bytes;
     bool bad_geometry = false;  // planner self-check failed: launch_pass refuses the launch
+    bool narrow = false;        // planned with the narrow tiles of a small call (NttPlan::narrow): the generic last pass
 };
 
 int pad_to_residue(int base, int residue) {  // smallest s >= base with s == residue (mod 32)
@@ -745,47 +715,30 @@ int pad_to_residue(int base, int residue) {  // smallest s >= base with s == res
     return base + r;
 }
 
-// Workgroup geometry (tunable for A/B runs through TF_NTT_WG_THREADS = 256 | 512):
-//   512 threads: 16 columns per tile (128-byte segments), 64 KiB exchange rounds, 2 workgroups per CU;
-//   256 threads:  8 columns per tile (64-byte segments, adjacent tiles paired on one XCD), 32 KiB rounds, 4 per CU.
-// A call with too little work to fill the chip with 512-thread tiles (a single slice of <= 2^20 points: 64 tiles for 256 CUs) is
-// planned with 256-thread workgroups and the generic last pass instead -- twice as many tiles of half the width: 2^16 44 -> 37 us,
-// 2^18 47.5 -> 39.7, 2^20 51.8 -> 43.8 us per call; from 2^22 words per call on the wide tiles win (tools/small_batch.py).
-// run_ntt sets the mode for the duration of one call (thread-local: the ABI is re-entrant).
-thread_local bool t_small_launch = false;
-std::atomic<int> g_small_launch_mode{-1};  // tf_set_ntt_small_launch: -1 automatic, 0 never, 1 always (tests)
-int wg_env() {
-    static const int v = [] {
-        const char* e = ab_env("TF_NTT_WG_THREADS");
-        return (e && atoi(e) == 256) ? 256 : ((e && atoi(e) == 512) ? 512 : 0);
-    }();
-    return v;
-}
-int wg_threads() {
-    if (wg_env()) return wg_env();
-    return t_small_launch ? 256 : 512;
-}
-int round_elems() {
+// Words per exchange round of a workgroup of g.wg threads (NttPlan::wg: 512, or 256 for the narrow tiles; tf_plan.hip has the
+// geometry and its measurements)
+int round_elems(const NttPlan& g) {
     static const int v = [] {
         const char* e = ab_env("TF_NTT_ROUND_ELEMS");
         const int r = e ? atoi(e) : 0;
         return r >= 1024 ? r : 0;
     }();
-    return v ? v : wg_threads() * 16;
+    return v ? v : g.wg * 16;
 }
 
 // thread / LDS geometry shared by all pass types: nc columns, exchanged in rounds of cpr columns
-void finish_geometry(Launch* l, int nc, int p2) {
+void finish_geometry(Launch* l, int nc, int p2, const NttPlan& g) {
     tfk::NttPassArgs& A = l->a;
     const int P2 = 1 << p2, R = 32 << p2;
     A.p2 = p2;
     A.nc = nc;
-    A.cpr = std::max(1, std::min(nc, round_elems() / R));
+    A.cpr = std::max(1, std::min(nc, round_elems(g) / R));
     A.nrounds = (nc + A.cpr - 1) / A.cpr;
     A.s2 = A.cpr;
     A.s3 = 1;
     A.s1 = pad_to_residue(P2 * A.cpr, A.cpr % 32);  // consecutive k1 rows land cpr banks apart: conflict-free reads
     l->threads = (unsigned)(nc * P2);
+    l->narrow = g.narrow;
     l->lds_bytes = size_t(32) * A.s1 * sizeof(u64);
     A.nc_magic = nc > 1 ? (u32)((u64(1) << 32) / (u64)nc + 1) : 0;  // umulhi(t, magic) == t / nc (nc == 1: kernel uses t)
     for (u32 t = 0; t < l->threads; ++t) {
@@ -796,13 +749,13 @@ void finish_geometry(Launch* l, int nc, int p2) {
 
 // Column pass: view [batch][outer][R][B*L words]; DFT along R for each of the B*L word-columns; same position in and out.
 // pre2: a = 11, run as pairs of 1024-point halves (ntt_kernels.h, PRE2): the kernel radix is 1024, the rows of a column 2048.
-Launch plan_column_pass(const u64* in, u64* out, long long in_bs, long long out_bs, size_t batch, long long outer, int a,
+Launch plan_column_pass(const NttPlan& g, const u64* in, u64* out, long long in_bs, long long out_bs, size_t batch, long long outer, int a,
                         long long B, int L, bool pre2 = false) {
     Launch l{};
     tfk::NttPassArgs& A = l.a;
     const int p2 = (pre2 ? a - 1 : a) - 5, P2 = 1 << p2;
     const long long R = 1ll << a, Bw = B * L;
-    int nc = (int)std::min<long long>(std::max(1, wg_threads() / P2), Bw);
+    int nc = (int)std::min<long long>(std::max(1, g.wg / P2), Bw);
     A.in = in;
     A.out = out;
     A.L = L;
@@ -831,7 +784,7 @@ Launch plan_column_pass(const u64* in, u64* out, long long in_bs, long long out_
         // table slice of one column tile = R rows x nc words; an XCD owns d2 / 8 column tiles and has a 4 MiB L2
         if (A.xcd_order) A.xcd_colfast = (size_t(A.d2 / 8) * size_t(R) * nc * sizeof(u64) <= (size_t(2) << 20)) ? 1 : 0;
     }
-    finish_geometry(&l, nc, p2);
+    finish_geometry(&l, nc, p2, g);
     l.tiles = (unsigned)(batch * outer * A.d2);
     if (pre2) {
         A.out_rs = 2 * Bw;  // kernel row k' of half h is row 2 k' + h of the 2048
@@ -845,20 +798,6 @@ Launch plan_column_pass(const u64* in, u64* out, long long in_bs, long long out_
     return l;
 }
 
-#ifdef TF_AB_BUILD
-std::atomic<int> g_ablate_cfg{-1};  // measurement only (TF_NTT_ABLATE=1|2 selects an ablated forward kernel; results are then garbage)
-int ablate_mode() {
-    int v = g_ablate_cfg.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = ab_env("TF_NTT_ABLATE");
-        v = e ? atoi(e) : 0;
-        g_ablate_cfg.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-#else
-constexpr int ablate_mode() { return 0; }  // the ablated kernels (no memory / no arithmetic / phase stamps) are laboratory instantiations
-#endif
 // The R = 1024 instantiations address memory through buffer resources: resource base + 32-bit per-thread offset + 32-bit
 // per-slot offset (ntt_kernels.h, buf_load).  A thread's row offset is at most 31 rows, a slot's at most 992 rows: with
 // row strides of rs words everything stays below 2^32 bytes when 1024 * rs * 8 (+ the tile's column span) does.
@@ -875,26 +814,9 @@ bool fits_buffer_offsets(const Launch& l) {
     return ok(l.a.in_rs, l.a.in_cs_hi, l.a.pre2_map ? (l.a.pre4_stw ? 4096ull : 2048ull) : rows) && ok(l.a.out_rs, l.a.out_cs_hi, rows) && ok(l.a.tw_rs, 0, rows);
 }
 
-// the specialised R = 1024 last-pass kernel (LAST1024) is available unless an A/B switch or an ablation run disables it
-bool last1024_enabled() {
-    static const bool off = ab_env("TF_NTT_NO_LAST1024") != nullptr;
-    return !off && ablate_mode() == 0 && !t_small_launch;
-}
-
-bool col_enabled() {
-    static const bool off = ab_env("TF_NTT_NO_COL") != nullptr;  // A/B switch
-    return !off;
-}
-
-// ... and its variant that multiplies on store (fast_coset_interpolate)
-bool scaled_last1024_enabled() {
-    static const bool off = ab_env("TF_NTT_NO_SCALED_LAST1024") != nullptr;  // A/B switch
-    return !off;
-}
-
 // rows (independent DFTs) per tile for the passes whose columns are whole rows of elements
-int rows_per_tile(int P2, int L, long long limit) {
-    int nc_max = std::max(1, wg_threads() / P2);
+int rows_per_tile(const NttPlan& g, int P2, int L, long long limit) {
+    int nc_max = std::max(1, g.wg / P2);
     int T = std::max(1, nc_max / L);
     return (int)std::min<long long>(T, limit);
 }
@@ -906,13 +828,13 @@ int rows_per_tile(int P2, int L, long long limit) {
 // k2 + N2 * k3 on the output side; the kernel's batch index carries k2 and its rho index carries k3.
 // words > 0: word-granular tiles of `words` adjacent output WORDS (whole 128-byte lines) instead of T whole elements; for
 // XFieldElement rows (24-byte elements) a tile then starts and ends inside an element (NttPassArgs::wtiles).
-Launch plan_transpose_pass(const u64* in, u64* out, long long in_bs, long long out_bs, size_t batch, int a, long long N1,
+Launch plan_transpose_pass(const NttPlan& g, const u64* in, u64* out, long long in_bs, long long out_bs, size_t batch, int a, long long N1,
                            long long Q, int L, long long split = 0, int words = 0, int pre = 1) {
     Launch l{};
     tfk::NttPassArgs& A = l.a;
     const int p2 = a - (pre == 4 ? 2 : (pre == 2 ? 1 : 0)) - 5, P2 = 1 << p2;
     const long long R = 1ll << a;  // elements per row (pre = 2 / 4: 2048 / 4096, transformed as two / four interleaved 1024-point classes)
-    int T = rows_per_tile(P2, L, N1);
+    int T = rows_per_tile(g, P2, L, N1);
     {
         // the kernel addresses its loads as uniform 64-bit base + 32-bit per-thread byte offset; the offset spans the
         // tile's T rows, Q * R * L words apart: keep it below 2^32 (only binds for n = 2^31)
@@ -957,7 +879,7 @@ Launch plan_transpose_pass(const u64* in, u64* out, long long in_bs, long long o
         A.js_i1 = N1 * split;
         batch = 1;
     }
-    finish_geometry(&l, nc, p2);
+    finish_geometry(&l, nc, p2, g);
     l.tiles = (unsigned)(batch * Q * A.d2);
     if (pre > 1) {
         A.pre2_in_off = 1024 * L;
@@ -972,11 +894,11 @@ Launch plan_transpose_pass(const u64* in, u64* out, long long in_bs, long long o
 }
 
 // Single pass (32 <= n <= 1024): a tile is T whole transforms, output in natural order at the same place.
-Launch plan_row_pass(const u64* in, u64* out, long long in_bs, long long out_bs, size_t batch, int a, int L) {
+Launch plan_row_pass(const NttPlan& g, const u64* in, u64* out, long long in_bs, long long out_bs, size_t batch, int a, int L) {
     Launch l{};
     tfk::NttPassArgs& A = l.a;
     const int p2 = a - 5, P2 = 1 << p2;
-    const int T = rows_per_tile(P2, L, (long long)batch);
+    const int T = rows_per_tile(g, P2, L, (long long)batch);
     const int nc = T * L;
     A.in = in;
     A.out = out;
@@ -997,7 +919,7 @@ Launch plan_row_pass(const u64* in, u64* out, long long in_bs, long long out_bs,
     A.n_out = -1;
     A.js_k = 1;  // single pass: output element index = k
     A.xcd_order = 0;
-    finish_geometry(&l, nc, p2);
+    finish_geometry(&l, nc, p2, g);
     static const bool no_gfast = ab_env("TF_NTT_NO_GFAST") != nullptr;  // A/B switch
     if (p2 >= 1 && !no_gfast) {
         // rows are contiguous: put the lanes along the row (8 * P2-byte pieces become P2 times longer).  Exchange layout
@@ -1105,7 +1027,7 @@ int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
     const bool std_geo = l.threads == 512 && l.a.nc == tfk::kR1024Nc && l.a.cpr == tfk::kR1024Cpr && l.a.nrounds == tfk::kR1024Rounds &&
                          l.a.s1 == tfk::kR1024S1 && l.a.s2 == tfk::kR1024Cpr && l.a.s3 == 1 && !l.a.gfast;
     const bool plain_last1024 = l.a.p2 == 5 && !l.a.post_tw && !l.a.gfast && !l.a.pre_scale && l.a.n_coeffs < 0 && !l.a.in2 &&
-                                (!l.a.post_scale || (inverse && scaled_last1024_enabled())) && last1024_enabled() && fits;
+                                (!l.a.post_scale || (inverse && scaled_last1024_enabled())) && last1024_enabled(l.narrow) && fits;
     if (l.a.p2 == 6) {
         // a 2048-point column pass in ONE workgroup of 2048 rows x 8 word-columns (ntt_kernels.h, ntt_col2048_kernel): planned by
         // run_ntt only, with exactly the geometry the kernel's immediates assume
@@ -1180,7 +1102,7 @@ int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
     }
     // last pass of a plain transform with R = 1024: specialised kernel (constant P2, stores fused with level 5)
     // (not for single-pass transforms: their stores run along the row as well, which only the gfast roles give -- 1.05 vs 1.20 ms)
-    const bool last1024 = l.a.p2 == 5 && !l.a.post_tw && last1024_enabled() && !l.a.gfast && fits;
+    const bool last1024 = l.a.p2 == 5 && !l.a.post_tw && last1024_enabled(l.narrow) && !l.a.gfast && fits;
     static const bool no_r1024 = ab_env("TF_NTT_NO_R1024") != nullptr;  // A/B switch
     const bool r1024 = l.a.p2 == 5 && l.a.post_tw && g_ablate == 0 && !no_r1024 && fits && std_geo;  // column pass with R = 1024
     if (last1024) {  // this instantiation lays its exchange buffer out itself (32 x 289 words, ntt_kernels.h)
@@ -1341,302 +1263,178 @@ int launch_block(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long 
 
 // (launchers of the latency-shaped kernels: tf_lat.hip)
 
-// Experiment switches for tools/split3.py: looked up on every call only when TF_NTT_EXPERIMENT is set at load time
-// (the sweep tool changes them while the process runs); otherwise the planner never touches the environment.
-const char* exp_env(const char* name) {
-    static const bool enabled = ab_env("TF_NTT_EXPERIMENT") != nullptr;
-    return enabled ? ab_env(name) : nullptr;
+// ------------------------------------------------------------------------------------ run_ntt: plan, then execute
+// One transform call as run_ntt received it: what the route executors below share.
+struct NttCall {
+    DeviceCtx* ctx;
+    const u64* in;
+    u64* out;
+    long long in_bs, out_bs;
+    size_t n, batch;
+    int L;
+    bool inverse;
+    const u64* pre_scale;
+    long long n_coeffs;
+    hipStream_t stream;
+    const u64* post_scale;
+    size_t cosets;
+    const u64* in2;
+    long long n_out;
+    const u64* coset_offset;
+    int log_n;
+};
+
+// n <= 16: one thread per transform
+int run_tiny(const NttCall& c) {
+    const u64* tw = nullptr;
+    TRY(get_tiny_table(c.ctx, c.log_n, c.inverse, &tw));
+    tfk::NttTinyArgs A{};
+    A.in = c.in;
+    A.out = c.out;
+    A.tw = tw;
+    A.pre_scale = c.pre_scale;
+    A.post_scale = c.post_scale;
+    A.n_coeffs = c.n_coeffs;
+    A.in_bs = c.in_bs;
+    A.out_bs = c.out_bs;
+    A.count = (long long)c.batch * c.L;
+    A.scale = (c.inverse && c.log_n > 0) ? gl::mont_inverse(gl::to_mont(u64(c.n))) : 0;
+    A.log_n = c.log_n;
+    A.L = c.L;
+    const long long blocks = (A.count + 255) / 256;
+    hipLaunchKernelGGL(tfk::ntt_tiny_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream, A);
+    HIPCHK(hipGetLastError());
+    return TF_OK;
 }
 
-int pass_count(int log_n) {  // global passes of a transform with log_n > 10
-    int P = log_n <= 20 ? 2 : (log_n <= 30 ? 3 : 4);
-    const int want = g_min_passes.load(std::memory_order_relaxed);  // test hook: deeper plans at small sizes
-    if (want > P && want <= 4 && log_n >= 5 * want) P = want;
-    return P;
-}
-
-// Radix split of a multi-pass plan: a[0..P-1], sum = log_n, every a[i] in [5, 10].
-void choose_split(int log_n, int P, int L, int (&a)[4]) {
-    {
-        // The last pass gets the largest radix it can (R = 1024 whenever possible: the specialised kernel with constant P2
-        // and stores fused into level 5, 128-byte output segments); the column passes share the rest evenly, larger first.
-        // Measured against the even split (tools/split3.py, 2^28 words per call): 2^15 1.92 vs 2.62 ms, 2^18 2.20 vs 2.48,
-        // 2^22 3.18 vs 3.49, 2^24 3.31 vs 4.15, 2^26 3.58 vs 3.99.
-        // XFieldElement slices (L = 3) follow the same rule for n = 2^15, 2^20 and n >= 2^23 now that the R = 1024 kernel tiles
-        // their rows by whole 128-byte lines (tools/xfe_sweep.sh: 2^15 1.62 vs 1.83 ms, 2^23 2.62 vs 2.71, 2^25 2.71 vs 2.86 per
-        // 3 * 2^26 words); the sweep still prefers R = 32 for n < 2^15 and R = 512 for 2^16 .. 2^19 (all within 1 % of R = 1024).
-        int last = std::min(10, log_n - 5 * (P - 1));
-        // (round 5, profiles/r05_xfe_split2_sweep.txt: 2^13 has no better split than (8, 5) -- 1.61 ms against 1.61-1.75 for every other --
-        // it is simply the first length that no longer fits one workgroup's LDS; 2^14 prefers (5, 9): 1.325 vs 1.367 ms)
-        if (L == 3 && P == 2 && log_n < 20 && log_n != 15) last = log_n < 14 ? 5 : 9;
-        a[P - 1] = last;
-        int rest = log_n - last;
-        if (P == 3 && last == 10 && log_n <= (L == 3 ? 25 : 23)) {
-            // (log_n - 15, 5, 10): an exchange-free radix-32 pass in the middle (tools/split3.py: XFE 2^21 2.26 vs 2.33 ms,
-            // 2^23 2.34 vs 2.45, 2^25 2.49 vs 2.51 per 3 * 2^26 words; BFE 2^22 2.90 vs 3.04, 2^23 3.01 vs 3.09 per 2^28)
-            a[1] = 5;
-            a[0] = rest - 5;
-            // BFieldElement 2^21 / 2^22: the radix-32 pass first, (5, log_n - 15, 10) -- since the column passes run lazy networks
-            // through buffer addressing (COL) the order matters only there: 2^21 2.49 vs 2.71 ms, 2^22 2.54 vs 2.59 ms per 2^28
-            // words; from 2^23 on and for XFieldElement slices both orders measure the same (tools/split3_ab.py)
-            if (L == 1 && log_n <= 22) a[0] = 5, a[1] = rest - 5;
-        } else {
-            for (int i = 0; i + 1 < P; ++i) {
-                a[i] = (rest + (P - 1 - i) - 1) / (P - 1 - i);
-                rest -= a[i];
-            }
-        }
-        if (const char* e2 = exp_env("TF_NTT_SPLIT2")) {  // experiment: a0 for two-pass plans
-            const int x0 = atoi(e2);
-            if (P == 2 && x0 >= 5 && x0 <= 10 && log_n - x0 >= 5 && log_n - x0 <= 10) a[0] = x0, a[1] = log_n - x0;
-        }
-        if (const char* e = exp_env("TF_NTT_SPLIT3")) {  // experiment: "a0,a1" for three-pass plans
-            int x0 = 0, x1 = 0;
-            if (P == 3 && sscanf(e, "%d,%d", &x0, &x1) == 2 && x0 >= 5 && x0 <= 10 && x1 >= 5 && x1 <= 10 && log_n - x0 - x1 >= 5 &&
-                log_n - x0 - x1 <= 10) {
-                a[0] = x0, a[1] = x1, a[2] = log_n - x0 - x1;
-            }
-        }
+// n <= 1024 in one pass: a tile is whole transforms
+int run_row(const NttCall& c, const NttPlan& plan) {
+    const u64* inner = nullptr;
+    TRY(get_inner_table(c.ctx, c.log_n, c.inverse, c.inverse ? c.log_n : 0, &inner));
+    // 2^31 columns limit per launch: split huge batches
+    const size_t max_batch = size_t(1) << 24;
+    for (size_t b0 = 0; b0 < c.batch; b0 += max_batch) {
+        const size_t nb = std::min(max_batch, c.batch - b0);
+        Launch l = plan_row_pass(plan, c.in + b0 * c.in_bs, c.out + b0 * c.out_bs, c.in_bs, c.out_bs, nb, c.log_n, c.L);
+        l.a.inner_tw = inner;
+        l.a.pre_scale = c.pre_scale;
+        l.a.post_scale = c.post_scale;
+        l.a.n_coeffs = c.n_coeffs;
+        l.a.in2 = c.in2 ? c.in2 + b0 * c.in_bs : nullptr;
+        TRY(launch_pass(l, c.inverse, c.stream));
     }
+    return TF_OK;
 }
 
-// Can the last pass of an n-point transform truncate its output (LAST1024 kernel: two or three passes, last radix 1024)?
-bool can_truncate(size_t n, int L) {
-    if (n <= 1024 || n > (size_t(1) << 30)) return false;
-    static const bool no_block = ab_env("TF_NTT_NO_BLOCK") != nullptr;
-    if (n <= (size_t(1) << 14)) return L == 1 && !no_block && g_min_passes.load(std::memory_order_relaxed) == 0;  // the block kernel truncates (BFE product inverse)
-    const int log_n = ilog2(n), P = pass_count(log_n);
-    int a[4] = {0, 0, 0, 0};
-    choose_split(log_n, P, L, a);
-    // ... and that kernel addresses its stores through a buffer resource: 1024 * (n L / 1024) * 8 bytes must fit 32 bits (fits_buffer_offsets)
-    return P <= 3 && a[P - 1] == 10 && last1024_enabled() && (unsigned long long)n * L * 8 + (1ull << 20) < (1ull << 32);
-}
+// The work space between the passes of one call and, with K > 1 tile streams, the fork of the caller's stream into them and the join
+// back (event edges only, no host synchronisation).  One owner, in the style of DevTemp (tf_temp.h): finish() -- or the destructor, on
+// any early return -- joins whatever was enqueued on the side streams, destroys the events and hands the scratch block back behind
+// the join.
+class TileScope {
+public:
+    TileScope(DeviceCtx* ctx, hipStream_t stream) : ctx_(ctx), stream_(stream) {}
+    TileScope(const TileScope&) = delete;
+    TileScope& operator=(const TileScope&) = delete;
+    ~TileScope() { (void)finish(); }
 
-// Whether run_ntt plans this call with the narrow (256-thread) tiles: too little work to fill the chip with 512-thread ones
-// (see wg_threads()); a truncating call keeps the R = 1024 last pass its caller planned for.
-bool small_launch_for(size_t n, size_t cosets, size_t batch, int L, long long n_out) {
-    const int small_mode = g_small_launch_mode.load(std::memory_order_relaxed);
-    static const bool no_small = ab_env("TF_NTT_NO_SMALL_LAUNCH") != nullptr;  // A/B switch
-    const bool small_call = (unsigned long long)n * cosets * batch * L <= (1ull << 21);
-    return n_out < 0 && !wg_env() && (small_mode == 1 || (small_mode < 0 && small_call && !no_small));
-}
-
-// Two-pass plans for 2^21 / 2^22 points (a 2048-point pass = pairs of 1024-point workgroups, ntt_kernels.h PRE2).
-std::atomic<int> g_pre2_mode{-1};  // tf_set_ntt_two_pass: -1 automatic (TF_NTT_NO_PRE2 disables), 0 never, 1 whenever supported (pairs), 3 (one-workgroup first pass)
-#ifndef TF_C8_DEFAULT
-#define TF_C8_DEFAULT 1
-#endif
-constexpr bool kC8Default = TF_C8_DEFAULT != 0;
-bool pre2_plan_ok(int log_n, int L, size_t n, size_t cosets, bool has_in2, long long n_out, bool inverse, bool load_work, bool store_scale) {
-    static const bool off = ab_env("TF_NTT_NO_PRE2") != nullptr;  // A/B switch
-    const int mode = g_pre2_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || (mode < 0 && off)) return false;  // (mode 2: the radix-4 plan where it applies, this one elsewhere)
-    if (log_n < 21 || log_n > 22 || cosets != 1 || has_in2 || n_out >= 0) return false;
-    if ((load_work && inverse) || (store_scale && !inverse)) return false;          // shapes no caller produces
-    if (!last1024_enabled() || ablate_mode() != 0 || wg_threads() != 512) return false;
-    if (g_min_passes.load(std::memory_order_relaxed) > 2) return false;
-    return (unsigned long long)n * L * 8 + (1ull << 20) < (1ull << 32);              // buffer addressing (fits_buffer_offsets)
-}
-// 2^22 points as 1024 x 4096 with the 4096-point LAST pass run as four 1024-point classes per tile (ntt_kernels.h, PRE4) -- round 4's
-// attempt on BASELINE configs[3]: the first pass of a coset evaluation is then an ordinary 1024-point column pass that scales every
-// coefficient once, where the 2048 x 2048 plan scales it in both workgroups of a PRE2 pair.  MEASURED (profiles/r04_c4_plan_ab.txt,
-// 64 x 2^22 XFE, per 16-polynomial tile): the first pass does get cheaper, 1 194 -> 981 us, but the radix-4 load stage costs the last
-// pass more than that, 752 -> 1 047 us (four reads of every input through the L2 in bursts of 16, 27 more instructions per element):
-// 7.9 ms against 7.6 -- a loss, so the product never plans it.  Laboratory build: TF_NTT_PRE4 in the environment makes it the
-// automatic plan of fast_coset_evaluate at 2^22, tf_set_ntt_two_pass(2) of every forward 2^22-point transform.
-bool pre4_plan_ok(int log_n, int L, size_t n, size_t cosets, bool has_in2, long long n_out, bool inverse, bool load_work, bool store_scale) {
-#ifdef TF_AB_BUILD
-    static const bool on = ab_env("TF_NTT_PRE4") != nullptr;
-    const int mode = g_pre2_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || mode == 1 || mode == 3 || (mode < 0 && !(on && load_work))) return false;
-    if (log_n != 22 || cosets != 1 || has_in2 || n_out >= 0 || inverse || store_scale) return false;
-    if (!last1024_enabled() || ablate_mode() != 0 || wg_threads() != 512) return false;
-    if (g_min_passes.load(std::memory_order_relaxed) > 2) return false;
-    return (unsigned long long)n * L * 8 + (1ull << 20) < (1ull << 32);              // buffer addressing (fits_buffer_offsets)
-#else
-    (void)log_n, (void)L, (void)n, (void)cosets, (void)has_in2, (void)n_out, (void)inverse, (void)load_work, (void)store_scale;
-    return false;
-#endif
-}
-// Round 6: the FIRST pass of a two-pass plan as ONE workgroup per 2048 x 8 tile (ntt_col2048_kernel): every element is loaded (and,
-// in a coset evaluation, scaled) once, where a PRE2 pair does both twice.  2^22 = 2048 (this kernel) x 2048 (the PRE2 last pass);
-// 2^21 = 2048 (this kernel) x 1024 (the plain R = 1024 last pass, no pair anywhere).  MEASURED (profiles/r06_c4_cols8_ab.txt, same
-// process, same words, ms per 2^28 / 3 * 2^26 words): it wins where the first pass SCALES, at 2^22 -- XFE coset evaluation 1.84 vs 1.94
-// (BASELINE configs[3]: 7.40 vs 7.80), BFE 2.53 vs 2.65 -- ties on BFE 2^21 / 2^22 plain transforms and loses 2-9 % on XFE plain
-// transforms and everything XFE at 2^21 (its 64-byte segments cost more there than the pair's second read).  So the automatic plan
-// takes it for coset evaluations of 2^22 points only; tf_set_ntt_two_pass(3) forces it wherever the two-pass plan applies, (1) forces
-// the round-3 pairs.
-bool c8_first_pass(int log_n, bool scaled) {
-    const int mode = g_pre2_mode.load(std::memory_order_relaxed);
-    if (mode == 3) return true;
-    if (mode >= 0) return false;
-    return kC8Default && log_n == 22 && scaled;
-}
-void pre2_split(int log_n, int (&a)[4]) { pre2_split(log_n, a, c8_first_pass(log_n, false)); }
-void pre2_split(int log_n, int (&a)[4], bool c8) {
-    // 2^21: the 2048-point pass last (the first pass of a coset evaluation then scales every coefficient once); 2^22: both
-    a[0] = log_n == 22 ? 11 : 10, a[1] = 11, a[2] = a[3] = 0;
-    if (c8) a[0] = 11, a[1] = log_n - 11;
-    if (const char* e = exp_env("TF_NTT_PRE2_FIRST")) {
-        if (log_n == 21 && atoi(e)) a[0] = 11, a[1] = 10;
+    u64* scratch() const { return blk_.p; }
+    int acquire(size_t bytes) {
+        const int rc = scratch_acquire(ctx_, bytes, stream_, &blk_);
+        if (rc) blk_ = DeviceCtx::ScratchBlock{};  // (nothing of ours to give back)
+        return rc;
     }
-}
-
-// The transform proper.  in/out are device pointers; in == out for ntt/intt, distinct for coset evaluation
-// (then pre_scale != null and rows >= n_coeffs read as zero).  in_bs/out_bs: words per polynomial.
-// cosets = C > 1 (forward coset evaluation only, n > 1024): the output has C * n points per polynomial,
-// out[j * C + c] = (transform of the coefficients scaled by pre_scale[c * n_coeffs + .])[j] -- the evaluation on the coset of
-// order C * n done as C transforms of length n whose outputs interleave (w_{Cn}^(jC + c) = w_{Cn}^c * w_n^j).  The first pass
-// reads the coefficients once per c and writes rows (k_1, c); from there on it is the ordinary plan with N_1 * C rows.
-int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, size_t n, size_t batch, int L,
-            bool inverse, const u64* pre_scale, long long n_coeffs, hipStream_t stream, const u64* post_scale,
-            size_t cosets, const u64* in2, long long n_out, const u64* coset_offset) {
-    // n_out >= 0 (only with can_truncate(n, L)): the last pass stores output elements j < n_out only and out_bs may be
-    // n_out * L -- the truncation of fast_multiply without a copy; `in` is then used as work space and clobbered
-    if (n == 0 || batch == 0) return TF_OK;
-    const int log_n = ilog2(n);
-    int rc;
-    // batches of short contiguous transforms: wave-private tiles, one coalesced round trip (a handful of them stay on the tiny kernel)
-    if (log_n >= 1 && (log_n <= 5 || (log_n == 6 && L == 1)) && !pre_scale && !post_scale && n_coeffs < 0 && !in2 && n_out < 0 &&
-        in_bs == (long long)n * L && out_bs == (long long)n * L && (log_n == 5 || (batch << log_n) * size_t(L) >= 4096)) {
-        static const bool no_rows32 = ab_env("TF_NTT_NO_ROWS32") != nullptr;  // A/B switch
-        if (!no_rows32) return launch_rows32(in, out, batch, L, log_n, inverse, stream);
-    }
-    if (log_n <= 4) {
-        const u64* tw = nullptr;
-        rc = get_tiny_table(ctx, log_n, inverse, &tw);
-        if (rc) return rc;
-        tfk::NttTinyArgs A{};
-        A.in = in;
-        A.out = out;
-        A.tw = tw;
-        A.pre_scale = pre_scale;
-        A.post_scale = post_scale;
-        A.n_coeffs = n_coeffs;
-        A.in_bs = in_bs;
-        A.out_bs = out_bs;
-        A.count = (long long)batch * L;
-        A.scale = (inverse && log_n > 0) ? gl::mont_inverse(gl::to_mont(u64(n))) : 0;
-        A.log_n = log_n;
-        A.L = L;
-        const long long blocks = (A.count + 255) / 256;
-        hipLaunchKernelGGL(tfk::ntt_tiny_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, A);
-        HIPCHK(hipGetLastError());
+    // the K side streams wait for everything the caller's stream holds so far
+    int fork(int K, const hipStream_t* side) {
+        K_ = K;
+        side_ = side;
+        hipError_t e = hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming);
+        for (int i = 0; i < K && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev_join_[i], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ev_fork_, stream_);
+        for (int i = 0; i < K && e == hipSuccess; ++i) e = hipStreamWaitEvent(side[i], ev_fork_, 0);
+        if (e != hipSuccess) {
+            // nothing has been enqueued on the side streams that touches the scratch: release and report
+            (void)finish();
+            return hip_fail(e, "fork into the tile streams", __FILE__, __LINE__);
+        }
+        forked_ = true;
         return TF_OK;
     }
-    // (the latency-shaped kernel also takes the coset scalings of fast_coset_evaluate / fast_coset_interpolate: a 2^10-point coset
-    //  evaluation is one launch of 8-element threads, 8 us, instead of one 32-element-thread workgroup, 19 us)
-    if (n_out < 0 && cosets == 1 && (!in2 || L == 1) && g_min_passes.load(std::memory_order_relaxed) == 0 && !(pre_scale && inverse) &&
-        !(post_scale && !inverse) && lat_wanted(log_n, batch, L))
-        return launch_lat(ctx, in, out, in_bs, out_bs, log_n, batch, L, inverse, n_coeffs, in2, stream, nullptr, pre_scale, post_scale);
-    if (n_out < 0 && cosets == 1 && (!in2 || L == 1) && g_min_passes.load(std::memory_order_relaxed) == 0 && !(pre_scale && inverse) &&
-        !(post_scale && !inverse) && lat2_wanted(log_n, batch, L))
-        return launch_lat2(ctx, in, out, in_bs, out_bs, log_n, batch, L, inverse, n_coeffs, in2, stream, pre_scale, post_scale);
-    if (log_n <= 10) {
-        const u64* inner = nullptr;
-        rc = get_inner_table(ctx, log_n, inverse, inverse ? log_n : 0, &inner);
-        if (rc) return rc;
-        // 2^31 columns limit per launch: split huge batches
-        const size_t max_batch = size_t(1) << 24;
-        for (size_t b0 = 0; b0 < batch; b0 += max_batch) {
-            const size_t nb = std::min(max_batch, batch - b0);
-            Launch l = plan_row_pass(in + b0 * in_bs, out + b0 * out_bs, in_bs, out_bs, nb, log_n, L);
-            l.a.inner_tw = inner;
-            l.a.pre_scale = pre_scale;
-            l.a.post_scale = post_scale;
-            l.a.n_coeffs = n_coeffs;
-            l.a.in2 = in2 ? in2 + b0 * in_bs : nullptr;
-            rc = launch_pass(l, inverse, stream);
-            if (rc) return rc;
+    int finish() {
+        hipError_t je = hipSuccess;
+        if (forked_) {  // join: whatever was enqueued (also after a failed launch) finishes before the caller's stream goes on
+            for (int i = 0; i < K_; ++i) {
+                hipError_t e1 = hipEventRecord(ev_join_[i], side_[i]);
+                if (e1 == hipSuccess) e1 = hipStreamWaitEvent(stream_, ev_join_[i], 0);
+                if (e1 != hipSuccess) je = e1;
+            }
+            forked_ = false;
         }
+        if (ev_fork_) (void)hipEventDestroy(ev_fork_);
+        ev_fork_ = nullptr;
+        for (int i = 0; i < kMaxPipe; ++i) {
+            if (ev_join_[i]) (void)hipEventDestroy(ev_join_[i]);
+            ev_join_[i] = nullptr;
+        }
+        if (je != hipSuccess) (void)hipDeviceSynchronize();  // cannot order the release after the side streams any other way
+        scratch_release(ctx_, blk_, stream_);
+        blk_ = DeviceCtx::ScratchBlock{};
+        if (je != hipSuccess) return hip_fail(je, "join of the tile streams", __FILE__, __LINE__);
         return TF_OK;
     }
-    {
-        static const bool no_block = ab_env("TF_NTT_NO_BLOCK") != nullptr;  // A/B switch
-        const bool product_inverse = in2 && inverse && !pre_scale && !post_scale && n_coeffs < 0;
-        // XFieldElement slices take the same kernel as three limb transforms per slice with element stride 3 (round 2;
-        // TF_NTT_NO_XFE_BLOCK restores the two-pass plan for an A/B run): one HBM pass instead of two
-        static const bool no_xfe_block = ab_env("TF_NTT_NO_XFE_BLOCK") != nullptr;
-        // (2^11 and 2^12 only: 1.09 vs 1.46 and 1.33 vs 1.42 ms per 3 * 2^26 words; at 2^13 / 2^14 the limbs of a slice sit in
-        // different workgroups and the 24-byte element stride costs more than the second pass saves: 1.52 vs 1.42, 1.78 vs 1.33)
-        if (!no_block && log_n >= 11 && log_n <= (L == 1 ? 14 : 12) && (L == 1 || (L == 3 && !no_xfe_block)) && cosets == 1 &&
-            g_min_passes.load(std::memory_order_relaxed) == 0 && batch < (size_t(1) << 29)) {
-            if (product_inverse && L == 1)
-                return launch_block(ctx, in, out, in_bs, out_bs, log_n, batch, true, nullptr, -1, nullptr, stream, in2, n_out);
-            if (!in2 && n_out < 0 && !((pre_scale || n_coeffs >= 0) && inverse) && !(post_scale && !inverse))
-                return launch_block(ctx, in, out, in_bs, out_bs, log_n, batch, inverse, pre_scale, n_coeffs, post_scale, stream, nullptr, -1, L);
-        }
-    }
-    // multi-pass: n = N_1 * ... * N_P, every N_i = 2^(a_i) <= 1024.  Passes 1 .. P-1 are column passes (DFT over digit i,
-    // inter-pass twiddle, same position in and out); the last pass transforms the contiguous rows of N_P elements and
-    // scatters output digit k_P to  k_1 + N_1 k_2 + ... + N_1..N_{P-1} k_P  (natural order).
-    struct SmallLaunchScope {  // see wg_threads(); a truncating call keeps the R = 1024 last pass its caller planned for
-        SmallLaunchScope(bool on) { t_small_launch = on; }
-        ~SmallLaunchScope() { t_small_launch = false; }
-    };
-    SmallLaunchScope small_scope(small_launch_for(n, cosets, batch, L, n_out));
-    int a[4] = {0, 0, 0, 0};
-    int P = pass_count(log_n);
-    choose_split(log_n, P, L, a);
-    // 2^21 and 2^22 points in TWO passes: a 2048-point pass runs as pairs of 1024-point workgroups that share their input
-    // (ntt_kernels.h, PRE2; a[i] = 11 below).  Plain transforms, coset evaluation (forward) and coset interpolation (inverse).
-    bool pre2[4] = {false, false, false, false};
-    bool c8 = false;         // the first pass is the one-workgroup 2048-point column pass (ntt_col2048_kernel)
-    bool pre4_last = false;  // the last pass is a 4096-point one in four classes (a[P - 1] = 12)
+
+private:
+    DeviceCtx* ctx_;
+    hipStream_t stream_;
+    DeviceCtx::ScratchBlock blk_;
+    int K_ = 0;
+    const hipStream_t* side_ = nullptr;
+    bool forked_ = false;
+    hipEvent_t ev_fork_ = nullptr, ev_join_[kMaxPipe] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+// multi-pass: n = N_1 * ... * N_P, every N_i = 2^(a_i) <= 1024.  Passes 1 .. P-1 are column passes (DFT over digit i,
+// inter-pass twiddle, same position in and out); the last pass transforms the contiguous rows of N_P elements and
+// scatters output digit k_P to  k_1 + N_1 k_2 + ... + N_1..N_{P-1} k_P  (natural order).  Everything that was decided -- passes,
+// radices, pairs, tiles, streams -- is read from the plan.
+int run_passes(const NttCall& c, const NttPlan& plan) {
+    DeviceCtx* const ctx = c.ctx;
+    const int P = plan.P, L = c.L, log_n = c.log_n;
+    const int (&a)[4] = plan.a;
+    const bool (&pre2)[4] = plan.pre2;
+    const bool inverse = c.inverse, c8 = plan.c8, pre4_last = plan.pre4_last;
+    const size_t n = c.n, cosets = c.cosets;
+    const long long n_coeffs = c.n_coeffs, n_out = c.n_out;
+    const u64 *const pre_scale = c.pre_scale, *const post_scale = c.post_scale;
     const u64* pre4_stw = nullptr;
-    if (pre4_plan_ok(log_n, L, n, cosets, in2 != nullptr, n_out, inverse, pre_scale != nullptr || n_coeffs >= 0, post_scale != nullptr)) {
-        P = 2;
-        a[0] = 10, a[1] = 12, a[2] = a[3] = 0;
-        pre4_last = true;
-    } else if (pre2_plan_ok(log_n, L, n, cosets, in2 != nullptr, n_out, inverse, pre_scale != nullptr || n_coeffs >= 0, post_scale != nullptr)) {
-        P = 2;
-        // (a scaling first pass on the one-workgroup kernel needs the offset itself, for the inter-pass table with offset^b folded in)
-        c8 = c8_first_pass(log_n, pre_scale != nullptr) && (!pre_scale || coset_offset);
-        pre2_split(log_n, a, c8);
-        pre2[0] = a[0] == 11 && !c8, pre2[1] = a[1] == 11;
-    }
     const u64* inner[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < P; ++i) {
         const bool p4 = pre4_last && i == P - 1;
-        rc = get_inner_table(ctx, (pre2[i] || p4) ? 10 : a[i], inverse, (i == P - 1 && inverse) ? log_n : 0, &inner[i], p4 ? 4 : (pre2[i] ? 2 : 1),
-                             p4 ? &pre4_stw : nullptr);  // n^-1 rides on the last pass
-        if (rc) return rc;
+        TRY(get_inner_table(ctx, (pre2[i] || p4) ? 10 : a[i], inverse, (i == P - 1 && inverse) ? log_n : 0, &inner[i], p4 ? 4 : (pre2[i] ? 2 : 1),
+                            p4 ? &pre4_stw : nullptr));  // n^-1 rides on the last pass
     }
     const u64* post[3] = {nullptr, nullptr, nullptr};
     const u64* post_u = nullptr;  // the plain table beside a scaled post[0] (one-workgroup scaling first pass)
     // tables too large to cache: given back on the caller's stream when the call returns, behind the join of the tile streams
-    DevTemp post_own[3] = {DevTemp(stream), DevTemp(stream), DevTemp(stream)}, post_u_own(stream);
+    DevTemp post_own[3] = {DevTemp(c.stream), DevTemp(c.stream), DevTemp(c.stream)}, post_u_own(c.stream);
     {
         int rest = log_n;
         for (int i = 0; i + 1 < P; ++i) {
             if (i == 0 && c8 && pre_scale) {
                 // the scaled table for every thread's own row, the plain one for the rows all threads share (ntt_col2048_kernel, TF_C8_UV)
-                TRY(get_scaled_post_table(ctx, rest, a[i], *coset_offset, stream, &post[i], &post_own[i]));
-                TRY(get_post_table(ctx, rest, a[i], inverse, stream, &post_u, &post_u_own));
+                TRY(get_scaled_post_table(ctx, rest, a[i], *c.coset_offset, c.stream, &post[i], &post_own[i]));
+                TRY(get_post_table(ctx, rest, a[i], inverse, c.stream, &post_u, &post_u_own));
             } else {
-                TRY(get_post_table(ctx, rest, a[i], inverse, stream, &post[i], &post_own[i]));
+                TRY(get_post_table(ctx, rest, a[i], inverse, c.stream, &post[i], &post_own[i]));
             }
             rest -= a[i];
         }
     }
-    read_env();
     static const bool no_col_shift = ab_env("TF_NTT_NO_COL_SHIFT") != nullptr;  // A/B switch
-    const size_t poly_bytes = n * cosets * size_t(L) * sizeof(u64);
-    size_t tb = std::max<size_t>(1, g_tile_bytes / poly_bytes);
-    tb = std::min(tb, batch);
-    // pipelined tiles (g_pipe): tile t runs on side stream t % K with scratch tile t % K; the caller's stream forks into
-    // the side streams before the first tile and joins them after the last (event edges only, no host synchronisation)
-    const size_t ntiles = (batch + tb - 1) / tb;
-    tb = (batch + ntiles - 1) / ntiles;  // equal tiles: 64 polynomials at 21 per tile are 4 x 16, not 21 + 21 + 21 + 1
-    // Automatic (round 6, profiles/r06_pipe_tiles.txt): two streams for the two-pass plans of 2^21 / 2^22 points -- their first pass is bound
-    // by the memory pipe (0.68-0.76 of the issue slots busy) and their last pass by the vector ALU (0.80), so tile t + 1's first pass beside
-    // tile t's last pass gains 2.6-3.4 % (configs[3] 7.27-7.36 -> 7.06-7.08 ms, 64 x 2^22 XFE ntt 6.67 -> 6.49) -- and one stream for
-    // everything else (1024 x 2^20 BFE: 7.20-7.30 vs 7.24-7.32 ms, both passes VALU-bound).
-    int pipe = g_pipe.load(std::memory_order_relaxed);
-    if (pipe <= 0) pipe = (P == 2 && log_n >= 21) ? 2 : 1;
-    int K = (P < 4) ? (int)std::min<size_t>((size_t)pipe, ntiles) : 1;
+    const size_t poly_bytes = n * cosets * size_t(L) * sizeof(u64), tb = plan.tb;
+    // pipelined tiles: tile t runs on side stream t % K with scratch tile t % K; the caller's stream forks into the side streams
+    // before the first tile and joins them after the last
+    int K = plan.K;
     hipStream_t side[kMaxPipe] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxPipe] = {nullptr, nullptr, nullptr, nullptr};
     if (K > 1) {
         std::lock_guard<std::mutex> lk(ctx->mu);
         for (int i = 0; i < K; ++i) {
@@ -1649,44 +1447,24 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
             side[i] = ctx->side[i];
         }
     }
-    u64* scratch = nullptr;
-    DeviceCtx::ScratchBlock sblk;
-    {
-        TRY(scratch_acquire(ctx, size_t(K) * tb * poly_bytes, stream, &sblk));
-        scratch = sblk.p;
-    }
-    if (K > 1) {
-        hipError_t e = hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming);
-        for (int i = 0; i < K && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(ev_fork, stream);
-        for (int i = 0; i < K && e == hipSuccess; ++i) e = hipStreamWaitEvent(side[i], ev_fork, 0);
-        if (e != hipSuccess) {
-            // nothing has been enqueued on the side streams that touches the scratch: release and report
-            if (ev_fork) (void)hipEventDestroy(ev_fork);
-            for (int i = 0; i < K; ++i)
-                if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
-            scratch_release(ctx, sblk, stream);
-            return hip_fail(e, "fork into the tile streams", __FILE__, __LINE__);
-        }
-    }
-    hipStream_t const caller_stream = stream;
-    u64* const scratch_base = scratch;
+    TileScope tiles(ctx, c.stream);  // (declared after the tables: it joins and releases before they are given back)
+    TRY(tiles.acquire(size_t(K) * tb * poly_bytes));
+    if (K > 1) TRY(tiles.fork(K, side));
     const long long sbs = (long long)(n * cosets) * L;  // scratch batch stride
     long long N[4];
     for (int i = 0; i < 4; ++i) N[i] = 1ll << a[i];
+    int rc = TF_OK;
     size_t tile_no = 0;
-    for (size_t b0 = 0; b0 < batch && rc == TF_OK; b0 += tb, ++tile_no) {
-        const size_t nb = std::min(tb, batch - b0);
-        if (K > 1) {
-            stream = side[tile_no % K];
-            scratch = scratch_base + (tile_no % K) * tb * (size_t)sbs;
-        }
-        const u64* tin = in + (long long)b0 * in_bs;
-        u64* tout = out + (long long)b0 * out_bs;
+    for (size_t b0 = 0; b0 < c.batch && rc == TF_OK; b0 += tb, ++tile_no) {
+        const size_t nb = std::min(tb, c.batch - b0);
+        hipStream_t const stream = K > 1 ? side[tile_no % K] : c.stream;
+        u64* const scratch = K > 1 ? tiles.scratch() + (tile_no % K) * tb * (size_t)sbs : tiles.scratch();
+        const u64* tin = c.in + (long long)b0 * c.in_bs;
+        u64* tout = c.out + (long long)b0 * c.out_bs;
         // column passes: the first reads the caller's input, the last writes the scratch tile, the ones between work
         // in place on the output
         const u64* src = tin;
-        long long src_bs = in_bs;
+        long long src_bs = c.in_bs;
         long long outer = 1, B = (long long)n;
         for (int i = 0; i + 1 < P && rc == TF_OK; ++i) {
             B >>= a[i];
@@ -1694,8 +1472,8 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
             // a truncated output (n_out >= 0) is smaller than the transform: the middle passes then work in place on the
             // INPUT, which the caller gives up (fast_multiply's temporary)
             u64* dst = to_scratch ? scratch : (n_out >= 0 ? const_cast<u64*>(tin) : tout);
-            const long long dst_bs = to_scratch ? sbs : (n_out >= 0 ? in_bs : out_bs);
-            Launch p = plan_column_pass(src, dst, src_bs, dst_bs, nb, (i == 0) ? (long long)cosets : outer, a[i], B, L, pre2[i]);
+            const long long dst_bs = to_scratch ? sbs : (n_out >= 0 ? c.in_bs : c.out_bs);
+            Launch p = plan_column_pass(plan, src, dst, src_bs, dst_bs, nb, (i == 0) ? (long long)cosets : outer, a[i], B, L, pre2[i]);
             p.a.inner_tw = inner[i];
             p.a.post_tw = post[i];
             p.a.post_tw_u = (i == 0 && post_u) ? post_u : nullptr;
@@ -1708,7 +1486,7 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
                 p.a.pre_scale = pre_scale;
                 if (c8 && pre_scale) p.a.ps_col = 0;  // the column part offset^b of the scaling comes with the inter-pass table
                 p.a.n_coeffs = n_coeffs;
-                p.a.in2 = in2 ? in2 + (long long)b0 * in_bs : nullptr;
+                p.a.in2 = c.in2 ? c.in2 + (long long)b0 * c.in_bs : nullptr;
                 if (cosets > 1) {  // "outer" index = coset c: same input for every c, output row (k_1, c), scale table c
                     p.a.ib1 = 0;
                     p.a.ob1 = B * L;
@@ -1724,28 +1502,15 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
         }
         if (rc) break;
         if (P < 4) {
-            // XFieldElement rows through the R = 1024 kernel: word-granular tiles (whole 128-byte lines on the output side)
-            static const bool no_words16 = ab_env("TF_NTT_NO_WORDS16") != nullptr;  // A/B switch
-            const bool plain1024 = (a[P - 1] == 10 || pre2[P - 1] || pre4_last) && last1024_enabled() && (!post_scale || (inverse && scaled_last1024_enabled() && log_n <= 28));
-            // (the other last-pass kernels too: all their thread slots as word-columns, e.g. 32 words = 256 bytes for R = 512)
-            int words = 0;
-            if (L == 3 && !no_words16) {
-                if (plain1024) {
-                    words = 16;
-                } else {  // share the N_1 * L words of a row evenly among the fewest tiles, in whole lines
-                    const long long tot = N[0] * (long long)cosets * L, wmax = std::max(16, wg_threads() >> (a[P - 1] - 5));
-                    const long long tiles_per_row = (tot + wmax - 1) / wmax;
-                    words = (int)((((tot + tiles_per_row - 1) / tiles_per_row) + 15) / 16 * 16);
-                }
-            }
-            Launch pl = plan_transpose_pass(scratch, tout, sbs, out_bs, nb, a[P - 1], N[0] * (long long)cosets, P == 3 ? N[1] : 1, L, 0,
-                                            words, pre4_last ? 4 : (pre2[P - 1] ? 2 : 1));
+            // (plan.words: XFieldElement rows in word-granular tiles, whole 128-byte lines on the output side)
+            Launch pl = plan_transpose_pass(plan, scratch, tout, sbs, c.out_bs, nb, a[P - 1], N[0] * (long long)cosets, P == 3 ? N[1] : 1, L, 0,
+                                            plan.words, pre4_last ? 4 : (pre2[P - 1] ? 2 : 1));
             pl.a.inner_tw = inner[P - 1];
             pl.a.pre4_stw = pre4_last ? pre4_stw : nullptr;
             pl.a.post_scale = post_scale;
             pl.a.n_out = n_out;
             pl.a.nt = g_nt.load(std::memory_order_relaxed) & 2;  // the result is written once
-            if (plain1024 && !pre4_last && pl.a.nc == 16 && !no_col_shift && (unsigned long long)n * L * sizeof(u64) < (1ull << 32)) {
+            if (plan.plain1024 && !pre4_last && pl.a.nc == 16 && !no_col_shift && (unsigned long long)n * L * sizeof(u64) < (1ull << 32)) {
                 // The R = 1024 last pass stores 128-byte segments of 16 adjacent output words.  When the output of batch entry
                 // b does not start on a cache line (a truncated product: stride n_out = na + nb - 1 words, or a caller's
                 // unaligned pointer) every segment would straddle two lines written by workgroups on different XCDs: shift
@@ -1754,13 +1519,13 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
                 // wrapped lanes' 32-bit byte offset spans the whole transform.)  Measured, tools/trunc_align.py: 256 products
                 // of 2^19 x 2^19 7.29 -> 7.05 ms, 1024 of 2^17 x 2^17 7.19 -> 6.66, 64 of 2^21 x 2^21 10.25 -> 9.65.
                 pl.a.col_shift0 = (int)((reinterpret_cast<uintptr_t>(tout) / sizeof(u64)) & 15);
-                pl.a.col_shift_i0 = (int)(out_bs & 15);
+                pl.a.col_shift_i0 = (int)(c.out_bs & 15);
                 pl.a.col_wrap = pl.a.col_limit;
             }
             rc = launch_pass(pl, inverse, stream);
         } else {
             for (size_t b = 0; b < nb && rc == TF_OK; ++b) {
-                Launch pl = plan_transpose_pass(scratch + (long long)b * sbs, tout + (long long)b * out_bs, sbs, out_bs, 1, a[3], N[0],
+                Launch pl = plan_transpose_pass(plan, scratch + (long long)b * sbs, tout + (long long)b * c.out_bs, sbs, c.out_bs, 1, a[3], N[0],
                                                 N[1] * N[2], L, N[1]);
                 pl.a.inner_tw = inner[3];
                 pl.a.post_scale = post_scale;
@@ -1768,25 +1533,39 @@ int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long 
             }
         }
     }
-    stream = caller_stream;
-    scratch = scratch_base;
-    if (K > 1) {  // join: whatever was enqueued (also after a failed launch) finishes before the caller's stream goes on
-        hipError_t je = hipSuccess;
-        for (int i = 0; i < K; ++i) {
-            hipError_t e1 = hipEventRecord(ev_join[i], side[i]);
-            if (e1 == hipSuccess) e1 = hipStreamWaitEvent(stream, ev_join[i], 0);
-            if (e1 != hipSuccess) je = e1;
-        }
-        (void)hipEventDestroy(ev_fork);
-        for (int i = 0; i < K; ++i) (void)hipEventDestroy(ev_join[i]);
-        if (je != hipSuccess) {
-            (void)hipDeviceSynchronize();  // cannot order the release after the side streams any other way
-            scratch_release(ctx, sblk, stream);
-            return hip_fail(je, "join of the tile streams", __FILE__, __LINE__);
-        }
+    const int jrc = tiles.finish();
+    return jrc ? jrc : rc;
+}
+
+// The transform proper.  in/out are device pointers; in == out for ntt/intt, distinct for coset evaluation
+// (then pre_scale != null and rows >= n_coeffs read as zero).  in_bs/out_bs: words per polynomial.
+// cosets = C > 1 (forward coset evaluation only, n > 1024): the output has C * n points per polynomial,
+// out[j * C + c] = (transform of the coefficients scaled by pre_scale[c * n_coeffs + .])[j] -- the evaluation on the coset of
+// order C * n done as C transforms of length n whose outputs interleave (w_{Cn}^(jC + c) = w_{Cn}^c * w_n^j).  The first pass
+// reads the coefficients once per c and writes rows (k_1, c); from there on it is the ordinary plan with N_1 * C rows.
+// n_out >= 0 (only with can_truncate(n, L)): the last pass stores output elements j < n_out only and out_bs may be
+// n_out * L -- the truncation of fast_multiply without a copy; `in` is then used as work space and clobbered
+int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, size_t n, size_t batch, int L,
+            bool inverse, const u64* pre_scale, long long n_coeffs, hipStream_t stream, const u64* post_scale,
+            size_t cosets, const u64* in2, long long n_out, const u64* coset_offset) {
+    if (n == 0 || batch == 0) return TF_OK;
+    NttShape s;
+    s.n = n, s.batch = batch, s.L = L, s.inverse = inverse, s.cosets = cosets, s.n_coeffs = n_coeffs, s.n_out = n_out;
+    s.pre_scale = pre_scale != nullptr, s.post_scale = post_scale != nullptr, s.in2 = in2 != nullptr, s.coset_offset = coset_offset != nullptr;
+    s.packed = in_bs == (long long)n * L && out_bs == (long long)n * L;
+    const NttPlan plan = plan_ntt(s);
+    const NttCall c{ctx, in, out, in_bs, out_bs, n, batch, L, inverse, pre_scale, n_coeffs, stream, post_scale, cosets, in2, n_out, coset_offset, ilog2(n)};
+    switch (plan.route) {
+        case NttRoute::Rows32: return launch_rows32(in, out, batch, L, c.log_n, inverse, stream);
+        case NttRoute::Tiny: return run_tiny(c);
+        case NttRoute::Lat: return launch_lat(ctx, in, out, in_bs, out_bs, c.log_n, batch, L, inverse, n_coeffs, in2, stream, nullptr, pre_scale, post_scale);
+        case NttRoute::Lat2: return launch_lat2(ctx, in, out, in_bs, out_bs, c.log_n, batch, L, inverse, n_coeffs, in2, stream, pre_scale, post_scale);
+        case NttRoute::Row: return run_row(c, plan);
+        // (a product's inverse carries in2 and n_out and nothing else; every other shape on this route carries neither)
+        case NttRoute::Block: return launch_block(ctx, in, out, in_bs, out_bs, c.log_n, batch, inverse, pre_scale, n_coeffs, post_scale, stream, in2, n_out, L);
+        case NttRoute::Passes: return run_passes(c, plan);
     }
-    scratch_release(ctx, sblk, stream);
-    return rc;
+    return TF_ERR_HIP;
 }
 
 int ntt_dev(u64* d_x, size_t n, size_t batch, int L, int inverse, void* stream) {
@@ -1818,33 +1597,12 @@ int coset_eval_dev(const u64* d_coeffs, size_t n_coeffs, u64 offset_raw, u64* d_
     }
     const u64* pw = nullptr;
     bool temp = false;
-    // Blown-up evaluation (n_coeffs <= order / 2, the low-degree-extension shape): when the padded coefficient length
-    // needs one global pass fewer than the order (len <= 2^20 < order), evaluate on the order / len cosets of the
-    // subgroup of size len instead of transforming zeros.  Same values: exact arithmetic.  Measured (tools/lde_shapes.py):
-    // 2^18 -> 2^21 2.94 vs 3.47 ms, 2^20 -> 2^23 2.80 vs 3.71 ms per 2^28 points; with equal pass counts the plain plan
-    // wins because its first pass skips the zero rows, so it stays the default there.
-    size_t len = 1;
-    while (len < n_coeffs) len <<= 1;
-    static const bool no_split = ab_env("TF_COSET_EVAL_NO_SPLIT") != nullptr;  // A/B switch
-    // ADVICE r3 asked whether the comparison should use the EFFECTIVE pass count of the plain plan (orders 2^21 / 2^22 run in two
-    // passes under PRE2, so the split then saves no pass).  Built and measured (profiles/r04_lde_split_rule.txt, 2^28 words per
-    // call): the split still wins where it matters -- BFE 2^20 -> 2^22 2.05 vs 2.48 ms, 2^19 -> 2^22 2.03 vs 2.40, 2^20 -> 2^21
-    // 2.07 vs 2.17; XFE 2^20 -> 2^22 1.01 vs 1.13 -- because its first pass reads n_coeffs rows instead of `order` and none of its
-    // passes pays the PRE2 pair's second read and second scaling; only XFE 2^18 / 2^19 -> 2^21 is 3 % faster on the plain plan.
-    // The round-3 rule (nominal pass counts) therefore stays; the other one is a laboratory switch.
-    static const bool effective_rule = ab_env("TF_COSET_EVAL_EFFECTIVE_PASSES") != nullptr;
-    int plain_passes = pass_count(ilog2(order));
-    if (effective_rule && !small_launch_for(order, 1, batch, L, -1)) {
-        // (wg_threads() is 512 outside a small-launch scope, which is the geometry the big call will be planned with)
-        if (pre2_plan_ok(ilog2(order), L, order, 1, false, -1, false, true, false)) plain_passes = 2;
-    }
-    // (at most kMaxCosetSplit cosets: one scale table of n_coeffs words per coset is built and, while it fits the budget, cached)
-    if (!no_split && len > 1024 && len < order && order / len <= kMaxCosetSplit && order <= (size_t(1) << 30) &&
-        pass_count(ilog2(len)) < plain_passes) {
-        const size_t cosets = order / len;
+    // the blown-up evaluation on order / len cosets of the padded coefficient length where it saves a global pass (coset_split, tf_plan.hip)
+    const size_t cosets = coset_split(n_coeffs, order, batch, L);
+    if (cosets > 1) {
         rc = get_pow_table(ctx, offset_raw, n_coeffs, s, &pw, &temp, cosets, ilog2(order));
         if (rc) return rc;
-        rc = run_ntt(ctx, d_coeffs, d_out, (long long)n_coeffs * L, (long long)order * L, len, batch, L, false, pw,
+        rc = run_ntt(ctx, d_coeffs, d_out, (long long)n_coeffs * L, (long long)order * L, order / cosets, batch, L, false, pw,
                      (long long)n_coeffs, s, nullptr, cosets);
     } else {
         rc = get_pow_table(ctx, offset_raw, n_coeffs, s, &pw, &temp);
