@@ -805,6 +805,73 @@ int tf_gather_elements_dev(const uint64_t *d_src, size_t src_len, int width, con
                            void *stream, int *d_status);
 
 /* ---------------------------------------------------------------------------------------------
+ * Tables: moving a table between the two layouts the library itself uses, and opening its rows.  replaces
+ *   Array2 .t() / reversed_axes, a prover's own transposes           table_transpose     dst line i, element o = src line o, element i
+ *   table.row(i) / select(Axis(0), indices)                          table_gather_rows   out row q = row indices[q]
+ *   the per-column low-degree extension of a trace kept row by row   table_lde_rows      tf_lde_*_dev of every column of a row-major table
+ * An element is `width` consecutive words: 1 for BFieldElement, 3 for XFieldElement [c0, c1, c2].  Strides count WORDS, every other
+ * length counts elements.  Words are moved as they are.
+ *   column-major     exactly the layout of tf_tip5_hash_table_rows: column j = n_rows elements at table + j * col_stride, col_stride >=
+ *                    n_rows * width; tables n_cols * col_stride words apart.  What a batch of coset evaluations leaves, and what
+ *                    tf_merkle_from_columns and tf_poly_linear_combination read.
+ *   row-major        row i = n_cols elements at rows + i * row_stride, row_stride >= n_cols * width; tables n_rows * row_stride words
+ *                    apart.  What tf_tip5_hash_varlen_rows and tf_merkle_from_rows read (row_stride = row_len), and how a prover keeps
+ *                    its trace and reveals rows.
+ *   padding          words between the end of a line and its stride are never read in a source and never written in a destination.
+ *   table_transpose  src: `batch` matrices of n_outer lines of n_inner elements, line o at src + o * src_stride, matrices
+ *                    n_outer * src_stride apart; dst: n_inner lines of n_outer elements at dst_stride, matrices n_inner * dst_stride apart.
+ *                      column-major -> row-major:  (table, n_cols, n_rows, width, col_stride, rows, row_stride, batch)
+ *                      row-major -> column-major:  (rows, n_rows, n_cols, width, row_stride, table, col_stride, batch)
+ *   table_gather_rows  out row q of table t (at out + (t * k + q) * out_stride, n_cols elements, out_stride >= n_cols * width) = row
+ *                    indices[q] of table t: one index list for all `batch` tables, repeats allowed; indices is the uint32_t array a
+ *                    sponge's index sampler writes.  `layout` is TF_TABLE_COLUMN_MAJOR or TF_TABLE_ROW_MAJOR and `stride` the
+ *                    col_stride or row_stride that goes with it.  An index >= n_rows is not read: the host form returns
+ *                    TF_ERR_INVALID_ARGUMENT; the _dev form writes it to *d_status, one int of device memory in which the first
+ *                    non-zero code stays and which is never cleared (the contract of tf_gather_elements_dev).  Either way that row's
+ *                    slot of out stays as it was, in every table, and every other row is correct.
+ *   table_lde_rows   ONE row-major table, device-resident only (as tf_lde_*_dev): rows in = n x n_cols values on {offset_in * w_n^i},
+ *                    rows out = m x n_cols values on {offset_out * w_m^i}.  Works through blocks of c = cols_per_block columns, the last
+ *                    one ragged: transpose the block in, tf_lde_*_dev with batch = c, transpose it out.  cols_per_block == 0 picks the
+ *                    largest c <= n_cols with c * (n + m) * width * 8 <= 256 MiB (at least 1; a chosen bound on the work space, not a
+ *                    measured optimum); a value above n_cols means n_cols.  Blocking bounds memory and costs time (2^18 -> 2^20 x 64
+ *                    BFieldElements: three blocks of 25 columns take about one and a half times as long as one block of 64,
+ *                    DESIGN 7.5): a caller
+ *                    with c = n_cols worth of work space to spare should pass cols_per_block = n_cols.  The two column-major
+ *                    temporaries are taken once per call
+ *                    on the caller's stream; tf_table_lde_rows_workspace returns their size in bytes (what tf_lde_*_dev takes itself
+ *                    comes on top), 0 for arguments the call rejects.  One stream, no side streams.
+ *   forms            a _dev form takes device pointers and only enqueues on `stream`: it never synchronises and copies nothing back.
+ *                    A host form takes host pointers and returns when the result is in place.  Source and destination may not overlap.
+ *   empty calls      any of n_outer, n_inner, n_cols, k, batch zero (the LDE: n_cols == 0 or m == 0): TF_OK, nothing touched, NULL
+ *                    pointers allowed.
+ *   errors           returned before any HIP call, in this order: TF_ERR_NULL_POINTER (d_status included); TF_ERR_INVALID_ARGUMENT (a
+ *                    width other than 1 or 3, a stride shorter than its line, a layout other than the two); TF_ERR_LEN_TOO_LARGE (any
+ *                    of n_outer, n_inner, n_rows, n_cols, k above 2^30, more than 2^35 words moved by the call, or an operand
+ *                    whose lines at its stride span more than 2^40 words -- a stride no device memory holds, which may
+ *                    not wrap the 64-bit offsets); then TF_ERR_NO_DEVICE.  table_lde_rows answers with the argument errors of tf_lde_*_dev first, in their order and
+ *                    before anything is enqueued (n > m, a length that is no power of two or too large, a NULL pointer, a zero
+ *                    offset_in), then with TF_ERR_LEN_TOO_LARGE for n_cols above 2^30 or more than 2^35 words of output, TF_ERR_INVALID_ARGUMENT for
+ *                    a short stride and TF_ERR_LEN_TOO_LARGE for a span above 2^40 words.  tf_table_lde_rows_workspace is 0 for
+ *                    every call that is rejected or empty (m == 0 included).
+ * The transpose stages tiles of 64 x 64 BFieldElements or 32 x 32 XFieldElements in LDS (csrc/table_kernels.h). */
+#define TF_TABLE_COLUMN_MAJOR 0
+#define TF_TABLE_ROW_MAJOR 1
+int tf_table_transpose(const uint64_t *src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t *dst, size_t dst_stride,
+                       size_t batch);
+int tf_table_transpose_dev(const uint64_t *d_src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t *d_dst,
+                           size_t dst_stride, size_t batch, void *stream);
+int tf_table_gather_rows(const uint64_t *table, int layout, size_t n_rows, size_t n_cols, int width, size_t stride, const uint32_t *indices,
+                         size_t k, uint64_t *out, size_t out_stride, size_t batch);
+int tf_table_gather_rows_dev(const uint64_t *d_table, int layout, size_t n_rows, size_t n_cols, int width, size_t stride,
+                             const uint32_t *d_indices, size_t k, uint64_t *d_out, size_t out_stride, size_t batch, void *stream,
+                             int *d_status);
+int tf_table_lde_rows_bfe_dev(const uint64_t *d_rows, size_t n, size_t n_cols, size_t row_stride_in, uint64_t offset_in_raw, uint64_t *d_out,
+                              size_t m, size_t row_stride_out, uint64_t offset_out_raw, size_t cols_per_block, void *stream);
+int tf_table_lde_rows_xfe_dev(const uint64_t *d_rows, size_t n, size_t n_cols, size_t row_stride_in, uint64_t offset_in_raw, uint64_t *d_out,
+                              size_t m, size_t row_stride_out, uint64_t offset_out_raw, size_t cols_per_block, void *stream);
+size_t tf_table_lde_rows_workspace(size_t n, size_t m, size_t n_cols, int width, size_t cols_per_block);
+
+/* ---------------------------------------------------------------------------------------------
  * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the
  * first call); every other TF_* switch of DESIGN_HISTORY.md exists in the laboratory build alone (TF_AB_BUILD, below).
  *   TF_NTT_TILE_BYTES : bytes of batch processed between the passes of a multi-pass NTT (scratch size),

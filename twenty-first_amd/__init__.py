@@ -26,8 +26,8 @@ import numpy as np
 from . import _lib
 
 __all__ = [
-    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "linear_combination", "get_colinear_y", "are_colinear", "mod_pow", "powers", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree",
-    "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "set_device", "get_device", "shard_range",
+    "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "linear_combination", "get_colinear_y", "are_colinear", "mod_pow", "powers", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree", "Table",
+    "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "table", "set_device", "get_device", "shard_range",
 ]
 
 P = 0xFFFFFFFF00000001  # BFieldElement::P, math/b_field_element.rs:225
@@ -1157,6 +1157,61 @@ class MerkleTreeInclusionProof:
 
 
 # ----------------------------------------------------------------------------- Merkle Mountain Range (util_types/mmr/)
+class Table:
+    """Whole tables between the two layouts of the library (include/tf_hip.h, "Tables"), host arrays in and out.  An element is
+    `width` raw words.  Column-major: column j = n_rows elements at j * col_stride words (what Tip5.hash_table_rows and
+    MerkleTree.from_columns read); row-major: row i = n_cols elements at i * row_stride words (what Tip5.hash_varlen_rows reads).  A
+    stride left as None is the exact one; the padding words of a source are never read, those of a result are zero."""
+
+    COLUMN_MAJOR = 0
+    ROW_MAJOR = 1
+
+    @staticmethod
+    def _transposed(src, n_outer: int, n_inner: int, width: int, src_stride, dst_stride, batch: int, where: str) -> np.ndarray:
+        src = _words(src, "table")
+        if width not in (1, 3) or min(n_outer, n_inner, batch) < 0:
+            raise ValueError("width must be 1 or 3 and the counts non-negative")
+        ss = n_inner * width if src_stride is None else int(src_stride)
+        ds = n_outer * width if dst_stride is None else int(dst_stride)
+        if ss < n_inner * width or ds < n_outer * width:
+            raise ValueError("a stride is shorter than its line")
+        lines = batch * n_outer
+        if src.size < ((lines - 1) * ss + n_inner * width if lines and n_inner else 0):
+            raise ValueError("the table is smaller than batch * lines at this stride")
+        out = np.zeros(batch * n_inner * ds, dtype=np.uint64)
+        _check(lib().tf_table_transpose(_ptr(src), n_outer, n_inner, width, ss, _ptr(out), ds, batch), where)
+        return out
+
+    @staticmethod
+    def columns_to_rows(table: np.ndarray, n_rows: int, n_cols: int, width: int = 1, col_stride=None, row_stride=None, batch: int = 1) -> np.ndarray:
+        """`batch` column-major tables -> batch * n_rows * row_stride words of row-major rows."""
+        return Table._transposed(table, n_cols, n_rows, width, col_stride, row_stride, batch, "Table::columns_to_rows")
+
+    @staticmethod
+    def rows_to_columns(rows: np.ndarray, n_rows: int, n_cols: int, width: int = 1, row_stride=None, col_stride=None, batch: int = 1) -> np.ndarray:
+        """`batch` row-major tables -> batch * n_cols * col_stride words of column-major columns."""
+        return Table._transposed(rows, n_rows, n_cols, width, row_stride, col_stride, batch, "Table::rows_to_columns")
+
+    @staticmethod
+    def gather_rows(table: np.ndarray, n_rows: int, n_cols: int, indices, layout: int = 0, width: int = 1, stride=None, batch: int = 1) -> np.ndarray:
+        """Rows indices[q] of every one of `batch` tables, from either layout: (batch, k, n_cols * width) words.  An index >= n_rows
+        raises TwentyFirstError (code 17)."""
+        table = _words(table, "table")
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        if width not in (1, 3) or layout not in (0, 1) or min(n_rows, n_cols, batch) < 0:
+            raise ValueError("width must be 1 or 3, layout COLUMN_MAJOR or ROW_MAJOR and the counts non-negative")
+        lines, line = (n_rows, n_cols * width) if layout == Table.ROW_MAJOR else (n_cols, n_rows * width)
+        st = line if stride is None else int(stride)
+        if st < line:
+            raise ValueError("stride is shorter than its line")
+        if table.size < ((batch * lines - 1) * st + line if batch * lines and line else 0):
+            raise ValueError("the table is smaller than batch tables at this stride")
+        out = np.zeros(batch * idx.size * n_cols * width, dtype=np.uint64)
+        _check(lib().tf_table_gather_rows(_ptr(table), layout, n_rows, n_cols, width, st, _ptr(idx), idx.size, _ptr(out), n_cols * width, batch),
+               "Table::gather_rows")
+        return out.reshape(batch, idx.size, n_cols * width)
+
+
 from . import mmr_index  # noqa: E402
 
 
@@ -1400,3 +1455,4 @@ def bag_peaks_batch(leaf_counts, peaks) -> np.ndarray:
 
 
 from . import device  # noqa: E402  (torch device-pointer API)
+from . import table  # noqa: E402  (tables on the device: transposes, row opening, row-major LDE)

@@ -139,6 +139,13 @@ SIGNATURES = {
     "tf_powers": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz]),
     "tf_powers_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _vp]),
     "tf_gather_elements_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp]),
+    "tf_table_transpose": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz]),
+    "tf_table_transpose_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz, _vp]),
+    "tf_table_gather_rows": (C.c_int, [_vp, C.c_int, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _sz]),
+    "tf_table_gather_rows_dev": (C.c_int, [_vp, C.c_int, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp]),
+    "tf_table_lde_rows_bfe_dev": (C.c_int, [_vp, _sz, _sz, _sz, C.c_uint64, _vp, _sz, _sz, C.c_uint64, _sz, _vp]),
+    "tf_table_lde_rows_xfe_dev": (C.c_int, [_vp, _sz, _sz, _sz, C.c_uint64, _vp, _sz, _sz, C.c_uint64, _sz, _vp]),
+    "tf_table_lde_rows_workspace": (_sz, [_sz, _sz, _sz, C.c_int, _sz]),
     "tf_zerofier_tree_new_bfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_xfe": (C.c_int, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "tf_zerofier_tree_new_bfe_dev": (C.c_int, [_vp, _sz, _vp, C.POINTER(C.c_void_p)]),

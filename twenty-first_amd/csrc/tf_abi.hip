@@ -962,6 +962,37 @@ int tf_gather_elements_dev(const uint64_t* src, size_t src_len, int width, const
                            int* d_status) try {
     return gather_elements_dev(src, src_len, width, indices, n, out, stream, d_status);
 } TF_ABI_CATCH
+// tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (tf_table.hip)
+int tf_table_transpose(const uint64_t* src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t* dst, size_t dst_stride,
+                       size_t batch) try {
+    return table_transpose(src, n_outer, n_inner, width, src_stride, dst, dst_stride, batch, true, nullptr);
+} TF_ABI_CATCH
+int tf_table_transpose_dev(const uint64_t* src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t* dst, size_t dst_stride,
+                           size_t batch, void* stream) try {
+    return table_transpose(src, n_outer, n_inner, width, src_stride, dst, dst_stride, batch, false, stream);
+} TF_ABI_CATCH
+int tf_table_gather_rows(const uint64_t* table, int layout, size_t n_rows, size_t n_cols, int width, size_t stride, const uint32_t* indices, size_t k,
+                         uint64_t* out, size_t out_stride, size_t batch) try {
+    return table_gather_rows(table, layout, n_rows, n_cols, width, stride, indices, k, out, out_stride, batch, true, nullptr, nullptr);
+} TF_ABI_CATCH
+int tf_table_gather_rows_dev(const uint64_t* table, int layout, size_t n_rows, size_t n_cols, int width, size_t stride, const uint32_t* indices,
+                             size_t k, uint64_t* out, size_t out_stride, size_t batch, void* stream, int* d_status) try {
+    return table_gather_rows(table, layout, n_rows, n_cols, width, stride, indices, k, out, out_stride, batch, false, stream, d_status);
+} TF_ABI_CATCH
+int tf_table_lde_rows_bfe_dev(const uint64_t* rows, size_t n, size_t n_cols, size_t row_stride_in, uint64_t off_in, uint64_t* out, size_t m,
+                              size_t row_stride_out, uint64_t off_out, size_t cols_per_block, void* stream) try {
+    return table_lde_rows_dev(rows, n, n_cols, row_stride_in, off_in, out, m, row_stride_out, off_out, cols_per_block, 1, stream);
+} TF_ABI_CATCH
+int tf_table_lde_rows_xfe_dev(const uint64_t* rows, size_t n, size_t n_cols, size_t row_stride_in, uint64_t off_in, uint64_t* out, size_t m,
+                              size_t row_stride_out, uint64_t off_out, size_t cols_per_block, void* stream) try {
+    return table_lde_rows_dev(rows, n, n_cols, row_stride_in, off_in, out, m, row_stride_out, off_out, cols_per_block, 3, stream);
+} TF_ABI_CATCH
+size_t tf_table_lde_rows_workspace(size_t n, size_t m, size_t n_cols, int width, size_t cols_per_block) try {
+    return table_lde_rows_workspace(n, m, n_cols, width, cols_per_block);
+} catch (...) {
+    ::tfi::abi_caught("C++ exception in tf_table_lde_rows_workspace", TF_ERR_INTERNAL);
+    return 0;
+}
 static int coset_extrapolate_host(uint64_t offset, const uint64_t* cw, size_t n, size_t batch, const uint64_t* pts, size_t np,
                                   uint64_t* out, int L) {
     if (n == 0) return TF_ERR_LEN_NOT_POWER_OF_TWO;

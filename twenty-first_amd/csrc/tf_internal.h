@@ -13,6 +13,7 @@
 //   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
 //   tf_algebra.hip add / sub / neg, scalar_mul, scale, formal_derivative, degree and weighted sums of columns (algebra_kernels.h)
 //   tf_points.hip get_colinear_y / are_colinear, element-wise mod_pow, geometric sequences and index gathers (points_kernels.h)
+//   tf_table.hip  tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (table_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 //   tf_temp.h     (header, included by the units above) DevTemp, the one owner of a stream-ordered temporary; the staged upload, the
 //                 per-unit Tip5 constants upload and the host round trip that every unit used to spell out for itself
@@ -318,6 +319,17 @@ int are_colinear(const u64* xs, const u64* ys, size_t n_groups, size_t k, int wx
 int mod_pow(const u64* bases, size_t n_bases, const uint64_t* exps, size_t n_exps, int width, u64* out, size_t n, bool host, void* stream);
 int powers(const u64* first, const u64* ratio, int width, u64* out, size_t n, bool host, void* stream);
 int gather_elements_dev(const u64* src, size_t src_len, int width, const uint32_t* indices, size_t n, u64* out, void* stream, int* d_status);
+
+// ------------------------------------------------------------------------------------ tf_table.hip
+// the table calls of include/tf_hip.h ("Tables"): host = false takes device pointers and only enqueues on `stream`, host = true
+// takes host pointers and blocks.  Strides count words, the other lengths elements of `width` words.
+int table_transpose(const u64* src, size_t n_outer, size_t n_inner, int width, size_t src_stride, u64* dst, size_t dst_stride, size_t batch, bool host,
+                    void* stream);
+int table_gather_rows(const u64* table, int layout, size_t n_rows, size_t n_cols, int width, size_t stride, const uint32_t* indices, size_t k, u64* out,
+                      size_t out_stride, size_t batch, bool host, void* stream, int* d_status);
+int table_lde_rows_dev(const u64* rows, size_t n, size_t n_cols, size_t row_stride_in, u64 offset_in, u64* out, size_t m, size_t row_stride_out,
+                       u64 offset_out, size_t cols_per_block, int width, void* stream);
+size_t table_lde_rows_workspace(size_t n, size_t m, size_t n_cols, int width, size_t cols_per_block);
 
 // ------------------------------------------------------------------------------------ tf_poly.hip
 extern std::atomic<int> g_batch_eval_route;

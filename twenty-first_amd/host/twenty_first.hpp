@@ -184,6 +184,41 @@ inline std::vector<FF> powers(FF first, FF ratio, size_t n) {
     return out;
 }
 
+// ---- tables between the column-major and the row-major layout (include/tf_hip.h, "Tables") ---------------------------------
+// column-major: n_cols columns of n_rows elements back to back (what hash_table_rows / MerkleTree::from_columns read);
+// row-major: n_rows rows of n_cols elements back to back (what hash_varlen_rows reads); `batch` tables one after the other
+template <class FF>
+inline std::vector<FF> table_columns_to_rows(const std::vector<FF>& table, size_t n_rows, size_t n_cols, size_t batch = 1) {
+    if (table.size() != batch * n_rows * n_cols) throw std::invalid_argument("table_columns_to_rows: the table is not batch x n_cols x n_rows");
+    constexpr int W = sizeof(FF) / 8;
+    std::vector<FF> rows(table.size());
+    check(tf_table_transpose(reinterpret_cast<const uint64_t*>(table.data()), n_cols, n_rows, W, n_rows * W, reinterpret_cast<uint64_t*>(rows.data()),
+                             n_cols * W, batch), "table_columns_to_rows");
+    return rows;
+}
+template <class FF>
+inline std::vector<FF> table_rows_to_columns(const std::vector<FF>& rows, size_t n_rows, size_t n_cols, size_t batch = 1) {
+    if (rows.size() != batch * n_rows * n_cols) throw std::invalid_argument("table_rows_to_columns: the table is not batch x n_rows x n_cols");
+    constexpr int W = sizeof(FF) / 8;
+    std::vector<FF> table(rows.size());
+    check(tf_table_transpose(reinterpret_cast<const uint64_t*>(rows.data()), n_rows, n_cols, W, n_cols * W, reinterpret_cast<uint64_t*>(table.data()),
+                             n_rows * W, batch), "table_rows_to_columns");
+    return table;
+}
+// rows indices[q] of every table, k rows of n_cols elements per table; layout is TF_TABLE_COLUMN_MAJOR or TF_TABLE_ROW_MAJOR.  An
+// index >= n_rows throws (BackendError, code 17)
+template <class FF>
+inline std::vector<FF> table_gather_rows(const std::vector<FF>& table, int layout, size_t n_rows, size_t n_cols, const std::vector<uint32_t>& indices,
+                                         size_t batch = 1) {
+    if (table.size() != batch * n_rows * n_cols) throw std::invalid_argument("table_gather_rows: the table is not batch x n_rows x n_cols");
+    constexpr int W = sizeof(FF) / 8;
+    std::vector<FF> out(batch * indices.size() * n_cols);
+    check(tf_table_gather_rows(reinterpret_cast<const uint64_t*>(table.data()), layout, n_rows, n_cols, W,
+                               (layout == TF_TABLE_ROW_MAJOR ? n_cols : n_rows) * W, indices.data(), indices.size(),
+                               reinterpret_cast<uint64_t*>(out.data()), n_cols * W, batch), "table_gather_rows");
+    return out;
+}
+
 // the field a product of an A and a B lives in (x_field_element.rs:491-556): the extension field if either is
 template <class A, class B>
 using ProductField = std::conditional_t<(sizeof(A) >= sizeof(B)), A, B>;
