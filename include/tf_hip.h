@@ -477,6 +477,48 @@ int tf_merkle_auth_structure_from_leafs(const uint64_t *leafs, size_t num_leafs,
 int tf_merkle_auth_structure_from_leafs_dev(const uint64_t *d_leafs, size_t num_leafs, size_t batch, const uint64_t *leaf_indices, size_t k,
                                             uint64_t *d_out_digests, size_t capacity_digests, size_t *out_count, uint64_t *d_roots, void *stream);
 size_t tf_merkle_auth_structure_from_leafs_workspace(size_t num_leafs, size_t batch, size_t k_nodes);
+/* The same openings with the leaf indices in DEVICE memory: n_lists independent lists of k u32 each, list l at d_leaf_indices + l * k,
+ * the layout tf_tip5_sponge_sample_indices_dev writes; all lists open trees of num_leafs leafs.  MerkleTree::
+ * authentication_structure_node_indices (util_types/merkle_tree.rs:449-504) is computed by a kernel where the indices lie: the calls
+ * only enqueue on `stream`, read nothing back and never synchronise.  k <= 8192 per list (index lists as long as the tree is wide
+ * keep the host-index calls above).
+ *   tf_merkle_auth_structure_max_nodes   sum over the levels l below the root of min(k, (num_leafs >> l) / 2): no list of k indices
+ *       has more structure nodes, so it is what `capacity` is sized with -- the true count is device data.  An upper bound only:
+ *       k = 1 attains it, two or more paths share nodes near the root and stay below it.  Pure host arithmetic; 0 for arguments the calls reject.
+ *   tf_merkle_auth_structure_indices_dev   the plan alone: list l writes its node indices (the reference's order, descending) to
+ *       d_node_indices + l * capacity, their number to d_counts[l] and, when d_level_ends is given, 32 run ends to
+ *       d_level_ends + 32 * l: entry j = the structure nodes on the levels of n, n / 2, ..., n >> j nodes (descending order puts the
+ *       leaf level first, so every level is one run); entries for levels at or above the root repeat the count.
+ *   tf_merkle_authentication_structure_sampled_dev   the gather from node arrays: n_lists * trees_per_list trees of 2 num_leafs digests
+ *       each, as tf_merkle_build leaves them; tree t is opened at list t / trees_per_list (a prover's main, auxiliary and quotient trees
+ *       under one transcript, many transcripts at once).  d_out_digests is tree-major, `capacity` digests per tree: the first
+ *       d_counts[list] are the structure, the words behind them stay as they were.
+ *   tf_merkle_auth_structure_from_leafs_sampled_dev   commit and open: the sweep of tf_merkle_auth_structure_from_leafs_dev over the
+ *       n_lists * trees_per_list trees of d_leafs, same output layout; d_roots is NULL or receives one root per tree, whatever the
+ *       status.  tf_merkle_auth_structure_from_leafs_sampled_workspace is what the call requests from the pool for `trees` trees in
+ *       all: the request of the host-index form plus the plan (4 bytes per node of the bound and 128 bytes per list); never shrinks
+ *       as `trees` grows; 0 for arguments the call rejects.
+ * The return value is what the host can decide, before any device is touched and in this order: TF_ERR_TOO_FEW_LEAFS,
+ * TF_ERR_INCORRECT_NUMBER_OF_LEAFS, TF_ERR_TREE_TOO_HIGH (more than 2^31 leafs), TF_ERR_LEN_TOO_LARGE (k > 8192; 2^31 lists or more;
+ * more than 2^31 trees), TF_ERR_NULL_POINTER (d_status, always; with n_lists > 0: d_leaf_indices with k > 0, d_counts; the trees and,
+ * with capacity > 0, the output).  n_lists == 0 or trees_per_list == 0: TF_OK, nothing is enqueued.
+ * What depends on the indices goes to *d_status, one caller-owned int in device memory that keeps the first non-zero code (as
+ * tf_table_gather_rows_dev):
+ *   a list with an index >= num_leafs stores TF_ERR_LEAF_INDEX_INVALID and gets d_counts[l] = 0;
+ *   a list with more than `capacity` nodes stores TF_ERR_BUFFER_TOO_SMALL and gets its full count in d_counts[l] (the plan alone has
+ *   then written the first `capacity` node indices);
+ * neither writes a digest for its trees, and the other lists of the call are unaffected.  k == 0, every leaf opened, and
+ * num_leafs == 1 all give count 0. */
+size_t tf_merkle_auth_structure_max_nodes(size_t num_leafs, size_t k);
+int tf_merkle_auth_structure_indices_dev(size_t num_leafs, const uint32_t *d_leaf_indices, size_t k, size_t n_lists, uint32_t *d_node_indices,
+                                         size_t capacity, uint32_t *d_counts, uint32_t *d_level_ends, void *stream, int *d_status);
+int tf_merkle_authentication_structure_sampled_dev(const uint64_t *d_nodes, size_t num_leafs, const uint32_t *d_leaf_indices, size_t k,
+                                                   size_t n_lists, size_t trees_per_list, uint64_t *d_out_digests, size_t capacity,
+                                                   uint32_t *d_counts, void *stream, int *d_status);
+int tf_merkle_auth_structure_from_leafs_sampled_dev(const uint64_t *d_leafs, size_t num_leafs, const uint32_t *d_leaf_indices, size_t k,
+                                                    size_t n_lists, size_t trees_per_list, uint64_t *d_out_digests, size_t capacity,
+                                                    uint32_t *d_counts, uint64_t *d_roots, void *stream, int *d_status);
+size_t tf_merkle_auth_structure_from_leafs_sampled_workspace(size_t num_leafs, size_t trees, size_t k, size_t n_lists);
 
 /* ---------------------------------------------------------------------------------------------
  * Inclusion proofs, batched.   replaces  MerkleTreeInclusionProof::try_verify / verify   util_types/merkle_tree.rs:727-748

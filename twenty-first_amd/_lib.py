@@ -182,6 +182,11 @@ SIGNATURES = {
     "tf_merkle_auth_structure_from_leafs": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, C.POINTER(C.c_size_t), _vp]),
     "tf_merkle_auth_structure_from_leafs_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, C.POINTER(C.c_size_t), _vp, _vp]),
     "tf_merkle_auth_structure_from_leafs_workspace": (_sz, [_sz, _sz, _sz]),
+    "tf_merkle_auth_structure_max_nodes": (_sz, [_sz, _sz]),
+    "tf_merkle_auth_structure_indices_dev": (C.c_int, [_sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "tf_merkle_authentication_structure_sampled_dev": (C.c_int, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "tf_merkle_auth_structure_from_leafs_sampled_dev": (C.c_int, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "tf_merkle_auth_structure_from_leafs_sampled_workspace": (_sz, [_sz, _sz, _sz, _sz]),
     "tf_mmr_append": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _vp, _vp]),
     "tf_mmr_append_dev": (C.c_int, [C.c_uint64, _vp, _vp, _sz, _vp, _vp, _vp]),
     "tf_mmr_bag_peaks": (C.c_int, [_vp, _sz, _vp, _vp]),

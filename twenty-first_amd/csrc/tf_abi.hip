@@ -1086,6 +1086,37 @@ size_t tf_merkle_auth_structure_from_leafs_workspace(size_t num_leafs, size_t ba
     return 0;
 }
 
+// the same openings with the leaf indices in device memory (tf_merkle_open.hip, second half)
+size_t tf_merkle_auth_structure_max_nodes(size_t num_leafs, size_t k) try {
+    return merkle_plan_max_nodes(num_leafs, k);
+} catch (...) {
+    ::tfi::abi_caught("C++ exception in tf_merkle_auth_structure_max_nodes", TF_ERR_INTERNAL);
+    return 0;
+}
+int tf_merkle_auth_structure_indices_dev(size_t num_leafs, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, uint32_t* d_node_indices,
+                                         size_t capacity, uint32_t* d_counts, uint32_t* d_level_ends, void* stream, int* d_status) try {
+    return merkle_plan_dev(num_leafs, d_leaf_indices, k, n_lists, d_node_indices, capacity, d_counts, d_level_ends, static_cast<hipStream_t>(stream),
+                           d_status);
+} TF_ABI_CATCH
+int tf_merkle_authentication_structure_sampled_dev(const uint64_t* d_nodes, size_t num_leafs, const uint32_t* d_leaf_indices, size_t k,
+                                                   size_t n_lists, size_t trees_per_list, uint64_t* d_out_digests, size_t capacity,
+                                                   uint32_t* d_counts, void* stream, int* d_status) try {
+    return merkle_nodes_sampled_dev(d_nodes, num_leafs, d_leaf_indices, k, n_lists, trees_per_list, d_out_digests, capacity, d_counts,
+                                    static_cast<hipStream_t>(stream), d_status);
+} TF_ABI_CATCH
+int tf_merkle_auth_structure_from_leafs_sampled_dev(const uint64_t* d_leafs, size_t num_leafs, const uint32_t* d_leaf_indices, size_t k,
+                                                    size_t n_lists, size_t trees_per_list, uint64_t* d_out_digests, size_t capacity,
+                                                    uint32_t* d_counts, uint64_t* d_roots, void* stream, int* d_status) try {
+    return merkle_open_sampled_dev(d_leafs, num_leafs, d_leaf_indices, k, n_lists, trees_per_list, d_out_digests, capacity, d_counts, d_roots,
+                                   static_cast<hipStream_t>(stream), d_status);
+} TF_ABI_CATCH
+size_t tf_merkle_auth_structure_from_leafs_sampled_workspace(size_t num_leafs, size_t trees, size_t k, size_t n_lists) try {
+    return merkle_open_sampled_workspace(num_leafs, trees, k, n_lists);
+} catch (...) {
+    ::tfi::abi_caught("C++ exception in tf_merkle_auth_structure_from_leafs_sampled_workspace", TF_ERR_INTERNAL);
+    return 0;
+}
+
 int tf_merkle_verify_proofs(const uint32_t* tree_heights, size_t n_proofs, const uint64_t* leaf_offsets, const uint64_t* leaf_indices,
                             const uint64_t* leaf_digests, const uint64_t* auth_offsets, const uint64_t* auth_digests,
                             const uint64_t* expected_roots, int* statuses) try {

@@ -263,6 +263,16 @@ int merkle_open_dev(const u64* d_leafs, size_t n, size_t batch, const uint64_t* 
 int merkle_open_host(const u64* leafs, size_t n, size_t batch, const uint64_t* leaf_indices, size_t k, u64* out, size_t capacity, size_t* out_count,
                      u64* roots);
 size_t merkle_open_workspace(size_t n, size_t batch, size_t k_nodes);
+// the same with the leaf indices in DEVICE memory (n_lists lists of k u32): the plan is made by a kernel, nothing is read back, and
+// what depends on the indices goes to *d_status.  merkle_plan_max_nodes bounds a list's structure nodes (host arithmetic).
+size_t merkle_plan_max_nodes(size_t n, size_t k);
+int merkle_plan_dev(size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, uint32_t* d_node_indices, size_t capacity, uint32_t* d_counts,
+                    uint32_t* d_level_ends, hipStream_t s, int* d_status);
+int merkle_nodes_sampled_dev(const u64* d_nodes, size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, size_t trees_per_list,
+                             u64* d_out, size_t capacity, uint32_t* d_counts, hipStream_t s, int* d_status);
+int merkle_open_sampled_dev(const u64* d_leafs, size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, size_t trees_per_list,
+                            u64* d_out, size_t capacity, uint32_t* d_counts, u64* d_roots, hipStream_t s, int* d_status);
+size_t merkle_open_sampled_workspace(size_t n, size_t trees, size_t k, size_t n_lists);
 
 // ------------------------------------------------------------------------------------ tf_sponge.hip
 // the sponge calls of include/tf_hip.h.  absorb: pad = false, len = 10 n_chunks, no offsets; pad_and_absorb_all: pad = true (the _dev

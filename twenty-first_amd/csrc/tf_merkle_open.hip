@@ -13,8 +13,14 @@
 //   leaf level    wanted leafs are read from the caller's array (a tree that is narrow from its leafs is all top block).
 // The plan (node -> slot, per level) is built on the host from the host's leaf indices and reaches the device through pinned staging, so
 // the _dev form never waits for its stream.
+//
+// The *_sampled forms (second half of this file) take their leaf indices from DEVICE memory, n_lists lists of k u32 each as the Tip5
+// sponges sample them: merkle_plan_kernel (merkle_plan_kernels.h) computes the plan where the indices lie, and the gather from a node
+// array and the same sweep run from it.  The host never sees an index or a count; it sizes grids and work space by the bound
+// plan_max_nodes, and what depends on the data goes to the caller's status word.
 #include "tf_temp.h"
 #include "merkle_open_kernels.h"
+#include "merkle_plan_kernels.h"
 
 namespace tfi {
 namespace {
@@ -182,6 +188,122 @@ int open_run(const u64* d_leafs, size_t n, size_t batch, const std::vector<unsig
     return emit(top, 10 * w, d_plan + top_first, count - top_first, batch, d_out, out_ts, s);
 }
 
+// ------------------------------------------------------------------------------------ leaf indices in device memory
+constexpr size_t kPlanMaxK = tfk::kPlanMaxIndices;
+constexpr size_t kPlanMaxLists = (size_t(1) << 31) - 1;  // one workgroup per list: the grid's x dimension
+constexpr size_t kPlanMaxTrees = size_t(1) << 31;
+
+// Structure nodes on the level of w nodes, at most: they are siblings of distinct path nodes (<= k of them) and lie outside the path
+// set, which holds at least as many nodes of the level as they do (<= w / 2).
+size_t plan_level_bound(size_t w, size_t k) { return std::min(k, w / 2); }
+
+// Everything the sampled entry points decide before a device is needed, in the order include/tf_hip.h gives
+int sampled_args(size_t n, size_t k, size_t n_lists, size_t trees_per_list, const void* d_leaf_indices, const void* d_counts, const int* d_status) {
+    TRY(check_leaves(n));
+    if (n > kMaxOpenLeafs) return TF_ERR_TREE_TOO_HIGH;
+    if (k > kPlanMaxK || n_lists > kPlanMaxLists || (trees_per_list && n_lists > kPlanMaxTrees / trees_per_list)) return TF_ERR_LEN_TOO_LARGE;
+    if (!d_status || (n_lists && ((k && !d_leaf_indices) || !d_counts))) return TF_ERR_NULL_POINTER;
+    return TF_OK;
+}
+
+// the plan of n_lists lists: `stride` u32 of node indices per list, then (sweep only) kPlanLevels run ends per list
+size_t plan_words(size_t n_lists, size_t stride, bool with_ends) { return n_lists * (stride + (with_ends ? size_t(tfk::kPlanLevels) : 0)); }
+size_t plan_bytes(size_t n_lists, size_t stride, bool with_ends) { return (plan_words(n_lists, stride, with_ends) * sizeof(uint32_t) + 7) & ~size_t(7); }
+
+// One workgroup per list, sized by k: one wave up to 64 indices, 256 threads up to 1024, 1024 threads up to kPlanMaxK.
+int launch_plan(size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, uint32_t* d_node_indices, size_t stride, size_t capacity,
+                uint32_t* d_counts, uint32_t* d_level_ends, int* d_status, hipStream_t s) {
+    if (n_lists == 0) return TF_OK;
+    unsigned padded = 1;
+    while (padded < k) padded <<= 1;
+    const int height = __builtin_ctzll((unsigned long long)n);
+    const unsigned cap = (unsigned)std::min<size_t>(capacity, 0xFFFFFFFFu);  // (a count is far below 2^32: the clamp changes no verdict)
+#define TF_PLAN_LAUNCH(T, CAP)                                                                                                                 \
+    hipLaunchKernelGGL((tfk::merkle_plan_kernel<T, CAP>), dim3((unsigned)n_lists), dim3(T), 0, s, d_leaf_indices, (unsigned)k, padded, (unsigned)n, \
+                       height, d_node_indices, (unsigned long long)stride, cap, d_counts, d_level_ends, d_status, (int)TF_ERR_LEAF_INDEX_INVALID, \
+                       (int)TF_ERR_BUFFER_TOO_SMALL)
+    if (k <= 64)
+        TF_PLAN_LAUNCH(64, 64);
+    else if (k <= 1024)
+        TF_PLAN_LAUNCH(256, 1024);
+    else
+        TF_PLAN_LAUNCH(1024, tfk::kPlanMaxIndices);
+#undef TF_PLAN_LAUNCH
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+}
+
+unsigned plan_copy_blocks(size_t trees, size_t bound) {
+    const long long total = (long long)(trees * bound) * 5;
+    return (unsigned)std::min<long long>((total + 255) / 256, 1ll << 20);
+}
+
+// emit() from the device plan: level `run` of the sweep (to_count: the top block, every level from `run` up), `bound` slots per tree
+int emit_sampled(const u64* level, long long level_ts, size_t first_node, const uint32_t* d_plan, size_t stride, const uint32_t* d_counts,
+                 const uint32_t* d_ends, int run, bool to_count, size_t capacity, size_t trees_per_list, size_t trees, size_t bound, u64* out,
+                 hipStream_t s) {
+    if (bound == 0) return TF_OK;
+    hipLaunchKernelGGL(tfk::merkle_plan_emit_kernel, dim3(plan_copy_blocks(trees, bound)), dim3(256), 0, s, level, level_ts, (unsigned)first_node, d_plan,
+                       (long long)stride, d_counts, d_ends, run, to_count ? 1 : 0, (unsigned)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                       (long long)trees_per_list, (long long)trees, (long long)bound, out, 5 * (long long)capacity);
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+}
+
+size_t sampled_workspace_bytes(size_t n, size_t trees, size_t k, size_t n_lists) {
+    const size_t sweep = open_workspace_bytes(n, trees, 0);
+    if (!sweep || k > kPlanMaxK || n_lists == 0 || n_lists > kPlanMaxLists) return 0;
+    return sweep + plan_bytes(n_lists, merkle_plan_max_nodes(n, k), true);
+}
+
+// open_run with the plan made on the device: the same buffers, the same hashing launches, emit_sampled for emit
+int open_run_sampled(const u64* d_leafs, size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, size_t trees_per_list, u64* d_out,
+                     size_t capacity, uint32_t* d_counts, u64* d_roots, int* d_status, hipStream_t s) {
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    TRY(ensure_tip5(ctx));
+    const size_t batch = n_lists * trees_per_list, stride = merkle_plan_max_nodes(n, k);
+    const OpenLayout lay = open_layout(n, batch);
+    const long long N = (long long)n, top_w = lay.top_w;
+
+    DevTemp ws(s);
+    if (ws.alloc_bytes(sampled_workspace_bytes(n, batch, k, n_lists), "merkle open (sampled)")) return TF_ERR_TREE_TOO_HIGH;
+    u64* a = ws.p;
+    u64* b = a + 5 * lay.a;
+    u64* top = b + 5 * lay.b;
+    // (the plan sits behind the digests of the REQUEST, as in open_run)
+    uint32_t* d_plan = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws.p) + open_workspace_bytes(n, batch, 0));
+    uint32_t* d_ends = d_plan + n_lists * stride;
+    TRY(launch_plan(n, d_leaf_indices, k, n_lists, d_plan, stride, capacity, d_counts, d_ends, d_status, s));
+    if (stride == 0 && !d_roots) return TF_OK;  // no index, or a tree that is its root: the counts are all there is
+    auto emit_level = [&](const u64* level, long long level_ts, long long w, int run) {
+        return emit_sampled(level, level_ts, (size_t)w, d_plan, stride, d_counts, d_ends, run, false, capacity, trees_per_list, batch,
+                            plan_level_bound((size_t)w, k), d_out, s);
+    };
+
+    const u64* level = d_leafs;
+    long long w = N, level_ts = 5 * N;
+    int run = 0;
+    if (!merkle_narrow_from(N, batch)) {
+        TRY(emit_level(d_leafs, 5 * N, N, run++));
+        w = N / 2;
+        TRY(launch_hash_pairs(d_leafs, a, nullptr, w * (long long)batch, w, 5 * N, 5 * w, 0, s));
+        while (!merkle_narrow_from(w, batch)) {
+            TRY(emit_level(a, 5 * w, w, run++));
+            const long long nw = w / 2;
+            TRY(launch_hash_pairs(a, b, nullptr, nw * (long long)batch, nw, 5 * w, 5 * nw, 0, s));
+            std::swap(a, b);
+            w = nw;
+        }
+        level = a;
+        level_ts = 5 * w;
+    }
+    TRY(merkle_narrow_levels(level, level_ts, w, top, 10 * w, d_roots, nullptr, batch, true, s));
+    size_t top_bound = 0;
+    for (size_t lw = (size_t)top_w; lw > 1; lw /= 2) top_bound += plan_level_bound(lw, k);
+    return emit_sampled(top, 10 * w, 0, d_plan, stride, d_counts, d_ends, run, true, capacity, trees_per_list, batch, top_bound, d_out, s);
+}
+
 }  // namespace
 
 size_t merkle_open_workspace(size_t n, size_t batch, size_t k_nodes) { return open_workspace_bytes(n, batch, k_nodes); }
@@ -215,5 +337,52 @@ int merkle_open_host(const u64* leafs, size_t n, size_t batch, const uint64_t* l
     if (roots) TRY(d2h(roots, droots.p, batch * 5, s));
     return sync(s);
 }
+
+size_t merkle_plan_max_nodes(size_t n, size_t k) {
+    if (check_leaves(n) || n > kMaxOpenLeafs || k > kPlanMaxK) return 0;
+    size_t sum = 0;
+    for (size_t w = n; w > 1; w /= 2) sum += plan_level_bound(w, k);
+    return sum;
+}
+
+int merkle_plan_dev(size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, uint32_t* d_node_indices, size_t capacity, uint32_t* d_counts,
+                    uint32_t* d_level_ends, hipStream_t s, int* d_status) {
+    TRY(sampled_args(n, k, n_lists, 0, d_leaf_indices, d_counts, d_status));
+    if (n_lists && capacity && !d_node_indices) return TF_ERR_NULL_POINTER;
+    if (n_lists == 0) return TF_OK;
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    return launch_plan(n, d_leaf_indices, k, n_lists, d_node_indices, capacity, capacity, d_counts, d_level_ends, d_status, s);
+}
+
+int merkle_nodes_sampled_dev(const u64* d_nodes, size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, size_t trees_per_list,
+                             u64* d_out, size_t capacity, uint32_t* d_counts, hipStream_t s, int* d_status) {
+    TRY(sampled_args(n, k, n_lists, trees_per_list, d_leaf_indices, d_counts, d_status));
+    if (n_lists && trees_per_list && (!d_nodes || (capacity && !d_out))) return TF_ERR_NULL_POINTER;
+    if (n_lists == 0 || trees_per_list == 0) return TF_OK;
+    DeviceCtx* ctx = nullptr;
+    TRY(current_ctx(&ctx));
+    const size_t stride = merkle_plan_max_nodes(n, k), trees = n_lists * trees_per_list;
+    DevTemp plan(s);
+    TRY(plan.alloc_bytes(plan_bytes(n_lists, stride, false), "merkle plan"));
+    TRY(launch_plan(n, d_leaf_indices, k, n_lists, plan.as<uint32_t>(), stride, capacity, d_counts, nullptr, d_status, s));
+    const size_t bound = std::min(stride, capacity);  // (a list with more nodes than `capacity` writes nothing)
+    if (bound == 0) return TF_OK;
+    hipLaunchKernelGGL(tfk::merkle_plan_gather_kernel, dim3(plan_copy_blocks(trees, bound)), dim3(256), 0, s, d_nodes, 10 * (long long)n,
+                       plan.as<const uint32_t>(), (long long)stride, d_counts, (unsigned)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                       (long long)trees_per_list, (long long)trees, (long long)bound, d_out, 5 * (long long)capacity);
+    HIPCHK(hipGetLastError());
+    return TF_OK;
+}
+
+int merkle_open_sampled_dev(const u64* d_leafs, size_t n, const uint32_t* d_leaf_indices, size_t k, size_t n_lists, size_t trees_per_list,
+                            u64* d_out, size_t capacity, uint32_t* d_counts, u64* d_roots, hipStream_t s, int* d_status) {
+    TRY(sampled_args(n, k, n_lists, trees_per_list, d_leaf_indices, d_counts, d_status));
+    if (n_lists && trees_per_list && (!d_leafs || (capacity && !d_out))) return TF_ERR_NULL_POINTER;
+    if (n_lists == 0 || trees_per_list == 0) return TF_OK;
+    return open_run_sampled(d_leafs, n, d_leaf_indices, k, n_lists, trees_per_list, d_out, capacity, d_counts, d_roots, d_status, s);
+}
+
+size_t merkle_open_sampled_workspace(size_t n, size_t trees, size_t k, size_t n_lists) { return sampled_workspace_bytes(n, trees, k, n_lists); }
 
 }  // namespace tfi
