@@ -847,6 +847,51 @@ int tf_gather_elements_dev(const uint64_t *d_src, size_t src_len, int width, con
                            void *stream, int *d_status);
 
 /* ---------------------------------------------------------------------------------------------
+ * FRI folding: the commit side of FRI, split-and-fold of whole codewords, one to many levels per call.  replaces
+ *   Polynomial::get_colinear_y   math/polynomial.rs:386-394   through (x_i, c[i]) and (-x_i, c[i + n/2]) at the challenge, for every
+ *                                                             i < n/2 of a codeword on an evaluation domain
+ * A codeword c of n = 2^k elements (n >= 2) lies on {g w_n^i} in natural order, g = offset_raw a non-zero BFieldElement and w_n the
+ * reference's primitive_root_of_unity(n).  One level folds it by the challenge alpha into n/2 elements on {g^2 w_{n/2}^i}:
+ *     out[i] = get_colinear_y((x_i, c[i]), (-x_i, c[i + n/2]), alpha) = 1/2 [(1 + alpha / x_i) c[i] + (1 - alpha / x_i) c[i + n/2]],
+ *     x_i = g w_n^i, 0 <= i < n/2
+ * and `levels` = r with the challenges alpha_1 .. alpha_r is r such folds in a row: level j runs on the offset g^(2^(j-1)) and the
+ * length n / 2^(j-1), the result has n / 2^r elements on the offset g^(2^r).  Words are canonical raw Montgomery words in and out,
+ * so the result is word for word that of the composition it replaces (tf_powers twice, tf_get_colinear_y with n_p2x = 1).
+ *   layout           codewords holds `batch` codewords of n elements of width_c words each, packed; out holds batch x n / 2^levels
+ *                    elements of width_a words.  out may not overlap an input.
+ *   widths           (width_c, width_a) is (1, 1), (3, 3) or (1, 3).  In the mixed form a BFieldElement codeword is folded by an
+ *                    XFieldElement challenge: the result is word for word that of (3, 3) on the lifted codeword, and the levels after
+ *                    the first run as (3, 3).
+ *   challenges       n_sets x levels elements of width_a words; n_sets is 1 (one set for every codeword) or `batch` (set b for
+ *                    codeword b: many transcripts).  In the _dev form this is device memory, exactly as
+ *                    tf_tip5_sponge_sample_scalars_dev leaves it.
+ *   forms            tf_fri_fold takes host pointers and returns when the result is in place.  tf_fri_fold_dev takes device pointers
+ *                    and only enqueues on `stream`: it never synchronises and copies nothing back.  Nothing in a fold depends on the
+ *                    data, so there is no status word.
+ *   passes           one launch folds up to R_max = 4 levels in registers; more levels run as several passes, R_max each and the
+ *                    remainder last, with the intermediates in stream-ordered temporaries from the library's pool (a failed
+ *                    allocation is TF_ERR_OUT_OF_MEMORY).  tf_fri_fold_plan writes the levels of each pass (at most `capacity`
+ *                    entries; levels_per_pass may be NULL) and returns the number of passes, or minus the status the fold would
+ *                    return for these arguments.  tf_fri_fold_workspace returns the bytes of those temporaries: nothing for one
+ *                    pass, the first intermediate (batch x n / 2^R_max elements of width_a words) for two, the first and the second
+ *                    for three and more (the later, smaller ones reuse the two blocks in turn); 0 for a call that is rejected or
+ *                    empty.  Both are host arithmetic and need no device.
+ *   empty calls      batch == 0: TF_OK, nothing touched, NULL pointers allowed.
+ *   errors           returned before any HIP call, in this order: TF_ERR_NULL_POINTER; TF_ERR_INVALID_ARGUMENT (a width pair not
+ *                    listed above, levels == 0, n_sets neither 1 nor batch); TF_ERR_LEN_NOT_POWER_OF_TWO (n, 0 included);
+ *                    TF_ERR_INVALID_ARGUMENT (2^levels > n); TF_ERR_LEN_TOO_LARGE (n above 2^30, or more than 2^35 words read);
+ *                    TF_ERR_INVERSE_OF_ZERO (offset_raw == 0: x_i == -x_i, the reference's assert_ne!(x0, x1), the code
+ *                    tf_get_colinear_y uses); then TF_ERR_NO_DEVICE on a machine without a GPU.
+ * No division: the inverse points g^-1 w_n^-i are a geometric sequence, and the twiddles inside a pass and the halvings are
+ * power-of-two products (csrc/fri_kernels.h). */
+int tf_fri_fold(const uint64_t *codewords, size_t n, size_t batch, int width_c, uint64_t offset_raw, const uint64_t *challenges,
+                size_t levels, size_t n_sets, int width_a, uint64_t *out);
+int tf_fri_fold_dev(const uint64_t *d_codewords, size_t n, size_t batch, int width_c, uint64_t offset_raw, const uint64_t *d_challenges,
+                    size_t levels, size_t n_sets, int width_a, uint64_t *d_out, void *stream);
+size_t tf_fri_fold_workspace(size_t n, size_t batch, int width_c, int width_a, size_t levels);
+int tf_fri_fold_plan(size_t n, size_t levels, int width_c, int width_a, int *levels_per_pass, int capacity);
+
+/* ---------------------------------------------------------------------------------------------
  * Tables: moving a table between the two layouts the library itself uses, and opening its rows.  replaces
  *   Array2 .t() / reversed_axes, a prover's own transposes           table_transpose     dst line i, element o = src line o, element i
  *   table.row(i) / select(Axis(0), indices)                          table_gather_rows   out row q = row indices[q]

@@ -139,6 +139,10 @@ SIGNATURES = {
     "tf_powers": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz]),
     "tf_powers_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _vp]),
     "tf_gather_elements_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp]),
+    "tf_fri_fold": (C.c_int, [_vp, _sz, _sz, C.c_int, C.c_uint64, _vp, _sz, _sz, C.c_int, _vp]),
+    "tf_fri_fold_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, C.c_uint64, _vp, _sz, _sz, C.c_int, _vp, _vp]),
+    "tf_fri_fold_workspace": (_sz, [_sz, _sz, C.c_int, C.c_int, _sz]),
+    "tf_fri_fold_plan": (C.c_int, [_sz, _sz, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "tf_table_transpose": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz]),
     "tf_table_transpose_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz, _vp]),
     "tf_table_gather_rows": (C.c_int, [_vp, C.c_int, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _sz]),

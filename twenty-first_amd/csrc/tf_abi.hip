@@ -962,6 +962,24 @@ int tf_gather_elements_dev(const uint64_t* src, size_t src_len, int width, const
                            int* d_status) try {
     return gather_elements_dev(src, src_len, width, indices, n, out, stream, d_status);
 } TF_ABI_CATCH
+// the FRI split-and-fold, one to many levels per call (tf_fri.hip)
+int tf_fri_fold(const uint64_t* codewords, size_t n, size_t batch, int width_c, uint64_t offset_raw, const uint64_t* challenges, size_t levels,
+                size_t n_sets, int width_a, uint64_t* out) try {
+    return fri_fold(codewords, n, batch, width_c, offset_raw, challenges, levels, n_sets, width_a, out, true, nullptr);
+} TF_ABI_CATCH
+int tf_fri_fold_dev(const uint64_t* codewords, size_t n, size_t batch, int width_c, uint64_t offset_raw, const uint64_t* challenges, size_t levels,
+                    size_t n_sets, int width_a, uint64_t* out, void* stream) try {
+    return fri_fold(codewords, n, batch, width_c, offset_raw, challenges, levels, n_sets, width_a, out, false, stream);
+} TF_ABI_CATCH
+size_t tf_fri_fold_workspace(size_t n, size_t batch, int width_c, int width_a, size_t levels) try {
+    return fri_fold_workspace(n, batch, width_c, width_a, levels);
+} catch (...) {
+    ::tfi::abi_caught("C++ exception in tf_fri_fold_workspace", TF_ERR_INTERNAL);
+    return 0;
+}
+int tf_fri_fold_plan(size_t n, size_t levels, int width_c, int width_a, int* levels_per_pass, int capacity) try {
+    return fri_fold_plan(n, levels, width_c, width_a, levels_per_pass, capacity);
+} TF_ABI_CATCH
 // tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (tf_table.hip)
 int tf_table_transpose(const uint64_t* src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t* dst, size_t dst_stride,
                        size_t batch) try {

@@ -13,6 +13,7 @@
 //   tf_inverse.hip batch inversion and inverse_or_zero over vectors (inverse_kernels.h), with their host and device flavours
 //   tf_algebra.hip add / sub / neg, scalar_mul, scale, formal_derivative, degree and weighted sums of columns (algebra_kernels.h)
 //   tf_points.hip get_colinear_y / are_colinear, element-wise mod_pow, geometric sequences and index gathers (points_kernels.h)
+//   tf_fri.hip    the FRI split-and-fold of codewords on an evaluation domain, one to many levels per call (fri_kernels.h)
 //   tf_table.hip  tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (table_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 //   tf_temp.h     (header, included by the units above) DevTemp, the one owner of a stream-ordered temporary; the staged upload, the
@@ -329,6 +330,14 @@ int are_colinear(const u64* xs, const u64* ys, size_t n_groups, size_t k, int wx
 int mod_pow(const u64* bases, size_t n_bases, const uint64_t* exps, size_t n_exps, int width, u64* out, size_t n, bool host, void* stream);
 int powers(const u64* first, const u64* ratio, int width, u64* out, size_t n, bool host, void* stream);
 int gather_elements_dev(const u64* src, size_t src_len, int width, const uint32_t* indices, size_t n, u64* out, void* stream, int* d_status);
+
+// ------------------------------------------------------------------------------------ tf_fri.hip
+// the fold of include/tf_hip.h ("FRI folding"): host = false takes device pointers and only enqueues on `stream`, host = true takes
+// host pointers and blocks; the work-space rule and the plan of passes are pure host arithmetic (the plan: passes, or minus a status)
+int fri_fold(const u64* codewords, size_t n, size_t batch, int wc, u64 offset_raw, const u64* challenges, size_t levels, size_t n_sets, int wa, u64* out,
+             bool host, void* stream);
+size_t fri_fold_workspace(size_t n, size_t batch, int wc, int wa, size_t levels);
+int fri_fold_plan(size_t n, size_t levels, int wc, int wa, int* levels_per_pass, int capacity);
 
 // ------------------------------------------------------------------------------------ tf_table.hip
 // the table calls of include/tf_hip.h ("Tables"): host = false takes device pointers and only enqueues on `stream`, host = true
