@@ -1097,6 +1097,52 @@ int tf_debug_ntt_network_dev(int form, uint64_t *d_x, size_t count, void *stream
  * TF_POW2_WIDE (null pointers are skipped). */
 void tf_debug_ntt_network_config(int *lazy, int *asm_bfly, int *asm_pow2, int *pow2_wide);
 
+/* Guard mode for the library's own device memory (debugging aid; process-wide, 0 = off is the default).  Every stream-ordered
+ * temporary of the library -- the work areas of every call, the staged descriptors, every input and output buffer of the host-pointer
+ * forms -- is taken at ONE place and given back at one place.  With tf_debug_temp_guard(mode), mode 1, 2 or 3, each such block is
+ *     [ TF_TEMP_GUARD_WORDS guard words | the request | TF_TEMP_GUARD_WORDS guard words ]
+ * and guards AND request are filled on the caller's stream with the mode's poison: 1 zeros, 2 all ones, 3 canonical pseudo-random
+ * words (word i of the block, counted from its base, is splitmix64 of i + 0xFE4CE reduced to [1, p - 1]: the sequence of tests/fence.py).
+ * When the block is given back, a kernel on the same stream compares both guards with the poison, 32-bit entry by entry (a request that
+ * is no multiple of 8 bytes is guarded from the next 4-byte boundary), and records what it finds in a per-device ledger; then the block
+ * is freed.  In this mode the scratch between the passes of a multi-pass transform is not taken from its block cache but guarded,
+ * checked and freed in the same way.  A kernel that stores past its work area shows in the ledger; a kernel that reads a work word
+ * it never wrote computes with the poison, so its result differs between the modes.  With the mode off, taking and giving back a block
+ * costs one relaxed atomic load and a branch more than without the feature.  Not covered: memory the library keeps for the life of the
+ * process (cached twiddle and power tables, Tip5 constants, a persistent zerofier-tree arena) and its page-locked staging blocks.
+ *
+ * Every allocation site has a label (a short text; the error message of a failed allocation names it too).  The library counts blocks
+ * and bytes REQUESTED per label while the mode is on.
+ *   tf_debug_temp_guard_report  waits for the current device, then copies its ledger into ledger[TF_TEMP_GUARD_LEDGER_WORDS]:
+ *                               [0] blocks checked, [1] blocks with an offending entry, [2] offending 32-bit entries in total,
+ *                               [3] records r that follow (the first 16 offending guards), then per record four words: label id,
+ *                               side (0 front, 1 back), offset of the first offending entry relative to the first entry of the request
+ *                               (two's complement; negative in the front guard), offending entries of that guard.  *n_labels is the
+ *                               number of labels known so far; label_blocks[i] / label_bytes[i], i < min(*n_labels, capacity), are
+ *                               the blocks / bytes requested under label i since the last reset.  A block that is still alive -- the
+ *                               arena of a zerofier-tree handle -- is counted at once but checked only when it is freed.
+ *   tf_debug_temp_guard_reset   waits for the current device, clears its ledger and every label's counters (the label ids stay).
+ *   tf_debug_temp_guard_label   the text of label `id` (valid for the life of the process), null for an unknown id.
+ *   tf_debug_temp_guard_words   TF_TEMP_GUARD_WORDS as the loaded library was built.
+ *   tf_debug_temp_guard_selftest  proves the mechanism: takes one guarded block of n_words words (defect 4: n_words words and four
+ *                               bytes) under the label "selftest" (and one word more for the result, same label), runs a one-thread
+ *                               kernel with ONE planted defect and frees both.  defect 0: none; 1: a 64-bit store at word -1; 2: at
+ *                               word n_words; 3: at word n_words + TF_TEMP_GUARD_WORDS - 1 (the last guard word); 4: a 32-bit store at
+ *                               entry 2 n_words + 1, just behind the odd payload; 5: no store, *out_word = word 0 of the block, which
+ *                               nobody wrote (else *out_word = 0).  Every store lands in the block's own guards.
+ *                               TF_ERR_INVALID_ARGUMENT when the mode is off.
+ * tf_debug_force_temp_tables(1) makes every multi-pass transform build its inter-pass twiddle table as a stream-ordered temporary
+ * (the route of a table above 2^28 words or over the cache budget) and every scaled inter-pass table of a coset evaluation take the
+ * uncached route (that of a fifth coset offset), whatever the caches hold; 0 restores the normal choice.  Results do not depend on it. */
+enum { TF_TEMP_GUARD_WORDS = 20480, TF_TEMP_GUARD_LEDGER_WORDS = 68 };
+int tf_debug_temp_guard(int mode);
+int tf_debug_temp_guard_report(uint64_t *ledger, uint64_t *label_blocks, uint64_t *label_bytes, size_t capacity, size_t *n_labels);
+int tf_debug_temp_guard_reset(void);
+const char *tf_debug_temp_guard_label(size_t id);
+size_t tf_debug_temp_guard_words(void);
+int tf_debug_temp_guard_selftest(int defect, size_t n_words, uint64_t *out_word);
+int tf_debug_force_temp_tables(int on);
+
 #ifdef __cplusplus
 }
 #endif

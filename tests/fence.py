@@ -17,9 +17,19 @@ shift.  After ONE synchronisation four things are checked, in this order:
     kept    a slot the documentation leaves "as it was", and every padding word, holds its poison
 
 The arena is plain torch and works on CPU tensors as well: tests/test_fence_cpu.py feeds it fake operations with each defect and
-checks that each is reported with the right check and offset.  What the harness cannot see: device temporaries the library takes
-from its own pool, and the host-pointer / numpy API, whose device buffers are allocated inside the library.
+checks that each is reported with the right check and offset.
+
+The arena sees the tensor arguments only.  The library's own device memory -- the pool temporaries of every call and the buffers of
+the host-pointer / numpy API -- is fenced by the library itself: tf_debug_temp_guard (include/tf_hip.h) puts G poisoned words on each
+side of every block it takes, poisons the block, and checks the guards when the block is given back.  temp_guarded() below switches
+that mode on around a call and asserts a clean ledger; tests/test_gpu_temp_guard.py runs every fenced call and every host form under
+it.  What remains unseen after both: memory the library keeps for the life of the process (cached twiddle and power tables, the
+Tip5 constants, the arena of a persistent zerofier tree), its page-locked staging blocks, and a stray LOAD from a neighbouring
+allocation that happens to hold the same words under all three poisons.
 """
+import contextlib
+import ctypes
+
 import numpy as np
 
 # Guard words (entries, for the 32-bit tensors) on each side of a payload.  A condition, not a measurement: G must exceed what ONE
@@ -210,3 +220,54 @@ def run(entry, shape, operands, call, device="cuda", shifts=SHIFTS, poisons=POIS
     for shift in shifts:
         for poison in poisons:
             run_once(entry, shape, operands, call, shift, poison, device)
+
+
+# ------------------------------------------------------------------ the library's own device memory (tf_debug_temp_guard)
+TEMP_POISONS = (1, 2, 3)          # the modes of tf_debug_temp_guard: POISONS, in this order
+LEDGER_WORDS = 4 + 4 * 16         # TF_TEMP_GUARD_LEDGER_WORDS
+SIDES = ("front", "back")
+
+
+class TempGuardReport:
+    """tf_debug_temp_guard_report, decoded: blocks checked, blocks with an offending entry, offending 32-bit entries, the records
+    (label, side, payload-relative offset of the first offending entry, offending entries) of the first 16 offending guards, and
+    {label: (blocks, bytes)} requested since the last reset (labels with no request left out)."""
+
+    def __init__(self, lib):
+        ledger = (ctypes.c_uint64 * LEDGER_WORDS)()
+        n = ctypes.c_size_t(0)
+        cap = 1024
+        blocks, nbytes = (ctypes.c_uint64 * cap)(), (ctypes.c_uint64 * cap)()
+        rc = lib.tf_debug_temp_guard_report(ledger, blocks, nbytes, cap, ctypes.byref(n))
+        assert rc == 0 and n.value <= cap, (rc, n.value)
+        text = lambda i: lib.tf_debug_temp_guard_label(i).decode()  # noqa: E731
+        self.blocks_checked, self.blocks_offending, self.entries_offending = int(ledger[0]), int(ledger[1]), int(ledger[2])
+        self.records = [(text(int(ledger[4 + 4 * r])), SIDES[int(ledger[5 + 4 * r])], int(np.uint64(ledger[6 + 4 * r]).astype(np.int64)), int(ledger[7 + 4 * r]))
+                        for r in range(int(ledger[3]))]
+        self.labels = {text(i): (int(blocks[i]), int(nbytes[i])) for i in range(n.value) if blocks[i]}
+
+    def __repr__(self):
+        return (f"checked {self.blocks_checked} blocks, {self.blocks_offending} offending, {self.entries_offending} offending entries, "
+                f"records {self.records}, labels {self.labels}")
+
+
+@contextlib.contextmanager
+def temp_guarded(lib, mode, must_see=(), clean=True):
+    """The body runs with the library's own device memory guarded and poisoned with `mode` (one of TEMP_POISONS): counters and ledger
+    are reset before, the mode is switched off in any case, and after a body that did not raise the report is taken (it waits for
+    the device) and must show no offending entry (clean) and at least one block under every label of `must_see`.  Yields a list that
+    holds the report afterwards."""
+    assert mode in TEMP_POISONS
+    assert lib.tf_debug_temp_guard_reset() == 0
+    assert lib.tf_debug_temp_guard(mode) == 0
+    box = []
+    try:
+        yield box
+        box.append(TempGuardReport(lib))
+    finally:
+        assert lib.tf_debug_temp_guard(0) == 0
+    report = box[0]
+    if clean:
+        assert report.entries_offending == 0 and report.blocks_offending == 0, f"temporary poison {POISONS[mode - 1]}: a guard of the library's own memory was written: {report}"
+    missing = [label for label in must_see if label not in report.labels]
+    assert not missing, f"no block was requested under {missing}: {report}"

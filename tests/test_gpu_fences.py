@@ -9,7 +9,10 @@ expected values come from the references the suite already trusts -- oracle.tfo,
 sponge_ref and the Merkle / MMR models of the existing tests --, never from another call into the library.  The shapes straddle the
 boundaries the kernel headers name, one count below, at and above; nothing exceeds 2^16 points or 2^17 words per tensor.
 tests/test_fence_cpu.py proves on CPU tensors that the harness reports each kind of defect, and fails when device.py grows a public
-callable without a row here.  What no row can see: the library's own pool temporaries and the host-pointer / numpy API."""
+callable without a row here.  No row here can see the library's own pool temporaries or the host-pointer / numpy API: those are
+fenced inside the library (tf_debug_temp_guard), and tests/test_gpu_temp_guard.py runs every row of this table again with that mode
+on.  What remains unseen after both: memory the library keeps for the life of the process (cached tables, Tip5 constants, a
+persistent zerofier-tree arena) and its page-locked staging blocks."""
 import itertools
 
 import numpy as np

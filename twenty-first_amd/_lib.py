@@ -248,6 +248,13 @@ SIGNATURES = {
     "tf_debug_field_op_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tf_debug_ntt_network_dev": (C.c_int, [C.c_int, _vp, _sz, _vp]),
     "tf_debug_ntt_network_config": (None, [C.POINTER(C.c_int)] * 4),
+    "tf_debug_temp_guard": (C.c_int, [C.c_int]),
+    "tf_debug_temp_guard_report": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "tf_debug_temp_guard_reset": (C.c_int, []),
+    "tf_debug_temp_guard_label": (C.c_char_p, [_sz]),
+    "tf_debug_temp_guard_words": (_sz, []),
+    "tf_debug_temp_guard_selftest": (C.c_int, [C.c_int, _sz, C.POINTER(C.c_uint64)]),
+    "tf_debug_force_temp_tables": (C.c_int, [C.c_int]),
 }
 
 

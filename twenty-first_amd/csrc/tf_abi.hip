@@ -84,12 +84,12 @@ int merkle_proofs_host(const uint32_t* heights, size_t n, const uint64_t* loff, 
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp di(s), dd(s), da(s), dr(s), dst(s), dp(s);
-    TRY(di.alloc(nk));
-    TRY(dd.alloc(5 * nk));
-    TRY(da.alloc(5 * na));
-    TRY(dr.alloc(paths ? 0 : 5 * n));
-    TRY(dst.alloc((n + 1) / 2));
-    TRY(dp.alloc(paths ? 5 * path_words : 0));
+    TRY(di.alloc(nk, "merkle proofs host buffers"));
+    TRY(dd.alloc(5 * nk, "merkle proofs host buffers"));
+    TRY(da.alloc(5 * na, "merkle proofs host buffers"));
+    TRY(dr.alloc(paths ? 0 : 5 * n, "merkle proofs host roots"));
+    TRY(dst.alloc_bytes(n * sizeof(int), "merkle proofs host buffers"));
+    TRY(dp.alloc(paths ? 5 * path_words : 0, "merkle proofs host paths"));
     if (nk) {
         TRY(h2d(di.p, idx + loff[0], nk, s));
         TRY(h2d(dd.p, dig + 5 * loff[0], 5 * nk, s));
@@ -282,6 +282,25 @@ int tf_debug_ntt_network_dev(int form, uint64_t* d_x, size_t count, void* stream
 
 void tf_debug_ntt_network_config(int* lazy, int* asm_bfly, int* asm_pow2, int* pow2_wide) { debug_ntt_network_config(lazy, asm_bfly, asm_pow2, pow2_wide); }
 
+// the guard mode for library-owned device memory (tf_temp_guard.hip)
+int tf_debug_temp_guard(int mode) try {
+    return temp_guard_set_mode(mode);
+} TF_ABI_CATCH
+int tf_debug_temp_guard_report(uint64_t* ledger, uint64_t* label_blocks, uint64_t* label_bytes, size_t capacity, size_t* n_labels) try {
+    return temp_guard_report(ledger, label_blocks, label_bytes, capacity, n_labels);
+} TF_ABI_CATCH
+int tf_debug_temp_guard_reset(void) try {
+    return temp_guard_reset();
+} TF_ABI_CATCH
+const char* tf_debug_temp_guard_label(size_t id) { return temp_guard_label(id); }
+size_t tf_debug_temp_guard_words(void) { return TF_TEMP_GUARD_WORDS; }
+int tf_debug_temp_guard_selftest(int defect, size_t n_words, uint64_t* out_word) try {
+    return temp_guard_selftest(defect, n_words, out_word);
+} TF_ABI_CATCH
+int tf_debug_force_temp_tables(int on) try {
+    return force_temp_tables(on);
+} TF_ABI_CATCH
+
 #ifdef TF_AB_BUILD
 // measurement helper (not part of the drop-in boundary): allocate / fetch the MODE-3 stamp buffer
 int tf_debug_stamps(unsigned long long* host_out, size_t words) try {
@@ -377,8 +396,8 @@ int tf_tip5_trace(uint64_t* states, uint64_t* trace, size_t count) try {
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp d(s), t(s);
-    TRY(d.alloc(count * 16));
-    TRY(t.alloc(count * 96));
+    TRY(d.alloc(count * 16, "tip5_trace host buffers"));
+    TRY(t.alloc(count * 96, "tip5_trace host buffers"));
     TRY(h2d(d.p, states, count * 16, s));
     TRY(tip5_trace_dev(d.p, t.p, count, s));
     TRY(d2h(states, d.p, count * 16, s));
@@ -404,8 +423,8 @@ int tf_tip5_hash_varlen_rows(const uint64_t* rows, size_t row_len, size_t n_rows
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp din(s), dout(s);
-    TRY(din.alloc(std::max<size_t>(1, n_rows * row_len)));
-    TRY(dout.alloc(n_rows * 5));
+    TRY(din.alloc(std::max<size_t>(1, n_rows * row_len), "hash_varlen_rows host buffers"));
+    TRY(dout.alloc(n_rows * 5, "hash_varlen_rows host buffers"));
     TRY(h2d(din.p, rows, n_rows * row_len, s));
     TRY(tip5_hash_varlen_rows_dev(din.p, row_len, n_rows, dout.p, s));
     TRY(d2h(out, dout.p, n_rows * 5, s));
@@ -424,7 +443,7 @@ static int prepare_run(size_t in_words, size_t out_words, const std::function<in
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp a(s), b(s);
-    if (a.alloc(in_words) || b.alloc(out_words)) return TF_ERR_OUT_OF_MEMORY;
+    if (a.alloc(in_words, "prepare buffers") || b.alloc(out_words, "prepare buffers")) return TF_ERR_OUT_OF_MEMORY;
     if (in_words) HIPCHK(hipMemsetAsync(a.p, 0, in_words * sizeof(u64), s));
     TRY(body(a.p, b.p, s));
     return sync(s);
@@ -475,15 +494,15 @@ int merkle_subtree_host(const u64* leaves_sub, size_t m, u64* nodes_tree, size_t
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp din(s), dout(s);
-    if (din.alloc(m * 5)) return TF_ERR_TREE_TOO_HIGH;
+    if (din.alloc(m * 5, "merkle subtree host leafs")) return TF_ERR_TREE_TOO_HIGH;
     TRY(h2d(din.p, leaves_sub, m * 5, s));
     if (!nodes_tree) {
-        TRY(dout.alloc(5));
+        TRY(dout.alloc(5, "merkle subtree host root"));
         TRY(merkle_root_dev(din.p, m, dout.p, 1, s));
         TRY(d2h(root_out, dout.p, 5, s));
         return sync(s);
     }
-    if (dout.alloc(m * 10)) return TF_ERR_TREE_TOO_HIGH;
+    if (dout.alloc(m * 10, "merkle subtree host nodes")) return TF_ERR_TREE_TOO_HIGH;
     TRY(merkle_build_dev(din.p, m, dout.p, 1, s));
     for (size_t l = 0; (size_t(1) << l) <= m; ++l) {
         const size_t w = size_t(1) << l;  // nodes of layer l: local heap indices [w, 2 w)
@@ -1079,8 +1098,8 @@ int tf_merkle_authentication_structure_dev(const uint64_t* d_nodes, size_t num_l
     TRY(current_ctx(&ctx));
     hipStream_t s = static_cast<hipStream_t>(stream);
     DevTemp didx(s), dout(s);
-    TRY(didx.alloc(idx.size()));
-    TRY(dout.alloc(idx.size() * 5));
+    TRY(didx.alloc(idx.size(), "authentication structure gather"));
+    TRY(dout.alloc(idx.size() * 5, "authentication structure gather"));
     TRY(h2d(didx.p, reinterpret_cast<const u64*>(idx.data()), idx.size(), s));
     TRY(gather_digests_dev(d_nodes, reinterpret_cast<const unsigned long long*>(didx.p), idx.size(), dout.p, s));
     TRY(d2h(out_digests, dout.p, idx.size() * 5, s));

@@ -25,9 +25,9 @@ struct WorkSpace {
     hipStream_t s;
     std::deque<DevTemp> blocks;
     explicit WorkSpace(hipStream_t st) : s(st) {}
-    int get(u64** p, size_t words) {
+    int get(u64** p, size_t words, const char* what) {
         blocks.emplace_back(s);
-        TRY(blocks.back().alloc(std::max<size_t>(words, 1), "divide"));
+        TRY(blocks.back().alloc(std::max<size_t>(words, 1), what));
         *p = blocks.back().p;
         return TF_OK;
     }
@@ -68,7 +68,7 @@ int fold(const u64* src, size_t len, long long src_bs, u64* dst, size_t N, size_
     for (;;) {
         const size_t M = cur_len > 64 * N ? next_pow2((cur_len + 63) / 64) : N;
         u64* target = dst;
-        if (M != N) TRY(tmp.get(&target, batch * M * L));
+        if (M != N) TRY(tmp.get(&target, batch * M * L, "divide fold step"));
         TRY(launch(tfk::fold_kernel, (long long)(batch * M * L), s, cur, (long long)(cur_len * L), cur_bs, target, (long long)(M * L),
                    (long long)batch));
         if (M == N) return TF_OK;
@@ -129,9 +129,9 @@ int inverse_of_reversed(DeviceCtx* ctx, const u64* b, size_t m, size_t k, u64* H
     for (size_t p = G::PMAX; p < k; p = std::min(2 * p, k)) nmax = next_pow2(2 * p + std::min(2 * p, k) - 1);
     TRY(check_len(nmax));
     u64 *rb = nullptr, *X = nullptr, *Y = nullptr;
-    TRY(tmp.get(&rb, nb * L));
-    TRY(tmp.get(&X, nmax * L));
-    TRY(tmp.get(&Y, nmax * L));
+    TRY(tmp.get(&rb, nb * L, "divide newton work"));
+    TRY(tmp.get(&X, nmax * L, "divide newton work"));
+    TRY(tmp.get(&Y, nmax * L, "divide newton work"));
     TRY(launch(tfk::reverse_kernel<L>, (long long)nb, s, b, (long long)nb, rb));
     for (size_t p = G::PMAX; p < k;) {
         const size_t p2 = std::min(2 * p, k), N = next_pow2(2 * p + p2 - 1);
@@ -161,39 +161,39 @@ int divide_dev_t(const u64* a, size_t na, size_t batch, const u64* b, size_t nb,
     const size_t k = na - m;
     if (m == 0) {  // a constant divisor: q = a lc^-1, no remainder
         u64* w = nullptr;
-        TRY(tmp.get(&w, L));
+        TRY(tmp.get(&w, L, "divide constant divisor"));
         TRY(launch(tfk::head_inverse_kernel<L>, 1, s, b, (const u64*)nullptr, w, status, 17, 0));
         if (q) TRY(launch(tfk::scale_kernel<L>, (long long)(batch * na), s, a, (const u64*)w, q, (long long)(batch * na)));
         return TF_OK;
     }
     // 1. h = rev(b)^-1 mod x^k, once for the batch
     u64* H = nullptr;
-    TRY(tmp.get(&H, k * L));
+    TRY(tmp.get(&H, k * L, "divide quotient work"));
     TRY(inverse_of_reversed<L>(ctx, b, m, k, H, status, s, tmp));
     // 2. q = coefficients k - 1 .. 2k - 2 of a[m ..] * rev_k(h), every dividend against ONE transform of rev_k(h)
     const size_t M = next_pow2(2 * k - 1);
     TRY(check_len(M));
     const long long wm = (long long)(M * L);
     u64 *HR = nullptr, *Hh = nullptr, *C = nullptr;
-    TRY(tmp.get(&HR, k * L));
-    TRY(tmp.get(&Hh, M * L));
-    TRY(tmp.get(&C, batch * M * L));
+    TRY(tmp.get(&HR, k * L, "divide quotient work"));
+    TRY(tmp.get(&Hh, M * L, "divide quotient work"));
+    TRY(tmp.get(&C, batch * M * L, "divide quotient work"));
     TRY(launch(tfk::reverse_kernel<L>, (long long)k, s, (const u64*)H, (long long)k, HR));
     TRY(xform(ctx, HR, wm, (long long)k, Hh, wm, M, 1, L, false, s));
     TRY(xform(ctx, a + m * L, (long long)(na * L), (long long)k, C, wm, M, batch, L, false, s));
     TRY(bcast_mul<L>(C, Hh, (long long)M, (long long)(batch * M), s));
     TRY(xform(ctx, C, wm, -1, C, wm, M, batch, L, true, s));
     u64* Q = q;
-    if (!Q) TRY(tmp.get(&Q, batch * k * L));
+    if (!Q) TRY(tmp.get(&Q, batch * k * L, "divide unwanted quotient"));
     TRY(copy_pad(C + (k - 1) * L, wm, (long long)(k * L), Q, (long long)(k * L), (long long)(k * L), (long long)batch, s));
     if (!r) return TF_OK;
     // 3. r = fold(a) - fold(q) fold(b) modulo x^N - 1, low m coefficients: one cyclic product of order N = next_power_of_two(m)
     const size_t N = next_pow2(m);
     const long long wn = (long long)(N * L);
     u64 *FA = nullptr, *FQ = nullptr, *FB = nullptr;
-    TRY(tmp.get(&FA, batch * N * L));
-    TRY(tmp.get(&FQ, batch * N * L));
-    TRY(tmp.get(&FB, N * L));
+    TRY(tmp.get(&FA, batch * N * L, "divide remainder work"));
+    TRY(tmp.get(&FQ, batch * N * L, "divide remainder work"));
+    TRY(tmp.get(&FB, N * L, "divide remainder work"));
     TRY(fold<L>(a, na, (long long)(na * L), FA, N, batch, s, tmp));
     TRY(fold<L>(Q, k, (long long)(k * L), FQ, N, batch, s, tmp));
     TRY(fold<L>(b, nb, (long long)(nb * L), FB, N, 1, s, tmp));
@@ -241,10 +241,10 @@ int divide_host(const u64* a, size_t na, size_t batch, const u64* b, size_t nb, 
     hipStream_t s = host_stream();
     WorkSpace tmp(s);
     u64 *da = nullptr, *db = nullptr, *dq = nullptr, *dr = nullptr;
-    TRY(tmp.get(&da, wa));
-    TRY(tmp.get(&db, nb * L));
-    if (wq) TRY(tmp.get(&dq, wq));
-    if (wr) TRY(tmp.get(&dr, wr));
+    TRY(tmp.get(&da, wa, "divide host inputs"));
+    TRY(tmp.get(&db, nb * L, "divide host inputs"));
+    if (wq) TRY(tmp.get(&dq, wq, "divide host quotient"));
+    if (wr) TRY(tmp.get(&dr, wr, "divide host remainder"));
     TRY(h2d(da, a, wa, s));
     TRY(h2d(db, b, nb * L, s));
     TRY(divide_dev(da, na, batch, db, nb, dq, dr, s, nullptr, L));
@@ -284,9 +284,9 @@ int fps_dev_t(const u64* f, size_t nf, size_t precision, u64* out, hipStream_t s
     TRY(check_len(F));
     WorkSpace tmp(s);
     u64 *Gh = nullptr, *X = nullptr, *Y = nullptr;
-    TRY(tmp.get(&Gh, F * L));
-    TRY(tmp.get(&X, F * L));
-    TRY(tmp.get(&Y, F * L));
+    TRY(tmp.get(&Gh, F * L, "fps_inverse work"));
+    TRY(tmp.get(&X, F * L, "fps_inverse work"));
+    TRY(tmp.get(&Y, F * L, "fps_inverse work"));
     TRY(xform(ctx, f, (long long)(F * L), (long long)nf, Gh, (long long)(F * L), F, 1, L, false, s));
     TRY(launch(tfk::head_inverse_kernel<L>, 1, s, f, lead, X, status, (int)TF_ERR_INVERSE_OF_ZERO, (int)TF_ERR_INVALID_ARGUMENT));
     size_t D = 1, deg = 0;

@@ -78,8 +78,8 @@ int fold_dev(const u64* in, size_t n, size_t batch, int wc, u64 offset_raw, cons
              hipStream_t s) {
     const int passes = passes_of(levels);
     DevTemp even(s), odd(s);  // what pass 0, 2, ... and pass 1, 3, ... leave; the last pass writes `out`
-    if (passes >= 2 && even.alloc(intermediate_words(n, batch, wa, levels, 0), "fri_fold")) return TF_ERR_OUT_OF_MEMORY;
-    if (passes >= 3 && odd.alloc(intermediate_words(n, batch, wa, levels, 1), "fri_fold")) return TF_ERR_OUT_OF_MEMORY;
+    if (passes >= 2 && even.alloc(intermediate_words(n, batch, wa, levels, 0), "fri_fold second-pass intermediate")) return TF_ERR_OUT_OF_MEMORY;
+    if (passes >= 3 && odd.alloc(intermediate_words(n, batch, wa, levels, 1), "fri_fold third-pass intermediate")) return TF_ERR_OUT_OF_MEMORY;
     const long long alpha_stride = n_sets == 1 ? 0 : (long long)(levels * wa);
     u64 g_inv = gl::mont_inverse(offset_raw);
     const u64* src = in;

@@ -16,6 +16,7 @@
 //   tf_fri.hip    the FRI split-and-fold of codewords on an evaluation domain, one to many levels per call (fri_kernels.h)
 //   tf_table.hip  tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (table_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
+//   tf_temp_guard.hip the guard mode for all of the above's device temporaries (tf_debug_temp_guard): guards, poison, ledger, self-test
 //   tf_temp.h     (header, included by the units above) DevTemp, the one owner of a stream-ordered temporary; the staged upload, the
 //                 per-unit Tip5 constants upload and the host round trip that every unit used to spell out for itself
 #pragma once
@@ -110,10 +111,26 @@ extern std::atomic<int> g_pipe, g_nt, g_min_passes, g_lat_mode, g_pre2_mode, g_s
 // ------------------------------------------------------------------------------------ tf_ntt.hip
 int current_ctx(DeviceCtx** out);
 int device_cus();  // compute units of the calling thread's CURRENT device (cached per device; 256 if the runtime will not say)
-hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream);  // every stream-ordered temporary of the library: taken through DevTemp (tf_temp.h)
-int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx::ScratchBlock* out);
+// every stream-ordered temporary of the library, taken through DevTemp (tf_temp.h) and given back with pool_free_async on the same
+// stream; `what` is the site's label: the error text names it, and the guard mode (tf_debug_temp_guard) counts and reports under it
+hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream, const char* what);
+hipError_t pool_free_async(void* p, hipStream_t stream);
+// (in guard mode the block is a guarded pool block under the label `what`, and the cache is bypassed: ready stays null)
+int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx::ScratchBlock* out, const char* what);
 void scratch_release(DeviceCtx* ctx, DeviceCtx::ScratchBlock blk, hipStream_t stream);
 int release_caches(DeviceCtx* ctx);
+// tf_temp_guard.hip: the guard mode's state (low 8 bits the mode, above them the guarded blocks alive; zero: nothing to do anywhere),
+// the two slow paths behind it, and the switch of tf_debug_force_temp_tables
+extern std::atomic<unsigned long long> g_temp_guard_state;
+extern std::atomic<int> g_force_temp_tables;
+hipError_t temp_guard_malloc(void** p, size_t bytes, hipStream_t stream, const char* what, hipMemPool_t pool, int dev, int mode);
+hipError_t temp_guard_free(void* p, hipStream_t stream);
+int temp_guard_set_mode(int mode);  // the bodies of the tf_debug_temp_guard* entry points (tf_abi.hip)
+int force_temp_tables(int on);
+int temp_guard_reset();
+int temp_guard_report(uint64_t* ledger, uint64_t* label_blocks, uint64_t* label_bytes, size_t capacity, size_t* n_labels);
+const char* temp_guard_label(size_t id);
+int temp_guard_selftest(int defect, size_t n_words, uint64_t* out_word);
 int ensure_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done_mask);
 int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, const u64** out, bool* temp, size_t cosets = 1, int log_order = 0);
 void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t stream);  // after the launches that read a table get_pow_table returned

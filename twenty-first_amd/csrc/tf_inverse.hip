@@ -57,7 +57,7 @@ int batch_inverse_dev(const u64* in, size_t n, u64* out, int L, bool or_zero, vo
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (or_zero || d_status) return launch(in, n, out, L, or_zero, d_status, s);
     DevTemp flag(s);
-    TRY(flag.alloc(1, "batch_inversion"));
+    TRY(flag.alloc(1, "batch_inversion flag"));
     return run_checked(in, n, out, L, flag.as<int>(), s);
 }
 
@@ -70,7 +70,7 @@ int batch_inverse_host(const u64* in, size_t n, u64* out, int L, bool or_zero) {
     hipStream_t s = host_stream();
     const size_t words = n * L;
     DevTemp d(s);  // the elements, then the flag word
-    TRY(d.alloc(words + 1, "batch_inversion"));
+    TRY(d.alloc(words + 1, "batch_inversion host buffer"));
     TRY(h2d(d.p, in, words, s));
     int rc = TF_OK;
     if (or_zero) {

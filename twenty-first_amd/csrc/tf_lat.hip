@@ -269,7 +269,7 @@ int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long l
     TRY(get_lat_table(ctx, a2, inverse, &tw2, inverse ? log_n : 0));
     TRY(get_post_table(ctx, log_n, a1, inverse, stream, &post, &post_own));
     DeviceCtx::ScratchBlock sblk;
-    TRY(scratch_acquire(ctx, batch * (size_t)n * L * sizeof(u64), stream, &sblk));
+    TRY(scratch_acquire(ctx, batch * (size_t)n * L * sizeof(u64), stream, &sblk, "lat2 inter-pass scratch"));
     tfk::NttLat2Args c{};  // column pass: the caller's input -> scratch
     c.in = in;
     c.out = sblk.p;

@@ -330,7 +330,7 @@ int merkle_open_host(const u64* leafs, size_t n, size_t batch, const uint64_t* l
     const size_t out_words = batch * idx.size() * 5;
     if (din.alloc(n * batch * 5, "merkle open leafs")) return TF_ERR_TREE_TOO_HIGH;
     TRY(dout.alloc(out_words, "merkle open output"));
-    TRY(droots.alloc(roots ? batch * 5 : 0, "merkle open output"));
+    TRY(droots.alloc(roots ? batch * 5 : 0, "merkle open roots"));
     TRY(h2d(din.p, leafs, n * batch * 5, s));
     TRY(open_run(din.p, n, batch, idx, dout.p, droots.p, s));
     TRY(d2h(out, dout.p, out_words, s));

@@ -155,8 +155,8 @@ int mmr_sweep(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64* new_
     TRY(up.put(dev, moves.data(), moves.size() * sizeof(unsigned long long), "mmr move list"));
     const auto* dm = up.as<unsigned long long>();
     DevTemp even(s), odd(s);
-    TRY(even.alloc(5 * even_words));
-    TRY(odd.alloc(5 * odd_words));
+    TRY(even.alloc(5 * even_words, "mmr sweep levels"));
+    TRY(odd.alloc(5 * odd_words, "mmr sweep levels"));
     const MmrMoveArrays arrays{{leafs, old_peaks, even.p, odd.p}, {wants.empty() ? proofs : wanted, new_peaks, even.p, odd.p}};
     auto level = [&](int h) { return h & 1 ? odd.p : even.p; };
     for (int h = 0; h <= top; ++h) {
@@ -193,7 +193,7 @@ int mmr_bag_peaks_dev(const uint64_t* leaf_counts, size_t n_acc, const u64* peak
     int dev = 0;
     TRY(ctx_dev(&dev));
     StagedUpload up(s);
-    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), "mmr chains"));
+    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), "mmr bag chains"));
     return launch_chains<tfm::tfk::kMmrBag>(up.as<MmrChain>(), (long long)n_acc, nullptr, peaks, nullptr, out, nullptr, 0, 0,
                                             nullptr, s);
 }
@@ -213,7 +213,7 @@ int mmr_verify_dev(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, c
     int dev = 0;
     TRY(ctx_dev(&dev));
     StagedUpload up(s);
-    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), "mmr chains"));
+    TRY(up.put(dev, ch.data(), ch.size() * sizeof(MmrChain), "mmr verify chains"));
     return launch_chains<tfm::tfk::kMmrVerify>(up.as<MmrChain>(), (long long)n, digests, paths, peaks, nullptr, idx, leaf_count,
                                                (long long)n_peaks, statuses, s);
 }
@@ -318,7 +318,7 @@ int mmr_mutate_dev(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, c
     TRY(up.put(dev, words.data(), words.size() * sizeof(unsigned long long), "mmr mutation plan"));
     const auto* dw = up.as<unsigned long long>();
     DevTemp A(s);
-    TRY(A.alloc(5 * M * (Lmax + 1)));
+    TRY(A.alloc(5 * M * (Lmax + 1), "mmr mutation chains"));
     TRY(launch_moves(leafs, dw + leaf_moves_at, (long long)M, A.p, s));
     for (u64 l = 0; l < Lmax; ++l) {
         const u64* row = A.p + 5 * M * l;
@@ -464,7 +464,7 @@ int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t 
     TRY(ctx_dev(&dev));
     DevTemp table(s);
     if (grows) {
-        TRY(table.alloc(5 * wants.size()));
+        TRY(table.alloc(5 * wants.size(), "mmr update wanted digests"));
         TRY(mmr_sweep(n, old_peaks, leafs, k, new_peaks, nullptr, wants, table.p, s));
     } else if (sweep) TRY(mmr_sweep(n, old_peaks, leafs, k, new_peaks, nullptr, {}, nullptr, s));
     if (!total) return TF_OK;
@@ -484,8 +484,8 @@ int mmr_update_proofs_dev(u64 n, const u64* old_peaks, const u64* leafs, size_t 
 // ------------------------------------------------------------------------------------ host flavours
 // Upload the inputs (waiting for each upload: pageable memory), run the _dev form on the thread's stream, copy back, synchronise.
 namespace {
-int up_words(DevTemp& t, const u64* h, size_t words, hipStream_t s) {
-    TRY(t.alloc(words));
+int up_words(DevTemp& t, const u64* h, size_t words, hipStream_t s, const char* what) {
+    TRY(t.alloc(words, what));
     return h && words ? h2d(t.p, h, words, s) : TF_OK;
 }
 }  // namespace
@@ -501,10 +501,10 @@ int mmr_append_host(u64 n, const u64* old_peaks, const u64* leafs, size_t k, u64
     hipStream_t s = host_stream();
     const size_t np_old = __builtin_popcountll(n), np_new = __builtin_popcountll(n + k);
     DevTemp dold(s), dl(s), dnew(s), dpr(s);
-    TRY(up_words(dold, old_peaks, 5 * np_old, s));
-    TRY(up_words(dl, leafs, 5 * k, s));
-    TRY(dnew.alloc(5 * np_new));
-    TRY(dpr.alloc(proofs ? 5 * n_proof : 0));
+    TRY(up_words(dold, old_peaks, 5 * np_old, s, "mmr_append host buffers"));
+    TRY(up_words(dl, leafs, 5 * k, s, "mmr_append host buffers"));
+    TRY(dnew.alloc(5 * np_new, "mmr_append host buffers"));
+    TRY(dpr.alloc(proofs ? 5 * n_proof : 0, "mmr_append host proofs"));
     u64 dummy = 0;
     TRY(mmr_append_dev(n, np_old ? dold.p : &dummy, k ? dl.p : &dummy, k, np_new ? dnew.p : &dummy, proofs ? (n_proof ? dpr.p : &dummy) : nullptr, s));
     TRY(d2h(new_peaks, dnew.p, 5 * np_new, s));
@@ -537,11 +537,11 @@ int mmr_verify_host(u64 leaf_count, const u64* peaks, size_t n_peaks, size_t n, 
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp dpk(s), di(s), dd(s), dpa(s), dst(s);
-    TRY(up_words(dpk, peaks, 5 * n_peaks, s));
-    TRY(up_words(di, idx, n, s));
-    TRY(up_words(dd, digests, 5 * n, s));
-    TRY(up_words(dpa, na ? paths + 5 * offsets[0] : nullptr, 5 * na, s));
-    TRY(dst.alloc((n + 1) / 2));
+    TRY(up_words(dpk, peaks, 5 * n_peaks, s, "mmr_verify host buffers"));
+    TRY(up_words(di, idx, n, s, "mmr_verify host buffers"));
+    TRY(up_words(dd, digests, 5 * n, s, "mmr_verify host buffers"));
+    TRY(up_words(dpa, na ? paths + 5 * offsets[0] : nullptr, 5 * na, s, "mmr_verify host buffers"));
+    TRY(dst.alloc_bytes(n * sizeof(int), "mmr_verify host buffers"));
     TRY(mmr_verify_dev(leaf_count, dpk.p, n_peaks, n, di.p, dd.p, offsets, dpa.p, dst.as<int>(), offsets[0], s));
     HIPCHK(hipMemcpyAsync(statuses, dst.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
     return sync(s);
@@ -556,11 +556,11 @@ int mmr_mutate_host(u64 leaf_count, u64* peaks, size_t M, const uint64_t* midx, 
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp dpk(s), dl(s), dm(s), dq(s), dmod(s);
-    TRY(up_words(dpk, peaks, 5 * np, s));
-    TRY(up_words(dl, leafs, 5 * M, s));
-    TRY(up_words(dm, nm ? mpaths + 5 * moff[0] : nullptr, 5 * nm, s));
-    TRY(up_words(dq, nq ? ppaths + 5 * poff[0] : nullptr, 5 * nq, s));
-    TRY(dmod.alloc((P + 1) / 2));
+    TRY(up_words(dpk, peaks, 5 * np, s, "mmr_mutate host peaks"));  // (only with peaks)
+    TRY(up_words(dl, leafs, 5 * M, s, "mmr_mutate host buffers"));
+    TRY(up_words(dm, nm ? mpaths + 5 * moff[0] : nullptr, 5 * nm, s, "mmr_mutate host buffers"));
+    TRY(up_words(dq, nq ? ppaths + 5 * poff[0] : nullptr, 5 * nq, s, "mmr_mutate host buffers"));
+    TRY(dmod.alloc_bytes(P * sizeof(int), "mmr_mutate host buffers"));
     u64 dummy = 0;
     TRY(mmr_mutate_dev(leaf_count, peaks ? (np ? dpk.p : &dummy) : nullptr, M, midx, dl.p, moff, dm.p, P, pidx, poff, dq.p,
                        dmod.as<int>(), M ? moff[0] : 0, P ? poff[0] : 0, s));
@@ -580,10 +580,10 @@ int mmr_successor_new_host(u64 n, const u64* old_peaks, const u64* leafs, size_t
     hipStream_t s = host_stream();
     const size_t np_old = new_peaks ? __builtin_popcountll(n) : 0, np_new = new_peaks ? __builtin_popcountll(n + k) : 0;
     DevTemp dold(s), dl(s), dnew(s), dpa(s);
-    TRY(up_words(dold, old_peaks, 5 * np_old, s));
-    TRY(up_words(dl, leafs, 5 * k, s));
-    TRY(dnew.alloc(5 * np_new));
-    TRY(dpa.alloc(5 * len));
+    TRY(up_words(dold, old_peaks, 5 * np_old, s, "mmr_successor_new host peaks"));  // (only with new_peaks, as dnew)
+    TRY(up_words(dl, leafs, 5 * k, s, "mmr_successor_new host buffers"));
+    TRY(dnew.alloc(5 * np_new, "mmr_successor_new host peaks"));
+    TRY(dpa.alloc(5 * len, "mmr_successor_new host buffers"));
     u64 dummy = 0;
     TRY(mmr_successor_new_dev(n, np_old ? dold.p : (new_peaks ? &dummy : nullptr), k ? dl.p : &dummy, k, dpa.p,
                               new_peaks ? (np_new ? dnew.p : &dummy) : nullptr, s));
@@ -607,10 +607,10 @@ int mmr_successor_verify_host(size_t P, const uint64_t* old_counts, const uint64
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp dold(s), dnew(s), dpa(s), dst(s);
-    TRY(up_words(dold, no ? old_peaks + 5 * old_off[0] : nullptr, 5 * no, s));
-    TRY(up_words(dnew, nn ? new_peaks + 5 * new_off[0] : nullptr, 5 * nn, s));
-    TRY(up_words(dpa, na ? paths + 5 * path_off[0] : nullptr, 5 * na, s));
-    TRY(dst.alloc((P + 1) / 2));
+    TRY(up_words(dold, no ? old_peaks + 5 * old_off[0] : nullptr, 5 * no, s, "mmr_successor_verify host buffers"));
+    TRY(up_words(dnew, nn ? new_peaks + 5 * new_off[0] : nullptr, 5 * nn, s, "mmr_successor_verify host buffers"));
+    TRY(up_words(dpa, na ? paths + 5 * path_off[0] : nullptr, 5 * na, s, "mmr_successor_verify host buffers"));
+    TRY(dst.alloc_bytes(P * sizeof(int), "mmr_successor_verify host buffers"));
     u64 dummy = 0;
     TRY(mmr_successor_verify_dev(P, old_counts, new_counts, old_off, no ? dold.p : &dummy, new_off, nn ? dnew.p : &dummy, path_off, na ? dpa.p : &dummy,
                                  dst.as<int>(), old_off[0], new_off[0], path_off[0], s));
@@ -635,11 +635,11 @@ int mmr_update_proofs_host(u64 n, const u64* old_peaks, const u64* leafs, size_t
     hipStream_t s = host_stream();
     const size_t np_old = sweep ? __builtin_popcountll(n) : 0, np_new = new_peaks ? __builtin_popcountll(n + k) : 0;
     DevTemp dold(s), dl(s), dq(s), dout(s), dnew(s);
-    TRY(up_words(dold, old_peaks, 5 * np_old, s));
-    TRY(up_words(dl, sweep ? leafs : nullptr, sweep ? 5 * k : 0, s));
-    TRY(up_words(dq, nq ? own_paths + 5 * own_off[0] : nullptr, 5 * nq, s));
-    TRY(dout.alloc(5 * total));
-    TRY(dnew.alloc(5 * np_new));
+    TRY(up_words(dold, old_peaks, 5 * np_old, s, "mmr_update_proofs host sweep inputs"));  // (only where the call sweeps)
+    TRY(up_words(dl, sweep ? leafs : nullptr, sweep ? 5 * k : 0, s, "mmr_update_proofs host sweep inputs"));
+    TRY(up_words(dq, nq ? own_paths + 5 * own_off[0] : nullptr, 5 * nq, s, "mmr_update_proofs host buffers"));
+    TRY(dout.alloc(5 * total, "mmr_update_proofs host buffers"));
+    TRY(dnew.alloc(5 * np_new, "mmr_update_proofs host new peaks"));  // (only with new_peaks)
     u64 dummy = 0;
     TRY(mmr_update_proofs_dev(n, np_old ? dold.p : &dummy, k && sweep ? dl.p : &dummy, k, P, own_idx, own_off, nq ? dq.p : &dummy, out_off,
                               total ? dout.p : &dummy, total ? (size_t)total : 1, modified, new_peaks ? (np_new ? dnew.p : &dummy) : nullptr,

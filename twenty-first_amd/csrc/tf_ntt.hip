@@ -119,8 +119,8 @@ int current_ctx(DeviceCtx** out) {
     return TF_OK;
 }
 
-// Every stream-ordered temporary of the library: from the context's pool (hipFreeAsync gives it back, whatever the pool).
-hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream) {
+// Every stream-ordered temporary of the library: from the context's pool (pool_free_async gives it back, whatever the pool).
+hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream, const char* what) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -129,7 +129,12 @@ hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream) {
         DeviceCtx* ctx = nullptr;
         if (current_ctx(&ctx) == TF_OK) pool = ctx->pool;
     }
+    if (const int mode = (int)(g_temp_guard_state.load(std::memory_order_relaxed) & 0xFF)) return temp_guard_malloc(p, bytes, stream, what, pool, dev, mode);
     return pool ? hipMallocFromPoolAsync(p, bytes, pool, stream) : hipMallocAsync(p, bytes, stream);
+}
+hipError_t pool_free_async(void* p, hipStream_t stream) {
+    if (g_temp_guard_state.load(std::memory_order_relaxed)) return temp_guard_free(p, stream);  // (the mode is on, or a guarded block is alive)
+    return hipFreeAsync(p, stream);
 }
 
 // Work space between the passes of a multi-pass transform.  Round 1 took it from the stream-ordered pool on every call; a
@@ -138,7 +143,15 @@ hipError_t pool_malloc_async(void** p, size_t bytes, hipStream_t stream) {
 // kept whole in a small per-device cache and handed from call to call with an event fence: release records an event on the
 // releasing stream, the next taker's stream waits for it -- no host synchronisation, any mix of streams and host threads.
 constexpr size_t kScratchCacheBytes = size_t(12) << 30;  // blocks beyond this are freed when they come back
-int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx::ScratchBlock* out) {
+int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx::ScratchBlock* out, const char* what) {
+    if (g_temp_guard_state.load(std::memory_order_relaxed) & 0xFF) {  // guard mode: a guarded pool block, no cache, no event
+        *out = DeviceCtx::ScratchBlock{};
+        out->bytes = bytes;
+        const hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&out->p), bytes, stream, what);
+        if (e == hipSuccess) return TF_OK;
+        out->p = nullptr;
+        return hip_fail(e, (std::string("pool_malloc_async(") + what + ")").c_str(), __FILE__, __LINE__);
+    }
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         int best = -1;
@@ -187,6 +200,10 @@ int scratch_acquire(DeviceCtx* ctx, size_t bytes, hipStream_t stream, DeviceCtx:
 }
 void scratch_release(DeviceCtx* ctx, DeviceCtx::ScratchBlock blk, hipStream_t stream) {
     if (!blk.p) return;
+    if (!blk.ready) {  // taken in guard mode: checked and freed behind the launches on `stream`
+        (void)pool_free_async(blk.p, stream);
+        return;
+    }
     if (hipEventRecord(blk.ready, stream) != hipSuccess) {  // cannot fence it: wait, then free
         (void)hipGetLastError();
         (void)hipStreamSynchronize(stream);
@@ -379,7 +396,7 @@ constexpr int kMaxCachedPostLog = 28;
 // caller's stream (their split tables by square-and-multiply on the device) and nothing waits.
 constexpr int kAlwaysCachedPostLog = 22;
 int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, DevTemp* own) {
-    bool temp = log_m > kMaxCachedPostLog;
+    bool temp = log_m > kMaxCachedPostLog || g_force_temp_tables.load(std::memory_order_relaxed);  // (tf_debug_force_temp_tables)
     const u64 key = make_key(TAG_POST, log_m, a, inverse, 0);
     std::unique_lock<std::mutex> lk(ctx->mu);
     if (!temp) {
@@ -402,19 +419,20 @@ int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t s
         const int h = (log_m + 1) / 2;
         const long long nlo = 1ll << h, nhi = 1ll << (log_m - h);
         u64* d_split = nullptr;
-        hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&d_split), size_t(nlo + nhi) * sizeof(u64), stream);
-        if (e == hipSuccess) e = pool_malloc_async(reinterpret_cast<void**>(&d), size_t(M) * sizeof(u64), stream);
+        // (the split powers and the table: always taken together, one label)
+        hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&d_split), size_t(nlo + nhi) * sizeof(u64), stream, "temporary twiddle table");
+        if (e == hipSuccess) e = pool_malloc_async(reinterpret_cast<void**>(&d), size_t(M) * sizeof(u64), stream, "temporary twiddle table");
         if (e != hipSuccess) {
-            if (d_split) (void)hipFreeAsync(d_split, stream);
-            return hip_fail(e, "pool_malloc_async(twiddle table)", __FILE__, __LINE__);
+            if (d_split) (void)pool_free_async(d_split, stream);
+            return hip_fail(e, "pool_malloc_async(temporary twiddle table)", __FILE__, __LINE__);
         }
         hipLaunchKernelGGL(tfk::build_split_powers_kernel, dim3((unsigned)((nhi + 255) / 256)), dim3(256), 0, stream, d_split, w, h, nhi);
         hipLaunchKernelGGL(tfk::build_split_powers_kernel, dim3((unsigned)((nlo + 255) / 256)), dim3(256), 0, stream, d_split + nhi, w, 0, nlo);
         hipLaunchKernelGGL(tfk::build_post_tw_kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, d, d_split, d_split + nhi, h, R, B);
         e = hipGetLastError();
-        (void)hipFreeAsync(d_split, stream);
+        (void)pool_free_async(d_split, stream);
         if (e != hipSuccess) {
-            (void)hipFreeAsync(d, stream);
+            (void)pool_free_async(d, stream);
             return hip_fail(e, "build_post_tw_kernel (temporary)", __FILE__, __LINE__);
         }
         own->adopt(d);
@@ -535,7 +553,7 @@ int get_tiny_table(DeviceCtx* ctx, int log_n, bool inverse, const u64** out) {
 
 // offset^j, j < n  (the power chain of Polynomial::scale, polynomial.rs:766-771).
 // Up to 16 tables per device are cached for the life of the process; beyond that a table is built into a
-// stream-ordered temporary (*temp = true) that the caller releases with hipFreeAsync after its launches, so no
+// stream-ordered temporary (*temp = true) that the caller releases with release_pow_table after its launches, so no
 // table another thread may still be using is ever freed.
 int build_pow_tables(u64 offset_raw, u64 w, size_t cosets, size_t n, u64* d, hipStream_t s) {
     // table c (c < cosets) = powers of base_c = offset * w^c: out[c * n + j] = base_c^j = HI_c[j >> h] * LO_c[j & (2^h - 1)].
@@ -605,7 +623,7 @@ int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, 
     // host for the depth of the queue (0.8-1.0 ms per call, measured around that one call) when several streams share the pool -- the
     // temporary therefore lives in a block of the scratch cache (hipMalloc'ed blocks handed on with event fences, no stream-ordered free).
     DeviceCtx::ScratchBlock blk;
-    int rc = scratch_acquire(ctx, words * sizeof(u64), stream, &blk);
+    int rc = scratch_acquire(ctx, words * sizeof(u64), stream, &blk, "temporary power table");
     if (rc) return rc;
     d = blk.p;
     {
@@ -650,7 +668,8 @@ void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t 
 constexpr size_t kScaledPostBudget = size_t(512) << 20;
 int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipStream_t stream, const u64** out, DevTemp* own) {
     const auto key = std::make_pair(offset_raw, (u64(log_m) << 8) | u64(a));
-    {
+    const bool forced = g_force_temp_tables.load(std::memory_order_relaxed);  // (tf_debug_force_temp_tables: the uncached route)
+    if (!forced) {
         std::lock_guard<std::mutex> lk(ctx->mu);
         auto it = ctx->scaled_post.find(key);
         if (it != ctx->scaled_post.end()) {
@@ -668,10 +687,11 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
     bool cache;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        cache = ctx->scaled_post.size() < 4 && ctx->cached_scaled_post_bytes + size_t(M) * sizeof(u64) <= kScaledPostBudget;
+        cache = !forced && ctx->scaled_post.size() < 4 && ctx->cached_scaled_post_bytes + size_t(M) * sizeof(u64) <= kScaledPostBudget;
     }
     u64* d = nullptr;
-    hipError_t e = cache ? hipMalloc(&d, size_t(M) * sizeof(u64)) : pool_malloc_async(reinterpret_cast<void**>(&d), size_t(M) * sizeof(u64), stream);
+    hipError_t e = cache ? hipMalloc(&d, size_t(M) * sizeof(u64))
+                         : pool_malloc_async(reinterpret_cast<void**>(&d), size_t(M) * sizeof(u64), stream, "temporary scaled twiddle table");
     if (e == hipSuccess) {
         hipLaunchKernelGGL(tfk::scale_post_tw_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, d, T, S, B, M);
         e = hipGetLastError();
@@ -679,7 +699,7 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
     }
     release_pow_table(ctx, S, s_temp, stream);
     if (e != hipSuccess) {
-        if (d) { if (cache) (void)hipFree(d); else (void)hipFreeAsync(d, stream); }
+        if (d) { if (cache) (void)hipFree(d); else (void)pool_free_async(d, stream); }
         return hip_fail(e, "scale_post_tw_kernel", __FILE__, __LINE__);
     }
     if (cache) {
@@ -1339,7 +1359,7 @@ public:
 
     u64* scratch() const { return blk_.p; }
     int acquire(size_t bytes) {
-        const int rc = scratch_acquire(ctx_, bytes, stream_, &blk_);
+        const int rc = scratch_acquire(ctx_, bytes, stream_, &blk_, "ntt inter-pass scratch");
         if (rc) blk_ = DeviceCtx::ScratchBlock{};  // (nothing of ours to give back)
         return rc;
     }

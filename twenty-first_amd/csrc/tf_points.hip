@@ -120,9 +120,9 @@ int launch_powers(const u64* first, const u64* ratio, int w, u64* out, size_t n,
 // host arrays -> one DevTemp each (waiting for each upload, see h2d)
 struct Uploads {
     explicit Uploads(hipStream_t s) : s_(s) {}
-    int put(const u64* host, size_t words, const u64** dev) {
+    int put(const u64* host, size_t words, const u64** dev, const char* what) {
         bufs_.emplace_back(new DevTemp(s_));
-        TRY(bufs_.back()->alloc(words, "points"));
+        TRY(bufs_.back()->alloc(words, what));
         TRY(h2d(bufs_.back()->p, host, words, s_));
         *dev = bufs_.back()->p;
         return TF_OK;
@@ -148,13 +148,13 @@ int get_colinear_y(const u64* x0, const u64* y0, const u64* x1, const u64* y1, s
     hipStream_t s = host_stream();
     Uploads up(s);
     const u64 *dx0, *dy0, *dx1, *dy1, *dp;
-    TRY(up.put(x0, n * wx, &dx0));
-    TRY(up.put(y0, n * wy, &dy0));
-    TRY(up.put(x1, n * wx, &dx1));
-    TRY(up.put(y1, n * wy, &dy1));
-    TRY(up.put(p2x, n_p2x * wy, &dp));
+    TRY(up.put(x0, n * wx, &dx0, "get_colinear_y host buffers"));
+    TRY(up.put(y0, n * wy, &dy0, "get_colinear_y host buffers"));
+    TRY(up.put(x1, n * wx, &dx1, "get_colinear_y host buffers"));
+    TRY(up.put(y1, n * wy, &dy1, "get_colinear_y host buffers"));
+    TRY(up.put(p2x, n_p2x * wy, &dp, "get_colinear_y host buffers"));
     DevTemp dout(s);  // the quotients, then the flag word
-    TRY(dout.alloc(n * wy + 1, "get_colinear_y"));
+    TRY(dout.alloc(n * wy + 1, "get_colinear_y host buffers"));
     int* flag = reinterpret_cast<int*>(dout.p + n * wy);
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s));
     TRY(launch_colinear_y(dx0, dy0, dx1, dy1, n, dp, each, wx, wy, dout.p, flag, s));
@@ -179,10 +179,10 @@ int are_colinear(const u64* xs, const u64* ys, size_t n_groups, size_t k, int wx
     hipStream_t s = host_stream();
     Uploads up(s);
     const u64 *dxs, *dys;
-    TRY(up.put(xs, n_groups * k * wx, &dxs));
-    TRY(up.put(ys, n_groups * k * wy, &dys));
+    TRY(up.put(xs, n_groups * k * wx, &dxs, "are_colinear host buffers"));
+    TRY(up.put(ys, n_groups * k * wy, &dys, "are_colinear host buffers"));
     DevTemp df(s);
-    TRY(df.alloc_bytes(n_groups * sizeof(int), "are_colinear"));
+    TRY(df.alloc_bytes(n_groups * sizeof(int), "are_colinear host buffers"));
     TRY(launch_are_colinear(dxs, dys, n_groups, k, wx, wy, df.as<int>(), s));
     HIPCHK(hipMemcpyAsync(flags, df.p, n_groups * sizeof(int), hipMemcpyDeviceToHost, s));
     return sync(s);
@@ -199,10 +199,10 @@ int mod_pow(const u64* bases, size_t n_bases, const uint64_t* exps, size_t n_exp
     hipStream_t s = host_stream();
     Uploads up(s);
     const u64 *db, *de;
-    TRY(up.put(bases, n_bases * width, &db));
-    TRY(up.put(exps, n_exps, &de));
+    TRY(up.put(bases, n_bases * width, &db, "mod_pow host buffers"));
+    TRY(up.put(exps, n_exps, &de, "mod_pow host buffers"));
     DevTemp dout(s);
-    TRY(dout.alloc(n * width, "mod_pow"));
+    TRY(dout.alloc(n * width, "mod_pow host buffers"));
     TRY(launch_mod_pow(db, base_each, de, exp_each, width, dout.p, n, s));
     TRY(d2h(out, dout.p, n * width, s));
     return sync(s);
@@ -217,7 +217,7 @@ int powers(const u64* first, const u64* ratio, int width, u64* out, size_t n, bo
     if (!host) return launch_powers(first, ratio, width, out, n, static_cast<hipStream_t>(stream));
     hipStream_t s = host_stream();
     DevTemp dout(s);
-    TRY(dout.alloc(n * width, "powers"));
+    TRY(dout.alloc(n * width, "powers host buffer"));
     TRY(launch_powers(first, ratio, width, dout.p, n, s));
     TRY(d2h(out, dout.p, n * width, s));
     return sync(s);

@@ -550,7 +550,7 @@ int batch_evaluate_tree_t(const u64* coeffs, size_t n_coeffs, size_t poly_stride
     DeviceCtx* ctx = nullptr;
     TRY(current_ctx(&ctx));
     DevTemp arena(s);
-    TRY(arena.alloc(words, "zerofier tree"));
+    TRY(arena.alloc(words, "batch_evaluate zerofier tree"));
     TRY(zerofier_tree_build<L>(ctx, points, (long long)n_points, &T, arena.p, arena.p + (size_t)(kTreeLevelArrays * h) * M * L, s));
     TRY(tree_batch_evaluate<L>(ctx, T, points, n_points, coeffs, n_coeffs, poly_stride, batch, out, s));
     return arena.release();
@@ -652,7 +652,7 @@ int padded_tree_build(const u64* points, size_t n_points, size_t extra_words, Pa
     const size_t work_words = (size_t)kTreeWorkArrays * (size_t)M * L;
     if ((words + work_words) * sizeof(u64) > (size_t(64) << 30)) return TF_ERR_OUT_OF_MEMORY;
     hipError_t e = persistent ? hipMalloc(reinterpret_cast<void**>(&pt->arena), words * sizeof(u64))
-                              : pool_malloc_async(reinterpret_cast<void**>(&pt->arena), words * sizeof(u64), s);
+                              : pool_malloc_async(reinterpret_cast<void**>(&pt->arena), words * sizeof(u64), s, "zerofier tree arena");
     if (e != hipSuccess) {
         pt->arena = nullptr;
         (void)hipGetLastError();
@@ -685,7 +685,7 @@ int padded_tree_build(const u64* points, size_t n_points, size_t extra_words, Pa
 
 int padded_tree_free(PaddedTree* pt, hipStream_t s, int rc) {
     hipError_t e = hipSuccess;
-    if (pt->arena) e = pt->persistent ? hipFree(pt->arena) : hipFreeAsync(pt->arena, s);
+    if (pt->arena) e = pt->persistent ? hipFree(pt->arena) : pool_free_async(pt->arena, s);
     pt->arena = nullptr;
     if (rc) return rc;
     if (e != hipSuccess) return hip_fail(e, "hipFree(zerofier tree)", __FILE__, __LINE__);

