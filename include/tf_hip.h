@@ -317,7 +317,8 @@ int tf_poly_evaluate_bfe_at_xfe_dev(const uint64_t *d_coeffs, size_t n_coeffs, s
  * :2620); the indeterminate inside the subgroup, or n == 0 -> TF_ERR_INVERSE_OF_ZERO (batch_inversion / inverse of zero). */
 int tf_barycentric_evaluate_bfe(const uint64_t *codewords, size_t n, size_t batch, const uint64_t indeterminate[3], uint64_t *out);
 int tf_barycentric_evaluate_xfe(const uint64_t *codewords, size_t n, size_t batch, const uint64_t indeterminate[3], uint64_t *out);
-/* (at most 65 534 x 8 codewords per call: more -> TF_ERR_LEN_TOO_LARGE; split the batch) */
+/* (at most 131 069 codewords per call -- two rows per workgroup, the shared denominator being one more row, in 65 535 row groups:
+ *  more -> TF_ERR_LEN_TOO_LARGE; split the batch) */
 int tf_barycentric_evaluate_bfe_dev(const uint64_t *d_codewords, size_t n, size_t batch, const uint64_t indeterminate[3], uint64_t *d_out, void *stream);
 int tf_barycentric_evaluate_xfe_dev(const uint64_t *d_codewords, size_t n, size_t batch, const uint64_t indeterminate[3], uint64_t *d_out, void *stream);
 /* Polynomial::<BFieldElement>::clean_divide  math/polynomial.rs:2358-2411: the quotient a / b of a division KNOWN to be clean

@@ -1253,6 +1253,14 @@ void tfo_fill_random_from(uint64_t *out, size_t count, uint64_t seed, uint64_t f
 
 void tfo_fill_random(uint64_t *out, size_t count, uint64_t seed) { tfo_fill_random_from(out, count, seed, 0); }
 
+void tfo_combine_rows(const uint64_t *f0, const uint64_t *f1, size_t len, const uint64_t *a, const uint64_t *b, size_t r0, size_t r1,
+                      uint64_t *out) {
+    for (size_t r = r0; r < r1; r++) {
+        u64 *o = out + (r - r0) * len;
+        for (size_t j = 0; j < len; j++) o[j] = bfe_add(bfe_mul(a[r], f0[j]), bfe_mul(b[r], f1[j]));
+    }
+}
+
 void tfo_digest_to_hex(const uint64_t d[5], char out[81]) {
     static const char *hx = "0123456789abcdef";
     for (int i = 0; i < 5; i++) {

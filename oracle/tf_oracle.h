@@ -102,6 +102,11 @@ uint64_t tfo_splitmix64(uint64_t *state);
 void tfo_fill_random(uint64_t *out, size_t count, uint64_t seed);
 /* elements [first_index, first_index + count) of the same counter-based sequence (a rank's shard of a job-wide input) */
 void tfo_fill_random_from(uint64_t *out, size_t count, uint64_t seed, uint64_t first_index);
+/* rows r0 .. r1 - 1 of the rank-2 family of two base rows of `len` words: out[(r - r0) * len + j] = a[r] * f0[j] + b[r] * f1[j], one
+ * BFieldElement product and sum per word (base-field scalars act on every limb of an XFieldElement alike, x_field_element.rs:540-548);
+ * the expected values of the tests that take 2^16 rows through a linear operation (tests/slab_ref.py) */
+void tfo_combine_rows(const uint64_t *f0, const uint64_t *f1, size_t len, const uint64_t *a, const uint64_t *b, size_t r0, size_t r1,
+                      uint64_t *out);
 /* digest -> 80 lowercase hex chars + NUL: canonical value, little-endian bytes (tip5/digest.rs:85-90,:144-153) */
 void tfo_digest_to_hex(const uint64_t d[5], char out[81]);
 

@@ -110,6 +110,7 @@ def lib() -> C.CDLL:
             "tfo_poly_clean_divide_bfe": (i32, [pu, sz, pu, sz, sz, pu]),
             "tfo_fill_random": (None, [pu, sz, u64]),
             "tfo_fill_random_from": (None, [pu, sz, u64, u64]),
+            "tfo_combine_rows": (None, [pu, pu, sz, pu, pu, sz, sz, pu]),
             "tfo_digest_to_hex": (None, [pu, C.c_char_p]),
         }
         for name, (res, args) in sig.items():
@@ -536,6 +537,22 @@ def fill_random(count: int, seed: int, first_index: int = 0) -> np.ndarray:
     out = np.zeros(count, dtype=np.uint64)
     if count:
         lib().tfo_fill_random_from(_p(out), count, seed, first_index)
+    return out
+
+
+def combine_rows(f0, f1, a, b, r0: int = 0, r1=None, out=None) -> np.ndarray:
+    """Rows r0 .. r1 - 1 of the rank-2 family of the base rows f0, f1 (raw words; XFieldElements as their limbs): row r =
+    a[r] * f0 + b[r] * f1 word by word, a and b base-field scalars.  One C loop per call (ctypes lets other threads run meanwhile);
+    `out`: a C-contiguous (r1 - r0) x len(f0) array to fill."""
+    f0, f1, a, b = _arr(f0).reshape(-1), _arr(f1).reshape(-1), _arr(a).reshape(-1), _arr(b).reshape(-1)
+    assert f0.size == f1.size and a.size == b.size
+    r1 = a.size if r1 is None else r1
+    assert 0 <= r0 <= r1 <= a.size
+    if out is None:
+        out = np.empty((r1 - r0, f0.size), dtype=np.uint64)
+    assert out.shape == (r1 - r0, f0.size)
+    if out.size:
+        lib().tfo_combine_rows(_p(f0), _p(f1), f0.size, _p(a), _p(b), r0, r1, _p(out))
     return out
 
 

@@ -1,0 +1,184 @@
+"""Shapes and expected values for the loops that are keyed by the batch (tests/test_gpu_slab_edges.py, tests/test_slab_edges_cpu.py):
+host loops that cut a batch into slabs, kernels that walk rows with `r += gridDim.y`, and the hard batch limits.
+
+1. The constants those loops turn on, mirrored from csrc/ with the text of the site each comes from.  test_slab_edges_cpu.py
+   requires every such text to stand in its file, so a changed constant fails on the CPU instead of silently moving a boundary out
+   of the reach of the GPU shapes.
+
+2. Rank-2 families.  Evaluation is linear in the coefficients, interpolation in the values, quotient and remainder in the dividend
+   (fixed divisor), the barycentric value in the codeword.  With two base rows F0, F1 and per-row base-field scalars a_r, b_r != 0,
+   row r = a_r F0 + b_r F1 differs from every other row and its result is a_r E0 + b_r E1, where E0, E1 are the oracle's plain
+   results for the two base rows alone.  Base-field scalars act on every limb of an XFieldElement alike (x_field_element.rs:540-548),
+   so the combination is the same word-wise product and sum for both widths.  It is one C loop of the oracle's own field
+   operations (oracle.combine_rows: the element-at-a-time oracle.hadamard takes minutes at 10^8 words), cheap at 2^16 rows and
+   independent of the device; test_slab_edges_cpu.py pins it to Python integers, to oracle.hadamard and to tests/pyref."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+P = (1 << 64) - (1 << 32) + 1
+
+# ------------------------------------------------------------------ 1. mirrored constants: name -> value, and where each lives
+GRID_Y = 65535                 # rows of one launch whose grid.y is the batch
+TREE_SLAB_ELEMS = 1 << 25      # elements of walk work per array: units per walk = 2^25 / M
+TREE_MAX_UNITS = 65536         # the walk's arrays are indexed per unit
+TREE_WORK_ARRAYS = 8           # kTreeWorkArrays
+INTERP_SLAB_ROWS = 32768       # rows of one turn of the walk up, at the most ...
+INTERP_SLAB_ELEMS = 1 << 26    # ... and elements: rows per turn = min(rows, 32 768, 2^26 / (M L))
+INTERP_ROW_ARRAYS = 5          # targets, two interpolant levels, the children's transforms (2)
+TREE_LEAF = {1: 256, 3: 128}   # tree_leaf(L): leaves of the one-shot evaluation tree
+INTERP_LEAF = 64               # tree_interp_leaf(L): leaves of every tree that is also walked upwards (the handle's too)
+HORNER_SPLIT = 1024            # coefficients from which Horner takes a workgroup per (point, polynomial)
+BARY_ROWS_PER_BLOCK = 2        # rpb
+BARY_MAX_BATCH = GRID_Y * BARY_ROWS_PER_BLOCK - 1   # the denominator is one more row: 131 069
+DIVIDE_MAX_BATCH = 65535       # kMaxDivideBatch
+CLEAN_DIVIDE_MAX_BATCH = 65535
+
+# (file under twenty-first_amd/csrc, text, occurrences) -- the literal at its site
+SITES = [
+    ("tf_poly.hip", f"for (size_t b0 = 0; b0 < batch; b0 += {GRID_Y}) {{", 2),                       # chunk_combine launches; Horner launches
+    ("tf_poly.hip", f"std::min<size_t>({GRID_Y}, batch - b0)", 2),
+    ("tf_poly.hip", "v > 0 ? (size_t)v : (size_t(1) << 25); }();", 1),                                # tree_batch_evaluate: slab_elems
+    ("tf_poly.hip", "std::max<size_t>(1, std::min<size_t>(units, slab_elems / (size_t)M))", 1),
+    ("tf_poly.hip", "std::max<size_t>(1, std::min<size_t>(units, (size_t(1) << 25) / M))", 2),       # tree_route and the handle: the same slab
+    ("tf_poly.hip", f"if (units > {TREE_MAX_UNITS}) return false;", 1),                               # tree_route
+    ("tf_poly.hip", f"if (units > {TREE_MAX_UNITS} || words * sizeof(u64) > (size_t(64) << 30))", 1),  # the handle's fall-back to Horner
+    ("tf_poly.hip", f"constexpr int kTreeWorkArrays = {TREE_WORK_ARRAYS};", 1),
+    ("tf_poly.hip", 'tmp.alloc((2 * units + (size_t)kTreeWorkArrays * slab) * ML, "zerofier tree walk")', 1),
+    ("tf_poly.hip", "padded + u0 * ML", 1),
+    ("tf_poly.hip", "vals + b0 * chunks * ML", 1),
+    ("tf_poly.hip", "coeffs + b0 * poly_stride", 1),
+    ("tf_poly.hip", f"std::min<size_t>(std::min<size_t>(rows, {INTERP_SLAB_ROWS}), (size_t(1) << 26) / ML)", 1),
+    ("tf_poly.hip", f'tmp.alloc({INTERP_ROW_ARRAYS} * slab * ML, "interpolation rows")', 1),
+    ("tf_poly.hip", "values + r0 * n * L", 2),                                                        # both leaf kernels of the walk up
+    ("tf_poly.hip", "return forced ? forced : (L == 1 ? 8 : 7);", 1),                                 # tree_leaf_log
+    ("tf_poly.hip", "return 1 << std::min(forced ? forced : 6, tree_leaf_log(L));", 1),               # tree_interp_leaf
+    ("tf_poly.hip", f"const bool split = n_coeffs >= {HORNER_SPLIT};", 1),
+    ("tf_poly.hip", "if (H->pt.T.h == 0 || n_coeffs < 2)", 1),                                        # the handle's Horner: one leaf or a constant
+    ("tf_poly.hip", f"const int rpb = rows_env ? rows_env : {BARY_ROWS_PER_BLOCK};", 1),
+    ("tf_poly.hip", "((long long)batch + 1 + rpb - 1) / rpb;", 1),
+    ("tf_poly.hip", f"if (row_groups > {GRID_Y}) return TF_ERR_LEN_TOO_LARGE;", 1),
+    ("tf_poly.hip", f"if (batch > {CLEAN_DIVIDE_MAX_BATCH}) return TF_ERR_LEN_TOO_LARGE;", 1),        # clean_divide_dev
+    ("tf_divide.hip", f"constexpr size_t kMaxDivideBatch = {DIVIDE_MAX_BATCH};", 1),
+    ("tf_divide.hip", "if (batch > kMaxDivideBatch ||", 1),
+    ("tf_algebra.hip", f"unsigned rows_dim(size_t rows) {{ return (unsigned)std::min<size_t>(rows, {GRID_Y}); }}", 1),
+    ("algebra_kernels.h", "for (long long r = blockIdx.y; r < rows; r += gridDim.y) {", 4),           # add / sub, derivative, scale, degree
+]
+
+
+def padded_points(n_points, leaf):
+    """M: the leaf size doubled until it holds the points"""
+    m = leaf
+    while m < n_points:
+        m <<= 1
+    return m
+
+
+def tree_units(n_coeffs, batch, m):
+    """(chunks per polynomial, units, units per walk) of tree_batch_evaluate on a tree of m padded points"""
+    chunks = max(1, -(-n_coeffs // m))
+    units = batch * chunks
+    return chunks, units, max(1, min(units, TREE_SLAB_ELEMS // m))
+
+
+def interp_slab(rows, m, width):
+    """rows per turn of tree_interpolate_rows"""
+    return max(1, min(rows, INTERP_SLAB_ROWS, INTERP_SLAB_ELEMS // (m * width)))
+
+
+def turns(total, step):
+    return -(-total // step)
+
+
+# ------------------------------------------------------------------ 2. rank-2 families
+def scalars(oracle, rows, seed):
+    """per-row base-field scalars a_r, b_r != 0 (raw words) of a fixed seed"""
+    s = oracle.fill_random(2 * rows, seed)
+    s[s == 0] = oracle.bfe_new(1)
+    return s[:rows].copy(), s[rows:].copy()
+
+
+_THREADS = max(1, min(16, os.cpu_count() or 1))
+_BLOCK_WORDS = 1 << 18   # words of one block of rows
+
+
+def _blocks(rows, cols):
+    step = max(1, _BLOCK_WORDS // max(cols, 1))
+    return [(r0, min(rows, r0 + step)) for r0 in range(0, rows, step)]
+
+
+def _run(fn, spans):
+    if len(spans) < 4:
+        return [fn(s) for s in spans]
+    with ThreadPoolExecutor(_THREADS) as pool:   # (the oracle's loop and numpy's comparison run outside the interpreter lock)
+        return list(pool.map(fn, spans))
+
+
+def family(oracle, f0, f1, a, b):
+    """rows x len(f0) words: row r = a_r f0 + b_r f1, word by word (oracle.combine_rows, a block of rows per call)"""
+    f0, f1 = np.ascontiguousarray(f0, dtype=np.uint64).reshape(-1), np.ascontiguousarray(f1, dtype=np.uint64).reshape(-1)
+    assert f0.shape == f1.shape and a.shape == b.shape and a.ndim == 1
+    out = np.empty((a.size, f0.size), dtype=np.uint64)
+    _run(lambda span: oracle.combine_rows(f0, f1, a, b, span[0], span[1], out[span[0]:span[1]]), _blocks(a.size, f0.size))
+    return out
+
+
+def family_mismatch(oracle, got, e0, e1, a, b):
+    """None when got (rows x len(e0) words, any shape) is the family of (e0, e1) word for word; else (row, word in the row, got,
+    expected) of the first difference.  The expected rows are formed block by block and never held as a whole."""
+    e0, e1 = np.ascontiguousarray(e0, dtype=np.uint64).reshape(-1), np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1)
+    got = np.asarray(got, dtype=np.uint64)
+    assert got.size == a.size * e0.size, (got.size, a.size, e0.size)
+    got = got.reshape(a.size, e0.size)
+
+    def one(span):
+        want = oracle.combine_rows(e0, e1, a, b, span[0], span[1])
+        have = got[span[0]:span[1]]
+        if np.array_equal(have, want):
+            return None
+        r, j = np.argwhere(have != want)[0]
+        return int(span[0] + r), int(j), int(have[r, j]), int(want[r, j])
+
+    bad = [x for x in _run(one, _blocks(a.size, e0.size)) if x is not None]
+    return min(bad) if bad else None
+
+
+# ------------------------------------------------------------------ the oracle's plain results for one base row
+def lift(row):
+    """BFieldElements as XFieldElements (v, 0, 0)"""
+    row = np.asarray(row, dtype=np.uint64).reshape(-1)
+    out = np.zeros(3 * row.size, dtype=np.uint64)
+    out[0::3] = row
+    return out
+
+
+def horner(oracle, coeffs, points, width, point_width=None):
+    """the polynomial at every point by the oracle's plain Horner: coefficients of `width`, points of `point_width` (default the
+    same); width 1 at point_width 3 is Polynomial<BFieldElement>::evaluate at XFieldElements (polynomial.rs:309-320)"""
+    point_width = point_width or width
+    points = np.asarray(points, dtype=np.uint64).reshape(-1, point_width)
+    if point_width == 1:
+        return np.concatenate([oracle.poly_eval(coeffs, int(p[0]), width=width) for p in points])
+    c = lift(coeffs) if width == 1 else coeffs
+    return np.concatenate([oracle.poly_eval_xfe_point(c, p) for p in points])
+
+
+def long_divide(oracle, a, b, width):
+    """(quotient of na - nb + 1, remainder of nb - 1 coefficients), zero padded: the oracle's naive_divide over BFieldElement, the
+    same schoolbook steps on the oracle's XFieldElement operations over XFieldElement"""
+    na, nb = a.size // width, b.size // width
+    q, r = np.zeros((na - nb + 1) * width, dtype=np.uint64), np.zeros((nb - 1) * width, dtype=np.uint64)
+    if width == 1:
+        wq, wr = oracle.naive_divide(a, b)
+        q[:wq.size], r[:wr.size] = wq, wr
+        return q, r
+    rem = [np.array(a[3 * i:3 * i + 3], dtype=np.uint64) for i in range(na)]
+    div = [np.array(b[3 * i:3 * i + 3], dtype=np.uint64) for i in range(nb)]
+    inv = oracle.xfe_inverse(div[-1])
+    for k in range(na - nb, -1, -1):
+        f = oracle.xfe_mul(rem[k + nb - 1], inv)
+        q[3 * k:3 * k + 3] = f
+        for j in range(nb):
+            rem[k + j] = oracle.xfe_sub(rem[k + j], oracle.xfe_mul(f, div[j]))
+    return q, np.concatenate(rem[:nb - 1])

@@ -1109,7 +1109,7 @@ int barycentric_dev(const u64* codewords, size_t n, size_t batch, int cw_width, 
         static const int rows_env = [] { const char* e = ab_env("TF_BARY_ROWS"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= tfk::kBaryRows) ? v : 0; }();
         const int rpb = rows_env ? rows_env : 2;  // rows per block (A/B: tools/barycentric_bench.py; 1 / 2 / 4 within 3 % of each other)
         const long long row_groups = ((long long)batch + 1 + rpb - 1) / rpb;  // the denominator is row `batch`
-        if (row_groups > 65535) return TF_ERR_LEN_TOO_LARGE;  // more than 65 534 codewords in one call
+        if (row_groups > 65535) return TF_ERR_LEN_TOO_LARGE;  // more than 65 535 rpb - 1 = 131 069 codewords in one call
         if (cw_width == 1)
             hipLaunchKernelGGL(tfk::barycentric_partial_kernel<1>, dim3((unsigned)n_chunks, (unsigned)row_groups), dim3(256), 0, s, codewords,
                                (const u64*)w, (long long)n, (long long)batch, partial, rpb);
