@@ -893,6 +893,70 @@ size_t tf_fri_fold_workspace(size_t n, size_t batch, int width_c, int width_a, s
 int tf_fri_fold_plan(size_t n, size_t levels, int width_c, int width_a, int *levels_per_pass, int capacity);
 
 /* ---------------------------------------------------------------------------------------------
+ * Prefix scans: the one operation of a prover whose value at row i depends on row i - 1 -- the auxiliary columns of an AIR.  replaces
+ * the sequential loop a caller runs on the host between two device calls:
+ *   running sum        y_i = y_(i-1) + b_i             tf_scan_sum_dev       a log-derivative column, b_i = m_i / d_i
+ *   running product    y_i = y_(i-1) a_i               tf_scan_product_dev   a permutation argument, a_i = alpha - v_i
+ *   running evaluation y_i = a_i y_(i-1) + b_i         tf_scan_affine_dev    a_i = alpha: Horner; also the recurrence behind tf_powers
+ * The recurrence is inclusive and runs along each of `batch` columns of n elements:
+ *     y_(-1) = init,   y_i = a_i y_(i-1) + b_i   (0 <= i < n),   out[i] = y_i
+ * with the field's own product (BFieldElement, or XFieldElement per x_field_element.rs:512-536).  Words are canonical raw Montgomery
+ * words in and out, so every result is the unique representative of its element and equals the sequential loop word for word,
+ * however the kernels regroup the products.
+ *   layout           column c of an operand starts stride_* WORDS after column c - 1, stride >= n * width: the column-major layout of
+ *                    tf_poly_linear_combination and tf_merkle_from_columns.  a, b and out each have a stride of their own; words
+ *                    between n * width and the stride are never read and never written.
+ *   widths           (width_a, width_b) is (1, 1), (3, 3) or (3, 1): the last is an XFieldElement multiplier over a BFieldElement
+ *                    column, word for word (3, 3) on the lifted column.  out and init have width_out = max(width_a, width_b) words per
+ *                    element.  sum and product take one width.
+ *   multipliers      of tf_scan_affine_dev: a_len == n: one element per row, column c at a + c * stride_a.  a_len == 1: one element for
+ *                    the whole column; `a` then holds a_sets elements packed, a_sets = 1 (one challenge for every column) or batch
+ *                    (element c for column c) -- device memory exactly as tf_tip5_sponge_sample_scalars_dev leaves it; stride_a and
+ *                    a_sets are looked at in their own form only.  With n == 1 both forms have a_len == 1 and stride_a decides:
+ *                    stride_a == 0, which no table has, is the packed form (a_sets elements); stride_a >= width_a is a table of one
+ *                    row and `batch` elements are READ at a + c * stride_a -- a caller that holds one broadcast challenge passes
+ *                    stride_a = 0, as it may for every n, or the call reads past its one element.
+ *   init             device pointer to n_init elements, n_init = 0 (NULL allowed: the neutral start, 0 for sum and affine, 1 for
+ *                    product), 1 (one start for every column) or batch.
+ *   forms            only _dev forms: device pointers, enqueued on `stream`, never synchronised, nothing copied back.  Nothing
+ *                    depends on the data, so there is no status word.
+ *   work space       the caller's: d_work, work_bytes.  tf_scan_workspace(mode, n, batch, width_out) returns the bytes a call needs
+ *                    (mode is TF_SCAN_SUM / _PRODUCT / _AFFINE): 0 for a column of at most one tile (one launch), for an empty and
+ *                    for a rejected call; else tiles * batch * (M + width_out) * 8, M = width_out words per tile map (2 width_out for
+ *                    affine).  d_work may be NULL when that is 0; it is 8-byte aligned; a smaller work_bytes is
+ *                    TF_ERR_INVALID_ARGUMENT; nothing behind the returned size is touched.  The library allocates nothing.
+ *   plan             tf_scan_plan writes (at most `capacity` entries; info may be NULL) info[0] elements per tile T, [1] tiles per
+ *                    column, [2] tile maps the spine takes per turn S, [3] launches (0 empty, 1 one tile, 3 otherwise), [4] elements up
+ *                    to which a column is scanned by one wave, [5] M; it returns the launches, or minus the status the call would
+ *                    return for (mode, n, batch, width_out).  Host arithmetic like tf_scan_workspace: no device needed.
+ *   aliasing         out may be exactly b (sum, and affine with width_a == width_b) or exactly a (product): the same pointer, the same
+ *                    stride, the same width.  Any other overlap of out or d_work with an operand, or of out with d_work, is the
+ *                    caller's error.
+ *   empty calls      n == 0 or batch == 0: TF_OK, nothing touched, NULL pointers allowed.
+ *   errors           returned before any HIP call, in this order: TF_ERR_NULL_POINTER (an operand, out, init with n_init != 0, d_work
+ *                    where an otherwise valid call needs work space); TF_ERR_INVALID_ARGUMENT (a width or pair not listed, a_len not
+ *                    in {1, n}, a_sets not in {1, batch} in the packed form, a stride below n * width, n_init not in {0, 1, batch}, a short
+ *                    work space); TF_ERR_LEN_TOO_LARGE (n above 2^30; n * batch * width_out above 2^35 words -- 2^34 for affine,
+ *                    which reads two operands; or, for columns above info[4] elements, batch * tiles above 2^24 - 1, the
+ *                    workgroups of one launch: first met at 2^24 columns of 1025 BFieldElements); then TF_ERR_NO_DEVICE on a
+ *                    machine without a GPU.
+ * Not built: the exclusive scan (it is the inclusive scan of n - 1 elements written one slot further, with init in slot 0), and
+ * row-major tables (tf_table_transpose exists).  Three launches in stream order (tile maps, one spine per column, tiles from their
+ * start values) and no workgroup ever waits for another (csrc/scan_kernels.h). */
+#define TF_SCAN_SUM 0
+#define TF_SCAN_PRODUCT 1
+#define TF_SCAN_AFFINE 2
+int tf_scan_sum_dev(const uint64_t *d_in, size_t n, size_t batch, int width, size_t stride_in, const uint64_t *d_init, size_t n_init,
+                    uint64_t *d_out, size_t stride_out, void *d_work, size_t work_bytes, void *stream);
+int tf_scan_product_dev(const uint64_t *d_in, size_t n, size_t batch, int width, size_t stride_in, const uint64_t *d_init, size_t n_init,
+                        uint64_t *d_out, size_t stride_out, void *d_work, size_t work_bytes, void *stream);
+int tf_scan_affine_dev(const uint64_t *d_a, size_t a_len, size_t a_sets, int width_a, size_t stride_a, const uint64_t *d_b, int width_b,
+                       size_t stride_b, size_t n, size_t batch, const uint64_t *d_init, size_t n_init, uint64_t *d_out, size_t stride_out,
+                       void *d_work, size_t work_bytes, void *stream);
+size_t tf_scan_workspace(int mode, size_t n, size_t batch, int width_out);
+int tf_scan_plan(int mode, size_t n, size_t batch, int width_out, int *info, int capacity);
+
+/* ---------------------------------------------------------------------------------------------
  * Tables: moving a table between the two layouts the library itself uses, and opening its rows.  replaces
  *   Array2 .t() / reversed_axes, a prover's own transposes           table_transpose     dst line i, element o = src line o, element i
  *   table.row(i) / select(Axis(0), indices)                          table_gather_rows   out row q = row indices[q]

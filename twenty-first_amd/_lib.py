@@ -143,6 +143,11 @@ SIGNATURES = {
     "tf_fri_fold_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, C.c_uint64, _vp, _sz, _sz, C.c_int, _vp, _vp]),
     "tf_fri_fold_workspace": (_sz, [_sz, _sz, C.c_int, C.c_int, _sz]),
     "tf_fri_fold_plan": (C.c_int, [_sz, _sz, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "tf_scan_sum_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "tf_scan_product_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "tf_scan_affine_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, C.c_int, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "tf_scan_workspace": (_sz, [C.c_int, _sz, _sz, C.c_int]),
+    "tf_scan_plan": (C.c_int, [C.c_int, _sz, _sz, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "tf_table_transpose": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz]),
     "tf_table_transpose_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz, _vp]),
     "tf_table_gather_rows": (C.c_int, [_vp, C.c_int, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _sz]),

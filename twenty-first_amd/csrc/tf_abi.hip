@@ -999,6 +999,30 @@ size_t tf_fri_fold_workspace(size_t n, size_t batch, int width_c, int width_a, s
 int tf_fri_fold_plan(size_t n, size_t levels, int width_c, int width_a, int* levels_per_pass, int capacity) try {
     return fri_fold_plan(n, levels, width_c, width_a, levels_per_pass, capacity);
 } TF_ABI_CATCH
+// prefix scans along columns: sums, products, the affine recurrence (tf_scan.hip)
+int tf_scan_sum_dev(const uint64_t* in, size_t n, size_t batch, int width, size_t stride_in, const uint64_t* init, size_t n_init, uint64_t* out,
+                    size_t stride_out, void* d_work, size_t work_bytes, void* stream) try {
+    return scan_dev(TF_SCAN_SUM, nullptr, 0, 0, width, 0, in, width, stride_in, n, batch, init, n_init, out, stride_out, d_work, work_bytes, stream);
+} TF_ABI_CATCH
+int tf_scan_product_dev(const uint64_t* in, size_t n, size_t batch, int width, size_t stride_in, const uint64_t* init, size_t n_init, uint64_t* out,
+                        size_t stride_out, void* d_work, size_t work_bytes, void* stream) try {
+    return scan_dev(TF_SCAN_PRODUCT, in, n, 1, width, stride_in, nullptr, width, 0, n, batch, init, n_init, out, stride_out, d_work, work_bytes, stream);
+} TF_ABI_CATCH
+int tf_scan_affine_dev(const uint64_t* a, size_t a_len, size_t a_sets, int width_a, size_t stride_a, const uint64_t* b, int width_b, size_t stride_b,
+                       size_t n, size_t batch, const uint64_t* init, size_t n_init, uint64_t* out, size_t stride_out, void* d_work, size_t work_bytes,
+                       void* stream) try {
+    return scan_dev(TF_SCAN_AFFINE, a, a_len, a_sets, width_a, stride_a, b, width_b, stride_b, n, batch, init, n_init, out, stride_out, d_work, work_bytes,
+                    stream);
+} TF_ABI_CATCH
+size_t tf_scan_workspace(int mode, size_t n, size_t batch, int width_out) try {
+    return scan_workspace(mode, n, batch, width_out);
+} catch (...) {
+    ::tfi::abi_caught("C++ exception in tf_scan_workspace", TF_ERR_INTERNAL);
+    return 0;
+}
+int tf_scan_plan(int mode, size_t n, size_t batch, int width_out, int* info, int capacity) try {
+    return scan_plan(mode, n, batch, width_out, info, capacity);
+} TF_ABI_CATCH
 // tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (tf_table.hip)
 int tf_table_transpose(const uint64_t* src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t* dst, size_t dst_stride,
                        size_t batch) try {

@@ -14,6 +14,7 @@
 //   tf_algebra.hip add / sub / neg, scalar_mul, scale, formal_derivative, degree and weighted sums of columns (algebra_kernels.h)
 //   tf_points.hip get_colinear_y / are_colinear, element-wise mod_pow, geometric sequences and index gathers (points_kernels.h)
 //   tf_fri.hip    the FRI split-and-fold of codewords on an evaluation domain, one to many levels per call (fri_kernels.h)
+//   tf_scan.hip   prefix scans along the columns of a table: running sums, products and the affine recurrence (scan_kernels.h)
 //   tf_table.hip  tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (table_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 //   tf_temp_guard.hip the guard mode for all of the above's device temporaries (tf_debug_temp_guard): guards, poison, ledger, self-test
@@ -355,6 +356,15 @@ int fri_fold(const u64* codewords, size_t n, size_t batch, int wc, u64 offset_ra
              bool host, void* stream);
 size_t fri_fold_workspace(size_t n, size_t batch, int wc, int wa, size_t levels);
 int fri_fold_plan(size_t n, size_t levels, int wc, int wa, int* levels_per_pass, int capacity);
+
+// ------------------------------------------------------------------------------------ tf_scan.hip
+// the scans of include/tf_hip.h ("Prefix scans"): device pointers, only enqueues on `stream`, the work space is the caller's.  mode is
+// TF_SCAN_*: a sum reads `b` alone, a product `a` alone (one multiplier per row); an affine call with a_len == 1 takes a_sets packed
+// multipliers.  The work-space rule and the plan are pure host arithmetic (the plan: launches, or minus a status)
+int scan_dev(int mode, const u64* a, size_t a_len, size_t a_sets, int wa, size_t stride_a, const u64* b, int wb, size_t stride_b, size_t n, size_t batch,
+             const u64* init, size_t n_init, u64* out, size_t stride_out, void* d_work, size_t work_bytes, void* stream);
+size_t scan_workspace(int mode, size_t n, size_t batch, int w);
+int scan_plan(int mode, size_t n, size_t batch, int w, int* info, int capacity);
 
 // ------------------------------------------------------------------------------------ tf_table.hip
 // the table calls of include/tf_hip.h ("Tables"): host = false takes device pointers and only enqueues on `stream`, host = true
