@@ -86,8 +86,8 @@ const char *tf_status_string(int status);
 const char *tf_last_error(void);
 /* Library/ABI version (major * 1000 + minor). */
 int tf_version(void);
-/* First 16 hex digits of the SHA-256 of the sources this library was built from (csrc/Makefile); "-ab" appended for the
- * laboratory build (TF_AB_BUILD).  Stored rocprof records carry it so that a figure is never quoted for another build. */
+/* First 16 hex digits of the SHA-256 of the sources this library was built from (csrc/Makefile).  Stored rocprof records carry
+ * it so that a figure is never quoted for another build. */
 const char *tf_source_hash(void);
 /* Number of visible HIP devices (0 if the runtime is unusable). */
 int tf_device_count(void);
@@ -1024,8 +1024,8 @@ int tf_table_lde_rows_xfe_dev(const uint64_t *d_rows, size_t n, size_t n_cols, s
 size_t tf_table_lde_rows_workspace(size_t n, size_t m, size_t n_cols, int width, size_t cols_per_block);
 
 /* ---------------------------------------------------------------------------------------------
- * Deployment settings (process-wide).  These two are the ONLY environment variables the product library reads (once, at the
- * first call); every other TF_* switch of DESIGN_HISTORY.md exists in the laboratory build alone (TF_AB_BUILD, below).
+ * Deployment settings (process-wide).  These two are the ONLY environment variables the library reads (once, at the first
+ * call); the TF_* switches that DESIGN_HISTORY.md names belonged to variants that lost their measurements and are gone.
  *   TF_NTT_TILE_BYTES : bytes of batch processed between the passes of a multi-pass NTT (scratch size),
  *                       (default 2 GiB: measured on MI355X the pass kernels are VALU-bound and larger
  *                       launches overlap better than Infinity-Cache-sized ones).
@@ -1054,8 +1054,7 @@ void tf_set_ntt_small_launch(int mode);
 /* Transforms of 2^21 and 2^22 points run in TWO global passes (a 2048-point pass = pairs of 1024-point workgroups sharing their
  * input) instead of three; -1 = automatic (default), 0 = never (the three-pass plan, which also serves the shapes the
  * two-pass plan does not: small launches, truncated products), 1 = the 2048-point pairs whenever the shape supports them.
- * (2: laboratory build only -- every FORWARD 2^22-point transform on the 1024 x 4096 plan whose last pass runs as four 1024-point
- * classes per tile, a measured loss, profiles/r04_c4_plan_ab.txt; the product library treats 2 as 1.)
+ * (2 is taken as 1: it once selected a 1024 x 4096 plan, a measured loss, profiles/r04_c4_plan_ab.txt.)
  * 3 = the two-pass plan with its FIRST pass as one workgroup per 2048-row x 8-column tile (every element loaded and scaled once,
  * DESIGN 4.1b, round 6) wherever the two-pass plan applies; the automatic plan takes that kernel for coset evaluations of 2^22 points,
  * where it measured faster (profiles/r06_c4_cols8_ab.txt). */
@@ -1079,22 +1078,6 @@ int tf_ntt_plan(size_t n, int width, int* log2_radix_out);
 /* Measurement helper: the shader clock (MHz) the current device is running at right now (one-wave ~0.5 ms spin; < 0 on failure). */
 double tf_debug_sclk_mhz(void);
 
-#ifdef TF_AB_BUILD
-/* ---------------------------------------------------------------------------------------------
- * Laboratory build only (csrc: make ab -> libtf_hip_ab.so).  The product library neither exports these nor contains the kernels
- * behind them: measured losers and diagnostics that are kept so that every claim of DESIGN_HISTORY.md stays reproducible
- * (tools/switch_matrix.sh runs the GPU suite under each switch against this library).
- *   TF_NTT_NT / tf_set_ntt_nt : bit 0 = non-temporal loads of the caller's input in the first pass, bit 1 = non-temporal stores
- *                               of the result in the last pass of a plain multi-pass transform (generic kernels).
- *   tf_set_ntt_chain          : the R = 1024 column pass as a chain of k tiles per workgroup, the next tile's loads issued inside
- *                               the store phase of the current one (TF_NTT_PERSIST): +11..22 % time, profiles/r03_chain_ab.txt.
- *   tf_debug_stamps           : per-wave phase cycle stamps of the NTT pass kernel (TF_NTT_ABLATE=3, tools/phase_timeline.py).
- *   environment               : TF_NTT_NO_* / TF_NTT_WG_THREADS / TF_NTT_ABLATE / TF_TREE_* / TF_POLY_MUL_NO_FUSE /
- *                               TF_POOL_REUSE_FOLLOW_EVENTS ... (the list is `grep ab_env csrc/`). */
-void tf_set_ntt_nt(int mask);
-void tf_set_ntt_chain(int tiles_per_workgroup);
-int tf_debug_stamps(unsigned long long *host_out, size_t words);
-#endif
 /* Synthetic inputs for benches/tests: d_out[i] = BFieldElement::new(splitmix64(seed ^ (first_index + i)) mod p),
  * raw Montgomery words, generated on the device (the oracle's tfo_fill_random is the same counter-based sequence). */
 int tf_debug_fill_random_dev(uint64_t *d_out, size_t count, uint64_t seed, uint64_t first_index, void *stream);

@@ -39,7 +39,7 @@ CLEAN_DIVIDE_MAX_BATCH = 65535
 SITES = [
     ("tf_poly.hip", f"for (size_t b0 = 0; b0 < batch; b0 += {GRID_Y}) {{", 2),                       # chunk_combine launches; Horner launches
     ("tf_poly.hip", f"std::min<size_t>({GRID_Y}, batch - b0)", 2),
-    ("tf_poly.hip", "v > 0 ? (size_t)v : (size_t(1) << 25); }();", 1),                                # tree_batch_evaluate: slab_elems
+    ("tf_poly.hip", "constexpr size_t slab_elems = size_t(1) << 25;", 1),                               # tree_batch_evaluate: slab_elems
     ("tf_poly.hip", "std::max<size_t>(1, std::min<size_t>(units, slab_elems / (size_t)M))", 1),
     ("tf_poly.hip", "std::max<size_t>(1, std::min<size_t>(units, (size_t(1) << 25) / M))", 2),       # tree_route and the handle: the same slab
     ("tf_poly.hip", f"if (units > {TREE_MAX_UNITS}) return false;", 1),                               # tree_route
@@ -52,11 +52,11 @@ SITES = [
     ("tf_poly.hip", f"std::min<size_t>(std::min<size_t>(rows, {INTERP_SLAB_ROWS}), (size_t(1) << 26) / ML)", 1),
     ("tf_poly.hip", f'tmp.alloc({INTERP_ROW_ARRAYS} * slab * ML, "interpolation rows")', 1),
     ("tf_poly.hip", "values + r0 * n * L", 2),                                                        # both leaf kernels of the walk up
-    ("tf_poly.hip", "return forced ? forced : (L == 1 ? 8 : 7);", 1),                                 # tree_leaf_log
-    ("tf_poly.hip", "return 1 << std::min(forced ? forced : 6, tree_leaf_log(L));", 1),               # tree_interp_leaf
+    ("tf_poly.hip", "inline int tree_leaf_log(int L) { return L == 1 ? 8 : 7; }", 1),                 # tree_leaf_log
+    ("tf_poly.hip", "return 1 << std::min(6, tree_leaf_log(L));", 1),                                 # tree_interp_leaf
     ("tf_poly.hip", f"const bool split = n_coeffs >= {HORNER_SPLIT};", 1),
     ("tf_poly.hip", "if (H->pt.T.h == 0 || n_coeffs < 2)", 1),                                        # the handle's Horner: one leaf or a constant
-    ("tf_poly.hip", f"const int rpb = rows_env ? rows_env : {BARY_ROWS_PER_BLOCK};", 1),
+    ("tf_poly.hip", f"constexpr int rpb = {BARY_ROWS_PER_BLOCK};", 1),
     ("tf_poly.hip", "((long long)batch + 1 + rpb - 1) / rpb;", 1),
     ("tf_poly.hip", f"if (row_groups > {GRID_Y}) return TF_ERR_LEN_TOO_LARGE;", 1),
     ("tf_poly.hip", f"if (batch > {CLEAN_DIVIDE_MAX_BATCH}) return TF_ERR_LEN_TOO_LARGE;", 1),        # clean_divide_dev

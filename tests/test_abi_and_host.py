@@ -11,15 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "tf_hip.h")
 
 
-def declared_functions(ab=False):
-    """Function names the header declares: the product's (outside #ifdef TF_AB_BUILD) or the laboratory build's extras."""
+def declared_functions():
+    """Function names the header declares."""
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    ab_blocks = re.findall(r"#ifdef TF_AB_BUILD(.*?)#endif", text, flags=re.S)
-    if ab:
-        text = "\n".join(ab_blocks)
-    else:
-        text = re.sub(r"#ifdef TF_AB_BUILD.*?#endif", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(tf_[a-z0-9_]+)\s*\(", text)))
 
 
@@ -40,12 +35,10 @@ def test_library_exports_every_declared_symbol(tf):
         assert hasattr(lib, n), f"libtf_hip.so does not export {n}"
         assert n in _lib.SIGNATURES, f"{n} has no ctypes signature"
     assert sorted(_lib.SIGNATURES) == names
-    # the laboratory hooks are declared under #ifdef TF_AB_BUILD and the product library does not export them
-    ab_names = declared_functions(ab=True)
-    assert sorted(_lib.AB_SIGNATURES) == ab_names
-    if not _lib.is_ab_build():
-        for n in ab_names:
-            assert not hasattr(lib, n), f"the product library exports the laboratory hook {n}"
+    # there is one build: the header has no conditional block of measurement hooks, and the library exports none of the retired ones
+    assert "TF_AB_BUILD" not in open(HEADER).read()
+    for n in ("tf_set_ntt_nt", "tf_set_ntt_chain", "tf_debug_stamps"):
+        assert not hasattr(lib, n), f"the library exports the retired measurement hook {n}"
     assert len(lib.tf_source_hash()) >= 16
     assert lib.tf_version() >= 1001
     assert lib.tf_status_string(2) == b"TF_ERR_INCORRECT_NUMBER_OF_LEAFS"
@@ -367,7 +360,7 @@ def test_every_status_returning_entry_point_is_a_function_try_block():
             else:
                 assert opens[:2] == ["try", "{"], f"{name} is not guarded"
         assert text.count(" TF_ABI_CATCH") == len([n for n in re.findall(r"^int (tf_[a-z0-9_]+)\(", text, flags=re.M) if n not in NOT_A_STATUS])
-    declared_ints = set(re.findall(r"^int\s+(tf_[a-z0-9_]+)\s*\(", re.sub(r"#ifdef TF_AB_BUILD.*?#endif", "", open(HEADER).read(), flags=re.S), flags=re.M))
+    declared_ints = set(re.findall(r"^int\s+(tf_[a-z0-9_]+)\s*\(", open(HEADER).read(), flags=re.M))
     assert declared_ints <= seen, sorted(declared_ints - seen)
 
 

@@ -1096,10 +1096,9 @@ def test_concurrent_tree_walks_stress_gives_single_threaded_words():
 @pytest.mark.parametrize("log_n", [7, 8, 9, 10, 11, 12, 13])
 @pytest.mark.parametrize("rows", [1, 3])
 def test_one_launch_per_level_walks_match_the_separate_kernels(tf, oracle, log_n, rows):
-    """tree_down_level_kernel / tree_up_level_kernel (a whole level of the walk in one launch, round 3) against the same walk
-    with TF_TREE_NO_LEVEL-style separate kernels is covered by the switch matrix; here: against the oracle's Horner values at
-    sampled points and the round trip, for every level size the kernels are instantiated for (2d = 64 .. 4096), one and
-    several rows / units per call."""
+    """tree_down_level_kernel / tree_up_level_kernel (a whole level of the walk in one launch, round 3) against the oracle's
+    Horner values at sampled points and the round trip, for every level size the kernels are instantiated for (2d = 64 .. 4096),
+    one and several rows / units per call."""
     import torch
 
     n = 1 << log_n

@@ -490,8 +490,8 @@ def test_two_pass_plan_for_2p21_2p22_matches_oracle(tf, oracle, log_n, width, ba
 
 @pytest.mark.parametrize("width,batch", [(1, 3), (3, 2)])
 def test_radix4_last_pass_plan_for_2p22_matches_oracle(tf, oracle, width, batch):
-    """2^22 points as 1024 x 4096 with the 4096-point last pass run as four 1024-point classes per tile (ntt_kernels.h PRE4: a measured
-    loss, so the laboratory library only -- tf_set_ntt_two_pass(2); the product library treats mode 2 as mode 1): forward NTT and
+    """tf_set_ntt_two_pass(2) once selected 2^22 points as 1024 x 4096 with a radix-4 last pass (a measured loss, retired: the
+    library takes mode 2 as mode 1, the 2048-point pairs): forward NTT and
     coset evaluation with full, zero-padded and ragged coefficient lists against the oracle's radix-2 sweeps (math/ntt.rs:153-228,
     polynomial.rs:1374-1399) and word for word against the 2048 x 2048 plan (mode 1) and the three-pass plan (mode 0); also
     device-resident with several polynomials per call and from an unaligned output pointer."""
@@ -968,35 +968,6 @@ def test_latency_shaped_two_pass_plan_matches_oracle(tf, oracle, log_n, width, b
     assert np.array_equal(got[0], got[1])
     if log_n <= 16:
         assert np.array_equal(got[1], oracle.poly_mul(a, b, width=width))
-
-
-def test_chained_column_pass_gives_the_same_words(tf, oracle):
-    """tf_set_ntt_chain: the R = 1024 column pass as chains of k tiles per workgroup with the next tile's loads issued inside the
-    store phase (an A/B path, slower) -- 128 transforms of 2^20 points (2048 tiles per launch), k = 2, 3, 8, against
-    the one-tile kernel word for word, and the first two transforms against the oracle."""
-    import torch
-
-    if not tf._lib.is_ab_build():
-        pytest.skip("ntt_col1024_chain_kernel is a measured loss: compiled into the laboratory library only (csrc: make ab; TF_HIP_LIBRARY=.../libtf_hip_ab.so)")
-    lib = tf._lib.lib()
-    n, batch = 1 << 20, 128
-    src = torch.empty(n * batch, dtype=torch.int64, device="cuda")
-    tf.device.fill_random(src, 7100)
-    ref = src.clone()
-    tf.device.ntt_(ref, n, batch=batch)
-    torch.cuda.synchronize()
-    want = oracle.ntt(src[: 2 * n].cpu().numpy().view(np.uint64), batch=2, threads=2)
-    assert np.array_equal(ref[: 2 * n].cpu().numpy().view(np.uint64), want)
-    try:
-        for k in (2, 3, 8):
-            lib.tf_set_ntt_chain(k)
-            for inverse in (False, True):
-                x = (ref if inverse else src).clone()
-                tf.device.ntt_(x, n, batch=batch, inverse=inverse)
-                torch.cuda.synchronize()
-                assert torch.equal(x, src if inverse else ref), (k, inverse)
-    finally:
-        lib.tf_set_ntt_chain(0)
 
 
 # ---- one host-resident batch over several GPUs at the C ABI (tf_*_multi, include/tf_hip.h) ------------------------------

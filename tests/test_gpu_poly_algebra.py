@@ -400,23 +400,6 @@ def test_fused_sum_equals_the_chain_of_scalar_mul_and_add(tf, oracle, wp, ww):
     assert torch.equal(fused, acc)
 
 
-@pytest.mark.parametrize("wp,ww", COMBOS)
-def test_laboratory_plain_form_returns_the_same_words(tf, oracle, wp, ww):
-    if not tf._lib.is_ab_build():
-        pytest.skip("the plain-product kernel (TF_LINCOMB_PLAIN) is compiled into the laboratory library only (csrc: make ab; TF_HIP_LIBRARY=.../libtf_hip_ab.so)")
-    shapes = [(n, k) for n in (1, 65, 257, 1000) for k in (1, 3, 17)] + [(65, 300), ((1 << 16) + 7, 24)]
-    for n, k in shapes:
-        cols, stride = _table(oracle, n, wp, k, 5, 0x4100 + n + k)
-        wts = _mix(oracle, k * ww, 0x4200 + n + k)
-        deferred = _lincomb(tf, cols, n, wp, stride, k, wts, ww)
-        os.environ["TF_LINCOMB_PLAIN"] = "1"
-        try:
-            plain = _lincomb(tf, cols, n, wp, stride, k, wts, ww)
-        finally:
-            del os.environ["TF_LINCOMB_PLAIN"]
-        assert np.array_equal(deferred, plain), (n, k)
-
-
 # ------------------------------------------------------------------ 8. the C++ mirror
 def test_cpp_mirror_doc_examples_pass():
     host = os.path.join(ROOT, "twenty-first_amd", "host")

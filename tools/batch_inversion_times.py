@@ -3,17 +3,15 @@
 n = 2^16, 2^20, 2^24 BFieldElements and 2^16, 2^20, 2^23 XFieldElements, inputs from tf_debug_fill_random_dev.
 For every size: `ms` (median of --reps warm calls of the enqueue-only form between HIP events), `blocking_ms` (the plain _dev form,
 which copies its zero flag back), the HBM floor of 16 / 48 bytes per element at the chip's measured copy rate (6.29 TB/s,
-MI355X float4 copy) and a device-to-device copy of the same bytes timed in the same run, and the per-element route of the laboratory
-library (TF_BATCH_INV_PER_ELEMENT, csrc/inverse_kernels.h), run in a child process that loads libtf_hip_ab.so (built with
-`make -C twenty-first_amd/csrc ab` when missing).  Both libraries' outputs are hashed: the words must agree.
+MI355X float4 copy) and a device-to-device copy of the same bytes timed in the same run.  (The comparison with one exponentiation
+per element is recorded in profiles/batch_inversion_bench.json.)
   --trace: a short run (one warm-up and two calls per size, synchronised) for `rocprofv3 --kernel-trace --stats` (a run of its own).
-usage: batch_inversion_times.py [--reps 20] [--out profiles/batch_inversion_bench.json] [--trace] [--child]"""
+usage: batch_inversion_times.py [--reps 20] [--out profiles/batch_inversion_bench.json] [--trace]"""
 import argparse
 import hashlib
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -75,33 +73,20 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--child", action="store_true", help="(internal) measure the loaded library and print JSON")
     args = ap.parse_args()
-    if args.child or args.trace:
+    if args.trace:
         print(json.dumps(measure(args.reps, args.trace)))
         return
     import twenty_first_amd as tf
 
     rec = {"what": "batch inversion, tf_batch_inversion_*_dev_async between HIP events, median of warm calls",
            "source_hash": tf.lib().tf_source_hash().decode(), "copy_rate_bytes_per_s": COPY_RATE, "sizes": measure(args.reps, False)}
-    ab = os.path.join(ROOT, "twenty-first_amd", "libtf_hip_ab.so")
-    if not os.path.exists(ab):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "twenty-first_amd", "csrc"), "ab", "-j16"], stdout=subprocess.DEVNULL)
-    env = dict(os.environ, TF_HIP_LIBRARY=ab, TF_BATCH_INV_PER_ELEMENT="1")
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--reps", str(args.reps)], env=env, capture_output=True,
-                         text=True, timeout=900)
-    if out.returncode != 0:
-        raise SystemExit(f"per-element child failed ({out.returncode}): {out.stderr[-2000:]}")
-    lab = json.loads(out.stdout.strip().splitlines()[-1])
-    for e, b in zip(rec["sizes"], lab):
+    for e in rec["sizes"]:
         bytes_ = 16 * e["n"] * e["width"]
         e["hbm_bytes"] = bytes_
         e["floor_us"] = bytes_ / COPY_RATE * 1e6
         e["x_floor"] = e["ms"] * 1e3 / e["floor_us"]
         e["x_copy"] = e["ms"] / e["copy_ms"]
-        e["per_element_ms"] = b["ms"]
-        e["speedup_vs_per_element"] = b["ms"] / e["ms"]
-        e["same_words_as_per_element"] = b["words_sha256"] == e["words_sha256"]
     text = json.dumps(rec, indent=1)
     if args.out:
         open(args.out, "w").write(text + "\n")

@@ -43,7 +43,7 @@ for f in glob.glob(os.path.join(src, "pmc_mfma/**/*counter_collection.csv"), rec
 # configs[3]: the two PRE2 pass kernels of the 64 x 2^22 XFE coset evaluation (SCALE 1 column pass, LAST1024 pass)
 coset_busy = [e["derived"]["valu_busy_frac_at_4_cycles"] for k, e in summ["kernels"].items()
               if "ntt_pass_kernel" in k and "valu_busy_frac_at_4_cycles" in e.get("derived", {})
-              and (k.startswith("ntt_pass_kernel<false, 1, 0, false, true, false, true") or k.startswith("ntt_pass_kernel<false, 0, 0, true, false, false, true"))]
+              and (k.startswith("ntt_pass_kernel<false, 1, false, true, false, true") or k.startswith("ntt_pass_kernel<false, 0, true, false, false, true"))]
 # (round 6: the first pass of configs[3] is ntt_col2048_kernel<false, 1>, bound by the memory pipe at ~0.68 busy; the last pass stays the PRE2 kernel)
 coset_busy += [e["derived"]["valu_busy_frac_at_4_cycles"] for k, e in summ["kernels"].items()
                if k.startswith("ntt_col2048_kernel<false, 1>") and "valu_busy_frac_at_4_cycles" in e.get("derived", {})]

@@ -13,16 +13,16 @@
 // multiply-adds on this ISA?  On gfx950 a 64-bit addition costs as much as a multiply-add (profiles/r03_instr_rates.txt), so
 // every saved product that needs a post-addition is a wash; the variant that needs none needs a third limb.
 //   D  (round 6) the i8 matrix pipe, v_mfma_i32_16x16x64_i8: ten byte planes, three signed digits of the matrix entries (below); adopted
-//      in tip5_kernels.h (TF_TIP5_I8 = 1), so "permutation, matrix pipe" of this file measures whichever form the header is built with:
-//      -DTF_TIP5_I8=0 gives the f64 yardstick of round 5, the default the product's round
-//   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form [-DTF_TIP5_I8=0] -I twenty-first_amd/csrc -o tools/microbench_mds tools/microbench_mds.hip
+//      in tip5_kernels.h: "permutation, matrix pipe" of this file measures the product's round (the f64 yardstick of round 5:
+//      profiles/r05_microbench_mds_mfma.txt)
+//   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -I twenty-first_amd/csrc -o tools/microbench_mds tools/microbench_mds.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <cstring>
 #include "gl64.h"
-#include "tip5_kernels.h"  // the shipping lane-per-permutation round (tfk::tip5_permutation) and its constant block
+#include "tip5_kernels.h"  // the matrix-pipe round, the constant blocks and the helpers the lane-per-permutation round below shares with it
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1);} } while (0)
 using gl::u32;
 using gl::u64;
@@ -515,6 +515,62 @@ __global__ void __launch_bounds__(256) perm_mx_kernel(u64* states, long long cou
         for (int i = 0; i < 4; ++i) states[((wave * NS + n) * 16 + j) * 16 + 4 * i + q] = s[4 * n + i];
 }
 
+// the lane-per-permutation round: the library's throughput kernel through round 4, kept here as the yardstick
+__device__ __forceinline__ void tip5_round(u64 (&s)[16], int round, const unsigned char* lut) {
+    // S-box layer (mod.rs:184-194)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u32 lo = tfk::lookup4((u32)s[i], lut), hi = tfk::lookup4((u32)(s[i] >> 32), lut);
+        s[i] = ((u64)hi << 32) | lo;  // may be >= p, exactly like the reference
+    }
+#pragma unroll
+    for (int i = 4; i < 16; i += 2) {  // x^7 = x * (x^2 * x^4), two elements per hand-scheduled product pair
+        u64 sq0, sq1, qu0, qu1, t0, t1;
+        gl::mont_mul2(s[i], s[i], s[i + 1], s[i + 1], sq0, sq1);
+        gl::mont_mul2(sq0, sq0, sq1, sq1, qu0, qu1);
+        gl::mont_mul2(sq0, qu0, sq1, qu1, t0, t1);
+        gl::mont_mul2(s[i], t0, s[i + 1], t1, s[i], s[i + 1]);
+    }
+    // MDS on 32-bit halves + round constant
+    u32 lo[16], hi[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        lo[i] = (u32)s[i];
+        hi[i] = (u32)(s[i] >> 32);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        u64 alo = 0, ahi = 0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const u32 m = tfk::mds_entry(16 + r - c);
+            alo += (u64)m * lo[c];
+            ahi += (u64)m * hi[c];
+        }
+        // value + round constant = alo + ahi * 2^32 + rc  (< 2^85)  as three 32-bit carry-chain words (t2 : t1 : t0), then one
+        // fold of t2 * 2^64 == t2 * (2^32 - 1) and one conditional subtraction: the canonical word of the reference's
+        // reduce-then-add (mod.rs:244-252, :178-180), because every step is exact
+        const u64 rc = tfk::g_tip5.rc[round * 16 + r];
+        unsigned c0, c1, c2, c3, c4;
+        const u32 w1 = __builtin_addc((u32)(alo >> 32), (u32)ahi, 0u, &c0);
+        const u32 w2 = __builtin_addc((u32)(ahi >> 32), 0u, c0, &c1);
+        const u32 t0 = __builtin_addc((u32)alo, (u32)rc, 0u, &c2);
+        const u32 t1 = __builtin_addc(w1, (u32)(rc >> 32), c2, &c3);
+        const u32 t2 = __builtin_addc(w2, 0u, c3, &c4);  // < 2^22
+        const u64 l64 = ((u64)t1 << 32) | t0;
+        const u64 t = (u64)t2 * 0xffffffffu + l64;  // true value < 2^64 + 2^54
+        const bool ca = t < l64;
+        const u64 u = t + gl::EPS;  // t - p (mod 2^64)
+        const bool cb = u < t;
+        s[r] = (ca | cb) ? u : t;
+    }
+}
+
+__device__ __forceinline__ void tip5_permutation(u64 (&s)[16], const unsigned char* lut) {
+#pragma unroll 1
+    for (int r = 0; r < 5; ++r) tip5_round(s, r, lut);
+}
+
 __global__ void __launch_bounds__(256) perm_a_kernel(u64* states, long long count, int reps) {
     __shared__ __attribute__((aligned(16))) unsigned char lut[256];
     tfk::stage_lut(lut);
@@ -525,7 +581,7 @@ __global__ void __launch_bounds__(256) perm_a_kernel(u64* states, long long coun
 #pragma unroll
     for (int k = 0; k < 16; ++k) s[k] = p[k];
 #pragma unroll 1
-    for (int rep = 0; rep < reps; ++rep) tfk::tip5_permutation(s, lut);
+    for (int rep = 0; rep < reps; ++rep) tip5_permutation(s, lut);
 #pragma unroll
     for (int k = 0; k < 16; ++k) p[k] = s[k];
 }

@@ -6,19 +6,16 @@
   add                  2^24 BFieldElements
 For every shape: `ms` (median of --reps warm calls of the _dev form between HIP events), the bytes the call has to move, that traffic
 over the time as a fraction of the 6.29 TB/s the project prices against, and a device-to-device copy moving the same bytes in the
-same run.  For the linear combination also the unfused chain (k x scalar_mul + add) in the same run and -- in a child process that
-loads the laboratory library (TF_AB_LIBRARY, default twenty-first_amd/libtf_hip_ab.so, built with `make -C twenty-first_amd/csrc ab`
-when missing) -- the deferred-reduction kernel, the plain-product kernel (TF_LINCOMB_PLAIN) and the plain-product kernel again, all in
-that one run: the difference of the two plain timings is the spread the adoption rule of DESIGN 7.3 uses.  Outputs are hashed: both
-kernels must return the same words.
+same run.  For the linear combination also the unfused chain (k x scalar_mul + add) in the same run; outputs are hashed: both must
+return the same words.  (The comparison of the deferred-reduction kernel with one product and one modular addition per term is
+recorded in profiles/poly_algebra_bench.json.)
   --trace: a short run (one warm-up and two calls per shape, synchronised) for `rocprofv3 --kernel-trace --stats` (a run of its own).
-usage: poly_algebra_times.py [--reps 20] [--out profiles/poly_algebra_bench.json] [--trace] [--child]"""
+usage: poly_algebra_times.py [--reps 20] [--out profiles/poly_algebra_bench.json] [--trace]"""
 import argparse
 import hashlib
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -66,7 +63,7 @@ def _entry(name, ms, bytes_moved, calls, **more):
     return e
 
 
-def measure_lincomb(reps, trace, lab):
+def measure_lincomb(reps, trace):
     import torch
 
     import twenty_first_amd as tf
@@ -84,16 +81,7 @@ def measure_lincomb(reps, trace, lab):
         run = lambda: d.linear_combination(cols, n, k, wts, out, width=wp, width_w=ww)  # noqa: E731
         bytes_moved = 8 * (k * n * wp + k * ww + n * wo)
         e = _entry(name, _time(run, calls), bytes_moved, calls, n=n, k=k, width_p=wp, width_w=ww, words_sha256=_sha(out))
-        if lab and not trace:  # the laboratory library: the plain-product kernel twice, in the same run
-            for key in ("plain_ms", "plain_repeat_ms"):
-                os.environ["TF_LINCOMB_PLAIN"] = "1"
-                try:
-                    e[key] = _time(run, calls)
-                    e["plain_words_sha256"] = _sha(out)
-                finally:
-                    del os.environ["TF_LINCOMB_PLAIN"]
-            e["deferred_again_ms"] = _time(run, calls)
-        if not lab and not trace:
+        if not trace:
             e["copy_ms"] = _copy_ms(bytes_moved, calls)
             wts_host = wts.cpu().numpy().view("uint64")
             acc = torch.empty(n * wo, dtype=torch.int64, device="cuda")
@@ -147,32 +135,15 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--child", action="store_true", help="(internal) the laboratory library's three linear-combination timings, as JSON")
     args = ap.parse_args()
-    if args.child:
-        print(json.dumps(measure_lincomb(args.reps, False, True)))
-        return
     if args.trace:
-        print(json.dumps(measure_lincomb(args.reps, True, False) + measure_elementwise(args.reps, True)))
+        print(json.dumps(measure_lincomb(args.reps, True) + measure_elementwise(args.reps, True)))
         return
     import twenty_first_amd as tf
 
     rec = {"what": "polynomial arithmetic, tf_poly_*_dev between HIP events, median of warm calls",
            "source_hash": tf.lib().tf_source_hash().decode(), "copy_rate_bytes_per_s": COPY_RATE,
-           "linear_combination": measure_lincomb(args.reps, False, False), "elementwise": measure_elementwise(args.reps, False)}
-    ab = os.environ.get("TF_AB_LIBRARY") or os.path.join(ROOT, "twenty-first_amd", "libtf_hip_ab.so")
-    if not os.path.exists(ab):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "twenty-first_amd", "csrc"), "ab", "-j16"], stdout=subprocess.DEVNULL)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--reps", str(args.reps)], env=dict(os.environ, TF_HIP_LIBRARY=ab),
-                         capture_output=True, text=True, timeout=900)
-    if out.returncode != 0:
-        raise SystemExit(f"laboratory child failed ({out.returncode}): {out.stderr[-2000:]}")
-    lab = json.loads(out.stdout.strip().splitlines()[-1])
-    for e, b in zip(rec["linear_combination"], lab):
-        e["laboratory_run"] = {"deferred_ms": b["ms"], "plain_ms": b["plain_ms"], "plain_repeat_ms": b["plain_repeat_ms"],
-                               "deferred_again_ms": b["deferred_again_ms"], "plain_spread_ms": abs(b["plain_ms"] - b["plain_repeat_ms"]),
-                               "deferred_gain_ms": min(b["plain_ms"], b["plain_repeat_ms"]) - max(b["ms"], b["deferred_again_ms"]),
-                               "same_words": b["plain_words_sha256"] == b["words_sha256"] == e["words_sha256"]}
+           "linear_combination": measure_lincomb(args.reps, False), "elementwise": measure_elementwise(args.reps, False)}
     text = json.dumps(rec, indent=1)
     if args.out:
         open(args.out, "w").write(text + "\n")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Walks over a PREPARED zerofier tree (tf_zerofier_tree_*), microseconds per call from HIP events over back-to-back calls:
-evaluation and interpolation of n = 2^log points, BFE and XFE.  usage: tree_latency.py [logs...]   (TF_TREE_LEAF_LOG to A/B the leaf)"""
+evaluation and interpolation of n = 2^log points, BFE and XFE.  usage: tree_latency.py [logs...]"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
@@ -25,4 +25,4 @@ for width in (1, 3):
                 for _ in range(50): fn()
                 e1.record(); torch.cuda.synchronize()
                 res.append(e0.elapsed_time(e1) / 50 * 1e3)
-        print(f"leaf_log {os.environ.get('TF_TREE_LEAF_LOG', 'default')} width {width} 2^{log:2d} points, prepared tree: evaluate {res[0]:8.1f} us   interpolate {res[1]:8.1f} us", flush=True)
+        print(f"width {width} 2^{log:2d} points, prepared tree: evaluate {res[0]:8.1f} us   interpolate {res[1]:8.1f} us", flush=True)

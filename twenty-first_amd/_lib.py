@@ -10,7 +10,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SO_PATH = os.environ.get("TF_HIP_LIBRARY") or os.path.join(_HERE, "libtf_hip.so")  # override: A/B builds only
+SO_PATH = os.environ.get("TF_HIP_LIBRARY") or os.path.join(_HERE, "libtf_hip.so")  # override: another build of the library (csrc: make fri_candidates, tools/fri_fold_times.py)
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tf_hip.h")
 
 _u64p = C.POINTER(C.c_uint64)
@@ -263,15 +263,6 @@ SIGNATURES = {
 }
 
 
-# declared under #ifdef TF_AB_BUILD in the header: present in the laboratory library (csrc: make ab, selected with
-# TF_HIP_LIBRARY=.../libtf_hip_ab.so) only -- the product library neither exports them nor contains the kernels behind them
-AB_SIGNATURES = {
-    "tf_set_ntt_chain": (None, [C.c_int]),
-    "tf_debug_stamps": (C.c_int, [_vp, _sz]),
-    "tf_set_ntt_nt": (None, [C.c_int]),
-}
-
-
 def build(force: bool = False) -> str:
     """Compile libtf_hip.so for gfx950 with hipcc (works without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -318,22 +309,12 @@ def lib() -> C.CDLL:
             )
         _load_hip_runtime()
         L = C.CDLL(SO_PATH)
-        older = os.environ.get("TF_HIP_ALLOW_OLDER_LIBRARY") == "1"  # tools/ab.sh only: time an earlier build through this harness
+        older = os.environ.get("TF_HIP_ALLOW_OLDER_LIBRARY") == "1"  # time an earlier build through this harness (tools/tip5_sponge_bench.py)
         for name, (res, args) in SIGNATURES.items():
             if older and not hasattr(L, name):
                 continue
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in AB_SIGNATURES.items():
-            if hasattr(L, name):
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
         _lib = L
     return _lib
-
-
-def is_ab_build() -> bool:
-    """True when the loaded library is the laboratory build (every A/B switch and measured-loser kernel compiled in)."""
-    return lib().tf_source_hash().decode().endswith("-ab")

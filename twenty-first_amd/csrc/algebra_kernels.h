@@ -254,9 +254,7 @@ __device__ __forceinline__ u64 acc_reduce(const AccCols& a) {
 // independent under a BFieldElement weight).  WP = 3 is XFieldElement x XFieldElement: the five coefficients of the unreduced
 // degree-4 product are accumulated (sums of products only) and x^3 = x - 1 is applied once at the end, as
 // x_field_element.rs:512-536 does per product:  r0 = d0 - d3,  r1 = d1 + d3 - d4,  r2 = d2 + d4.
-// PLAIN (laboratory build): one Montgomery product and one modular addition per term instead, the form the deferred reduction
-// was measured against.
-template <int WP, int WW, bool PLAIN>
+template <int WP, int WW>
 __global__ void __launch_bounds__(kAlgThreads) poly_lincomb_kernel(const u64* __restrict__ polys, long long n, long long stride, int k,
                                                                   const u64* __restrict__ w, u64* __restrict__ out) {
     static_assert(WP == 1 || WW == 3, "XFieldElement columns under BFieldElement weights run as words (WP = 1)");
@@ -265,25 +263,7 @@ __global__ void __launch_bounds__(kAlgThreads) poly_lincomb_kernel(const u64* __
     for (long long i = (long long)blockIdx.x * kAlgThreads + threadIdx.x; i < n; i += step) {
         const u64* col = polys + i * WP;
         u64 r[WO];
-        if constexpr (PLAIN) {
-#pragma unroll
-            for (int m = 0; m < WO; ++m) r[m] = 0;
-#pragma unroll 4
-            for (int j = 0; j < k; ++j) {
-                const u64* c = col + (long long)j * stride;
-                if constexpr (WP == 1) {
-                    const u64 x = c[0];
-#pragma unroll
-                    for (int m = 0; m < WO; ++m) r[m] = gl::add(r[m], gl::mont_mul(x, w[(long long)j * WW + m]));
-                } else {
-                    const u64 x[3] = {c[0], c[1], c[2]}, f[3] = {w[3ll * j], w[3ll * j + 1], w[3ll * j + 2]};
-                    u64 y[3];
-                    inv_mul<3>(x, f, y);
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) r[m] = gl::add(r[m], y[m]);
-                }
-            }
-        } else if constexpr (WP == 1) {
+        if constexpr (WP == 1) {
             AccCols acc[WO];
 #pragma unroll
             for (int m = 0; m < WO; ++m) acc_zero(acc[m]);

@@ -152,27 +152,4 @@ __global__ void __launch_bounds__(256) batch_inverse_kernel(const u64* in, long 
     }
 }
 
-#ifdef TF_AB_BUILD
-// Laboratory baseline (TF_BATCH_INV_PER_ELEMENT): the per-element route of the library's other inversions (poly_kernels.h:
-// fe_inverse_kernel), one exponentiation per element, with the same zero handling as batch_inverse_kernel.
-template <int L, bool OR_ZERO>
-__global__ void __launch_bounds__(256) per_element_inverse_kernel(const u64* in, long long n, u64* out, int* status, int code) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        u64 a[L], r[L];
-#pragma unroll
-        for (int k = 0; k < L; ++k) a[k] = in[i * L + k];
-        if (inv_is_zero<L>(a)) {
-            if (!OR_ZERO) atomicCAS(status, 0, code);
-#pragma unroll
-            for (int k = 0; k < L; ++k) r[k] = 0;
-        } else {
-            inv_single<L>(a, r);
-        }
-#pragma unroll
-        for (int k = 0; k < L; ++k) out[i * L + k] = r[k];
-    }
-}
-#endif
-
 }  // namespace tfk

@@ -82,10 +82,6 @@ struct NttPassArgs {
                                              // segments start on cache lines even when the output stride is not a multiple of 16 words
                                              // (truncated products); tile 0 wraps around to the last s columns
     u32 nc_magic;                            // t / nc == umulhi(t, nc_magic) for every t < blockDim (checked by the planner)
-    int nt;                                  // bit 0: non-temporal loads of the input, bit 1: non-temporal stores of the output (plain
-                                             // transforms only): streams that are touched once stay out of the Infinity Cache, which is
-                                             // then left to the scratch tile between the passes (TF_NTT_NT, planner)
-    unsigned long long* dbg;                 // MODE 3 only: per-wave cycle stamps (6 per wave)
     // PRE2 instantiations only (a 2048-point pass as two 1024-point passes, see the kernel):
     long long pre2_in_off;                   // words from a row to its partner row 1024 rows further
     long long pre2_out_off;                  // words added to `out` by the odd half (the strides above already step two rows)
@@ -93,9 +89,6 @@ struct NttPassArgs {
     long long pre2_js_off;                   // ... to the output element index (SCALE 2)
     const u64* pre2_cp;                      // SCALE 1: -> offset^(index distance of partner rows), multiplies the partner coefficient
     int pre2_map;                            // 0: not a PRE2 launch; 1: half = bit 3 of the block id (a pair shares an XCD); 2: bit 0
-                                             // (PRE4: the residue class q = bits 3-4 / bits 0-1)
-    const u64* post_tw_u;                    // ntt_col2048_kernel: the UNSCALED inter-pass table (rows 64 q are read from it; post_tw may carry offset^b)
-    const u64* pre4_stw;                     // PRE4 only: [2][32] Montgomery words w_128^(+-q i), q = 1, 3 (the per-slot part of w_4096^(q c))
 };
 
 // ---- buffer addressing for the R = 1024 instantiations --------------------------------------------------------------------
@@ -112,20 +105,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p) {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc_n(const void* p, u32 nbytes) {  // loads beyond nbytes return zero
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)nbytes, 0x00020000);
 }
-#ifndef TF_LOAD_AUX
-#define TF_LOAD_AUX 2  // cache-policy bits of the data stream's buffer loads / stores: 2 = nt (streamed once; 0 for an A/B build).  Measured on 256 x 2^20: 1.919 -> 1.845 ms with both (loads alone 1.889, stores alone 1.890, profiles/r02f)
-#endif
-#ifndef TF_STORE_AUX
-#define TF_STORE_AUX 2
-#endif
-// per-role overrides for A/B builds: the scratch tile between the passes (stores of a column pass, loads of the last pass)
-#ifndef TF_AUX_COL_STORE
-#define TF_AUX_COL_STORE TF_STORE_AUX
-#endif
-#ifndef TF_AUX_LAST_LOAD
-#define TF_AUX_LAST_LOAD TF_LOAD_AUX
-#endif
-template <int AUX = TF_LOAD_AUX>
+// cache-policy bits of the data stream's buffer loads / stores: 2 = nt (streamed once).  Measured on 256 x 2^20: 1.919 -> 1.845 ms with
+// both (loads alone 1.889, stores alone 1.890, profiles/r02f)
+constexpr int kLoadAux = 2, kStoreAux = 2;
+template <int AUX = kLoadAux>
 __device__ __forceinline__ u64 buf_load(__amdgpu_buffer_rsrc_t r, u32 voff, u32 soff) {
     const tf_v2u v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AUX);
     return ((u64)v[1] << 32) | v[0];
@@ -134,7 +117,7 @@ __device__ __forceinline__ u64 buf_load_tab(__amdgpu_buffer_rsrc_t r, u32 voff, 
     const tf_v2u v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
     return ((u64)v[1] << 32) | v[0];
 }
-template <int AUX = TF_STORE_AUX>
+template <int AUX = kStoreAux>
 __device__ __forceinline__ void buf_store(__amdgpu_buffer_rsrc_t r, u32 voff, u32 soff, u64 x) {
     tf_v2u v;
     v[0] = (u32)x;
@@ -150,7 +133,7 @@ __device__ __forceinline__ void buf_store(__amdgpu_buffer_rsrc_t r, u32 voff, u3
 //         sbase + 32 q s_rs_bytes + soff for slot q.
 template <bool INV, int Q0, bool TRUNC = false, bool SCALED = false>
 __device__ __forceinline__ void tail_p5(u64 (&x)[32], bool act, char* obase, u32 toff, long long out_rs_bytes, int qlim = 32,
-                                        const char* sbase = nullptr, u32 soff = 0, long long s_rs_bytes = 0, bool nt = false) {
+                                        const char* sbase = nullptr, u32 soff = 0, long long s_rs_bytes = 0) {
     DitRange<INV, 5, Q0, Q0 + 4, false>::run(x);  // canonical: these words are stored
     if (act) {
         const __amdgpu_buffer_rsrc_t ro = buf_rsrc(obase);  // LAST1024 only: the planner checked that the offsets fit (see buf_load)
@@ -164,7 +147,6 @@ __device__ __forceinline__ void tail_p5(u64 (&x)[32], bool act, char* obase, u32
 #pragma unroll
             for (int i = 0; i < 4; ++i) gl::mont_mul2(x[Q0 + i], w[i], x[Q0 + i + 16], w[4 + i], x[Q0 + i], x[Q0 + i + 16]);
         }
-        (void)nt;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (!TRUNC || Q0 + i < qlim) buf_store(ro, toff, (u32)((long long)(32 * (Q0 + i)) * out_rs_bytes), x[Q0 + i]);
@@ -186,8 +168,6 @@ __device__ __forceinline__ u32 div_by_L(u32 v, int L) {  // v / L for L in {1, 3
 //            n_coeffs as zero (polynomial.rs:760-773, :1394-1395).
 // SCALE = 2: last pass of fast_coset_interpolate -- multiply output coefficient j by offset^-j on store
 //            (polynomial.rs:1907-1918: intt, then scale by the inverse offset).
-// MODE: 0 = product kernel.  1 / 2 are measurement-only ablations (TF_NTT_ABLATE, never the default):
-//   1 = no global loads/stores (synthetic operands), 2 = no arithmetic (loads, LDS exchange, stores only).
 // PRE2 (R = 1024 instantiations only): the pass is a 2048-point DFT per column.  One radix-2 decimation-in-frequency stage is
 //   fused into the load,  y_r = x_r + x_{r+1024},  z_r = (x_r - x_{r+1024}) w_2048^r,  and the 1024-point DFT of y gives the even
 //   outputs, that of z the odd ones: every tile is run by TWO workgroups (half 0: y, half 1: z) that read the same 32 Ki input
@@ -210,7 +190,7 @@ __device__ __forceinline__ void pre2_combine8(u64 (&x)[32], const u64 (&w)[8], b
     constexpr int Q = Q0 + I;
     if (odd) {
         x[Q] = Pre2Slot<INV, Q>::neg ? gl::sub(w[I], x[Q]) : gl::sub(x[Q], w[I]);
-    } else if constexpr ((Q & 1) || !TF_LAZY) {  // (an all-canonical A/B build, TF_LAZY = 0, keeps every sum canonical)
+    } else if constexpr ((Q & 1) || !TF_LAZY) {  // (an all-canonical build, TF_LAZY = 0, keeps every sum canonical)
         x[Q] = gl::add(x[Q], w[I]);
     } else {
         const u64 s = x[Q] + w[I];
@@ -225,73 +205,10 @@ __device__ __forceinline__ void pre2_shift(u64 (&x)[32]) {
     if constexpr (Q + 1 < END) pre2_shift<INV, Q + 1, END>(x);
 }
 
-// PRE4 (LAST1024, forward, no scaling): the pass is a 4096-point DFT per row, run as FOUR 1024-point workgroups per tile that share
-//   their input.  One radix-4 decimation-in-frequency stage is fused into the load: with x_m = x[c + 1024 m],
-//     class q:  z_q[c] = w_4096^(q c) * sum_m x_m w_4^(q m)   and the 1024-point DFT of z_q gives the outputs k = 4 k' + q
-//     q = 0: (x_0 + x_2) + (x_1 + x_3)          q = 2: ((x_0 + x_2) - (x_1 + x_3)) w_64^i
-//     q = 1: ((x_0 - x_2) + w_4 (x_1 - x_3)) w_128^i        q = 3: ((x_0 - x_2) - w_4 (x_1 - x_3)) w_128^(3 i)
-//   where c = g + 32 i: w_4 and w_64^i are powers of two (shifts); w_128^(q i) is one Montgomery product per element for the odd
-//   classes, its 32 words uniform per register slot (A.pre4_stw, scalar loads); w_4096^(q g) rides on the inner twiddle (inner_tw
-//   holds the four tables, [4][32][32]).  This is the last pass of the 2^22-point plan 1024 x 4096 that fast_coset_evaluate takes:
-//   its FIRST pass (where every coefficient is scaled by offset^j) is then an ordinary 1024-point column pass -- the 2048 x 2048
-//   plan scales every coefficient twice there, once per half of a PRE2 pair.
-#ifdef TF_AB_BUILD  // measured loss (7.9 vs 7.6 ms on BASELINE configs[3], profiles/r04_c4_plan_ab.txt): laboratory build only
-// slots Q0 .. Q0+3 from their four quarter-row words; cls = q (uniform).  Every step adds or subtracts a CANONICAL word (a loaded
-// word or a power-of-two product) to an accumulator that may be any representative (gl::add_lazy4 / sub_lazy4: four instructions, four
-// slots round-robin, no wait states); what leaves is canonical: a power-of-two product, a Montgomery product (stw), or -- class 0 --
-// the odd slots' sums made canonical (the second operands of the lazy network's first level, ntt_network.h), the even slots' left lazy.
-template <bool INV, int Q0, int I = 0>
-__device__ __forceinline__ void pre4_shift4(u64 (&x)[32], const u64 (&d)[4]) {  // x[Q] = d * w_64^i up to the sign the caller folded in
-    x[Q0 + I] = gl::Pow2Mul<Pre2Slot<INV, Q0 + I>::E>::apply(d[I]);
-    if constexpr (I + 1 < 4) pre4_shift4<INV, Q0, I + 1>(x, d);
-}
-template <bool INV, int Q0>
-__device__ __forceinline__ void pre4_combine4(u64 (&x)[32], const u64 (&v0)[4], const u64 (&v1)[4], const u64 (&v2)[4], const u64 (&v3)[4], u32 cls,
-                                              const u64* stw) {
-    u64 t[4], u[4];
-    if (cls == 0) {  // ((x_0 + x_2) + x_1) + x_3
-        gl::add_lazy4(v0, v2, t);
-        gl::add_lazy4(t, v1, u);
-        gl::add_lazy4(u, v3, t);
-        x[Q0] = t[0], x[Q0 + 1] = gl::add(t[1], 0), x[Q0 + 2] = t[2], x[Q0 + 3] = gl::add(t[3], 0);
-    } else if (cls == 2) {  // ((x_0 + x_2) - x_1 - x_3) w_64^i; a slot whose power-of-two product comes back negated takes x_1 + x_3 - x_0 - x_2
-        const u64 p0[4] = {Pre2Slot<INV, Q0>::neg ? v1[0] : v0[0], Pre2Slot<INV, Q0 + 1>::neg ? v1[1] : v0[1], Pre2Slot<INV, Q0 + 2>::neg ? v1[2] : v0[2],
-                           Pre2Slot<INV, Q0 + 3>::neg ? v1[3] : v0[3]};
-        const u64 p1[4] = {Pre2Slot<INV, Q0>::neg ? v3[0] : v2[0], Pre2Slot<INV, Q0 + 1>::neg ? v3[1] : v2[1], Pre2Slot<INV, Q0 + 2>::neg ? v3[2] : v2[2],
-                           Pre2Slot<INV, Q0 + 3>::neg ? v3[3] : v2[3]};
-        const u64 m0[4] = {Pre2Slot<INV, Q0>::neg ? v0[0] : v1[0], Pre2Slot<INV, Q0 + 1>::neg ? v0[1] : v1[1], Pre2Slot<INV, Q0 + 2>::neg ? v0[2] : v1[2],
-                           Pre2Slot<INV, Q0 + 3>::neg ? v0[3] : v1[3]};
-        const u64 m1[4] = {Pre2Slot<INV, Q0>::neg ? v2[0] : v3[0], Pre2Slot<INV, Q0 + 1>::neg ? v2[1] : v3[1], Pre2Slot<INV, Q0 + 2>::neg ? v2[2] : v3[2],
-                           Pre2Slot<INV, Q0 + 3>::neg ? v2[3] : v3[3]};
-        gl::add_lazy4(p0, p1, t);
-        gl::sub_lazy4(t, m0, u);
-        gl::sub_lazy4(u, m1, t);
-        pre4_shift4<INV, Q0>(x, t);
-    } else {  // ((x_0 - x_2) +- w_4 (x_1 - x_3)) w_128^(q i)
-        constexpr int E4 = TwExp<INV, 2, 1>::value;  // w_4^(+-1)
-        gl::sub_lazy4(v0, v2, t);
-        gl::sub_lazy4(v1, v3, u);
-        const u64 w[4] = {gl::Pow2Mul<E4>::apply(u[0]), gl::Pow2Mul<E4>::apply(u[1]), gl::Pow2Mul<E4>::apply(u[2]), gl::Pow2Mul<E4>::apply(u[3])};
-        if ((cls == 1) != gl::Pow2Mul<E4>::negate) gl::add_lazy4(t, w, u);
-        else gl::sub_lazy4(t, w, u);
-        const u64 b4[4] = {stw[brev5(Q0)], stw[brev5(Q0 + 1)], stw[brev5(Q0 + 2)], stw[brev5(Q0 + 3)]};
-        gl::mont_mul4(u, b4, t);
-        x[Q0] = t[0], x[Q0 + 1] = t[1], x[Q0 + 2] = t[2], x[Q0 + 3] = t[3];
-    }
-}
-#endif  // TF_AB_BUILD
-
-template <bool INV, int SCALE, int MODE = 0, bool LAST1024 = false, bool R1024 = false, bool COL = false, bool PRE2 = false, bool PRE4 = false>
-#ifndef TF_PRIO_LOAD
-#define TF_PRIO_LOAD 3
-#endif
-#ifndef TF_PRIO_STEP2
-#define TF_PRIO_STEP2 0
-#endif
-#ifndef TF_NTT_WAVES
-#define TF_NTT_WAVES 4
-#endif
-__global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPassArgs A) {
+constexpr int kPrioLoad = 3, kPrioStep2 = 0;  // s_setprio of a pass kernel's load phase and of its step 2
+constexpr int kNttWaves = 4;                  // waves per SIMD the 512-thread pass kernels are compiled for (two workgroups per CU)
+template <bool INV, int SCALE, bool LAST1024 = false, bool R1024 = false, bool COL = false, bool PRE2 = false>
+__global__ void __launch_bounds__(512, kNttWaves) ntt_pass_kernel(const NttPassArgs A) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     const int t = threadIdx.x;
     // LAST1024: R = 1024, no output multiplier (last pass of a forward/inverse NTT).  R1024: R = 1024 with the generic
@@ -304,24 +221,16 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
     // COL: any column pass (inter-pass table present) of a plan whose offsets fit the buffer window -- the R1024 treatment
     // (lazy networks, buffer addressing) with a run-time P2; R1024 is its constant-P2 special case.
     constexpr bool COLP = R1024 || COL;
-    constexpr bool LAZY1 = (LAST1024 || COLP) && MODE != 2;
-    constexpr bool LAZY2 = COLP && MODE == 0;
+    constexpr bool LAZY1 = LAST1024 || COLP;
+    constexpr bool LAZY2 = COLP;
     const int L = A.L;
 
-    static_assert(!PRE2 || ((LAST1024 || R1024) && MODE == 0 && SCALE != 3), "PRE2 is a variant of the R = 1024 kernels");
-    static_assert(!PRE4 || (LAST1024 && !PRE2 && !INV && MODE == 0 && SCALE == 0), "PRE4 is a variant of the plain forward R = 1024 last pass");
-#ifndef TF_AB_BUILD
-    static_assert(!PRE4, "the radix-4 last pass is a measured loss: laboratory build only");
-#endif
-    // PRE2: two workgroups per tile; `half` selects the even (y) or odd (z) outputs.  PRE4: four, `half` is the residue class q
+    static_assert(!PRE2 || ((LAST1024 || R1024) && SCALE != 3), "PRE2 is a variant of the R = 1024 kernels");
+    // PRE2: two workgroups per tile; `half` selects the even (y) or odd (z) outputs
     u32 bid = blockIdx.x, half = 0;
     if constexpr (PRE2) {
         if (A.pre2_map == 1) half = (bid >> 3) & 1u, bid = (bid & 7u) | ((bid >> 4) << 3);
         else half = bid & 1u, bid >>= 1;
-    }
-    if constexpr (PRE4) {
-        if (A.pre2_map == 1) half = (bid >> 3) & 3u, bid = (bid & 7u) | ((bid >> 5) << 3);
-        else half = bid & 3u, bid >>= 2;
     }
     u32 i0, i1, i2;
     if (A.xcd_order) {
@@ -338,13 +247,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
         const u32 ngrp = A.d2 / (8u * G);
         const u32 grp = A.xcd_colfast ? slot % ngrp : slot / (G * A.d01);
         const u32 within = A.xcd_colfast ? slot / ngrp : slot % (G * A.d01);
-#ifndef TF_XCD_SKEW
-#define TF_XCD_SKEW 0  // experiment (tools/build_variant.sh): XCD x takes column tile (x + SKEW * grp) mod 8 of column group grp
-#endif
-#ifndef TF_NAT_SKEW
-#define TF_NAT_SKEW 0  // experiment: the natural order with the column tile rotated by SKEW * (outer index) within its group of 8
-#endif
-        i2 = ((grp << 3) | (TF_XCD_SKEW ? ((xcd + grp * TF_XCD_SKEW) & 7u) : xcd)) * G + within % G;
+        i2 = ((grp << 3) | xcd) * G + within % G;
         const u32 rest = within / G;
         i1 = rest % A.d1;
         i0 = rest / A.d1;
@@ -354,7 +257,6 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
         const u32 rest = tile / A.d2;
         i1 = rest % A.d1;
         i0 = rest / A.d1;
-        if (TF_NAT_SKEW && (A.d2 & 7u) == 0) i2 = (i2 & ~7u) | ((i2 + (i2 >> 3) * TF_NAT_SKEW + rest * TF_NAT_SKEW) & 7u);
     }
     const u64* in = A.in + (long long)i0 * A.ib0 + (long long)i1 * A.ib1 + (long long)i2 * A.ib2;
     u64* out = A.out + (long long)i0 * A.ob0 + (long long)i1 * A.ob1 + (long long)i2 * A.ob2;
@@ -380,7 +282,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
         in = A.in + (long long)i0 * A.ib0 + (long long)i1 * A.ib1 + (long long)ch0 * A.in_cs_hi;
         out = A.out + (long long)i0 * A.ob0 + (long long)i1 * A.ob1 + (long long)ch0 * A.out_cs_hi;
     }
-    if constexpr (PRE2 || PRE4) out += (long long)half * A.pre2_out_off;
+    if constexpr (PRE2) out += (long long)half * A.pre2_out_off;
 
     // LAST1024 always runs 512 threads in 16 column slots
     // gfast (single-pass transforms, whose "columns" are whole rows of contiguous elements): lanes along the row, g = t % P2
@@ -404,10 +306,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
     // values and reads its 32 new ones in the same round: g_in = bits {0,1,2,4,5}, c_in = bits {6,7,8} + 8 * bit 3.
     int g_in = LAST1024 ? ((t & 7) | ((t >> 1) & 0x18)) : g;
     int c_in = LAST1024 ? (((t >> 6) & 7) | (t & 8)) : c;
-#ifndef TF_XFE_ROLES
-#define TF_XFE_ROLES 1
-#endif
-    if constexpr (LAST1024 && TF_XFE_ROLES) {
+    if constexpr (LAST1024) {
         // XFieldElement rows: consecutive elements of one limb are 24 bytes apart, so the assignment above makes a wave-load
         // touch 768 bytes for 256 it uses (measured: 1.53 x the bytes of the pass fetched on the L2's memory side).  Here the
         // 256 (column, g) pairs of an exchange round are dealt to the round's 256 threads in ADDRESS order instead -- within a
@@ -446,55 +345,21 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
     // work.  VALU arbitration favours the OLDER workgroup on a CU, so a young workgroup whose loads needed
     // address arithmetic would not get them issued until the old one finished computing; together with the
     // s_setprio brackets this is what lets one workgroup's memory phase overlap the other's arithmetic.
-    unsigned long long stamp[6];
-    if constexpr (MODE == 3) stamp[0] = __builtin_readcyclecounter();
     u64 x[32];
 #pragma unroll
     for (int q = 0; q < 32; ++q) x[q] = 0;
-    constexpr bool LDS_TW = TF_LDS_TW && MODE == 0;
+    constexpr bool LDS_TW = TF_LDS_TW != 0;
     u64* const ltw = lds + (LAST1024 ? kL1024ExchangeWords : 32 * s1_);  // the staged inner table [P2][32], behind the exchange buffer
     if constexpr (LDS_TW) {
         if ((LAST1024 || R1024) || A.inner_tw) {  // uniform
-            const u64* itw = A.inner_tw + ((PRE2 || PRE4) ? (int)half * 1024 : 0);
+            const u64* itw = A.inner_tw + (PRE2 ? (int)half * 1024 : 0);
             for (int i = t; i < 32 * P2; i += blockDim.x) ltw[(i >> 5) * kLdsTwStride + (i & 31)] = itw[i];
             __syncthreads();
         }
     }
     // ------------------------------------------------------------------ load + step 1 (radix 32 over i, rows g + P2*i)
-    __builtin_amdgcn_s_setprio(TF_PRIO_LOAD);
-    if constexpr (MODE == 1) {
-#pragma unroll
-        for (int q = 0; q < 32; ++q) x[q] = (u64)(t * 32 + q) * 0x9e3779b97f4a7c15ULL >> 1;
-#ifdef TF_AB_BUILD
-    } else if (PRE4 && act_in) {
-        // the tile's 64 Ki input elements, four slots at a time: the words c, c + 1024, c + 2048, c + 3072 of the row (c = g + 32 i),
-        // combined into class `half`'s z[c]; default cache policy -- the three partner workgroups read the same lines out of the L2
-        const u32 toff = (u32)(((long long)ch_in * A.in_cs_hi + cl_in + (long long)g_in * A.in_rs) * 8);
-        const __amdgpu_buffer_rsrc_t ri = buf_rsrc(in);
-        const u32 poff = (u32)(A.pre2_in_off * 8);
-        const auto slot_off = [&](int q) { return (u32)((long long)(brev5(q) << p2) * A.in_rs * 8); };
-        const auto ld = [&](u32 so) { return buf_load<0>(ri, toff, so); };
-        const u64* stw = A.pre4_stw + (half >> 1) * 32;  // uniform: scalar loads
-        const auto group = [&](auto q0c) {
-            constexpr int Q0 = decltype(q0c)::value;
-            u64 v0[4], v1[4], v2[4], v3[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u32 so = slot_off(Q0 + i);
-                v0[i] = ld(so), v1[i] = ld(so + poff), v2[i] = ld(so + 2 * poff), v3[i] = ld(so + 3 * poff);
-            }
-            pre4_combine4<INV, Q0>(x, v0, v1, v2, v3, half, stw);
-        };
-        group(std::integral_constant<int, 0>{});
-        group(std::integral_constant<int, 4>{});
-        group(std::integral_constant<int, 8>{});
-        group(std::integral_constant<int, 12>{});
-        group(std::integral_constant<int, 16>{});
-        group(std::integral_constant<int, 20>{});
-        group(std::integral_constant<int, 24>{});
-        group(std::integral_constant<int, 28>{});
-#endif  // TF_AB_BUILD
-    } else if (PRE2 && act_in) {
+    __builtin_amdgcn_s_setprio(kPrioLoad);
+    if (PRE2 && act_in) {
         // the tile's 32 Ki input elements: rows r = g + 32 i in x[], their partner rows r + 1024 eight at a time, combined at once
         const u32 toff = (u32)(((long long)ch_in * A.in_cs_hi + cl_in + (long long)g_in * A.in_rs) * 8);
         u32 nrec = 0xffffffffu;
@@ -513,14 +378,9 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
         // (the range check of a raw buffer covers the per-lane offset only, not the scalar one: with zero padding the whole
         //  offset goes through the VGPR -- one v_add_u32 per load)
         constexpr bool CHK = SCALE == 1;
-#ifndef TF_PRE2_LOAD_AUX
-#define TF_PRE2_LOAD_AUX 0  // default cache policy: the partner workgroup's read of the same lines should find them in the L2
-#endif
-        constexpr int AUX = TF_PRE2_LOAD_AUX;
-#ifndef TF_PRE2_BURST16
-#define TF_PRE2_BURST16 2  // 2: 48 loads (slots 0-15, their partners, slots 16-31), then the last 16 partners in flight under the first
-                           //    half's scaling / shifts / levels 1-4; 1: two bursts of 32 loads; 0: 32 loads, then the partners eight at a time (A/B)
-#endif
+        constexpr int AUX = 0;  // default cache policy: the partner workgroup's read of the same lines should find them in the L2
+        // The plain instantiations overlap: 48 loads (slots 0-15, their partners, slots 16-31), then the last 16 partners in flight under
+        // the first half's shifts / levels 1-4.  The scaling one takes two bursts of 32 loads:
         const auto slot_off = [&](int q) { return (u32)((long long)(brev5(q) << p2) * A.in_rs * 8); };
         const auto ld = [&](u32 so) { return CHK ? buf_load<AUX>(ri, toff + so, 0) : buf_load<AUX>(ri, toff, so); };
         const auto scale8 = [&](u64 (&w)[8]) {  // coefficient j + d is scaled by offset^(j + d) = offset^j * c: the common factor follows below
@@ -538,26 +398,8 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
         };
         // (the overlapped order costs the coset-scaling instantiation 22 spilled VGPRs and 9 % -- profiles/r03_two_pass_ab.txt -- so
         //  that one keeps the two plain bursts)
-        if constexpr (TF_PRE2_BURST16 == 2 && SCALE != 1) {
-            const auto scale_half = [&](int h0) {  // coefficient j times offset^j for slots h0 .. h0+15 (as the SCALE 1 block below does for 32)
-                if constexpr (SCALE == 1) {
-                    if (A.pre_scale) {
-                        const u64* ps = A.pre_scale + (long long)i1 * A.ps_i1;
-#pragma unroll
-                        for (int q0 = 0; q0 < 16; q0 += 8) {
-                            u64 w[8];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) {
-                                const long long ur = (long long)(brev5(h0 + q0 + i) << p2);
-                                const long long j = (ur + g) * A.ps_rs + (A.ps_col ? bcol : 0);
-                                w[i] = ps[j < A.n_coeffs ? j : 0];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 8; i += 4) mul4_inplace(x, h0 + q0 + i, w[i], w[i + 1], w[i + 2], w[i + 3]);
-                        }
-                    }
-                }
-            };
+        constexpr bool OVERLAP = SCALE != 1;
+        if constexpr (OVERLAP) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) x[q] = ld(slot_off(q));
             u64 wa[8], wb[8];
@@ -577,7 +419,6 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             for (int i = 0; i < 8; ++i) wb[i] = ld(slot_off(24 + i) + poff);
             __builtin_amdgcn_sched_barrier(0);
             // the first half goes all the way through levels 1-4 while the last 16 partners are in flight
-            scale_half(0);
             if (half) pre2_shift<INV, 1, 16>(x);
             dit_half<INV, 0, LAZY1>(x);
             __builtin_amdgcn_sched_barrier(0);
@@ -585,9 +426,8 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             scale8(wb);
             pre2_combine8<INV, 16>(x, wa, half != 0);
             pre2_combine8<INV, 24>(x, wb, half != 0);
-            scale_half(16);
             if (half) pre2_shift<INV, 16, 32>(x);
-        } else if constexpr (TF_PRE2_BURST16 != 0) {
+        } else {
 #pragma unroll
         for (int h0 = 0; h0 < 32; h0 += 16) {
 #pragma unroll
@@ -607,20 +447,6 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
                 pre2_combine8<INV, 24>(x, wb, half != 0);
             }
         }
-        } else {
-#pragma unroll
-        for (int q = 0; q < 32; ++q) x[q] = ld(slot_off(q));
-#pragma unroll
-        for (int q0 = 0; q0 < 32; q0 += 8) {
-            u64 w[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) w[i] = ld(slot_off(q0 + i) + poff);
-            scale8(w);
-            if (q0 == 0) pre2_combine8<INV, 0>(x, w, half != 0);
-            else if (q0 == 8) pre2_combine8<INV, 8>(x, w, half != 0);
-            else if (q0 == 16) pre2_combine8<INV, 16>(x, w, half != 0);
-            else pre2_combine8<INV, 24>(x, w, half != 0);
-        }
         }
     } else if (act_in) {
         const u32 toff = (u32)(((long long)ch_in * A.in_cs_hi + cl_in + (long long)g_in * A.in_rs) * 8);
@@ -628,7 +454,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
         if constexpr ((LAST1024 || COLP) && SCALE != 1) {
             const __amdgpu_buffer_rsrc_t ri = buf_rsrc(in);
 #pragma unroll
-            for (int q = 0; q < 32; ++q) x[q] = buf_load<LAST1024 ? TF_AUX_LAST_LOAD : TF_LOAD_AUX>(ri, toff, (u32)((long long)(brev5(q) << p2) * A.in_rs * 8));
+            for (int q = 0; q < 32; ++q) x[q] = buf_load(ri, toff, (u32)((long long)(brev5(q) << p2) * A.in_rs * 8));
         } else
 #pragma unroll
         for (int q = 0; q < 32; ++q) {
@@ -638,11 +464,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
                 const long long j = (ur + g) * A.ps_rs + (A.ps_col ? bcol : 0);
                 if (A.n_coeffs < 0 || j < A.n_coeffs) x[q] = *ptr;  // rows beyond the coefficients read as zero; scaled below
             } else {
-#ifdef TF_AB_BUILD
-                x[q] = (A.nt & 1) ? __builtin_nontemporal_load(ptr) : *ptr;  // uniform: the compiler emits the burst twice
-#else
-                x[q] = *ptr;  // (the run-time non-temporal variant, tf_set_ntt_nt, is a laboratory switch: TF_AB_BUILD)
-#endif
+                x[q] = *ptr;
             }
         }
     }
@@ -682,22 +504,17 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             }
         }
     }
-    if constexpr (PRE2 && !(TF_PRE2_BURST16 == 2 && SCALE != 1)) {
+    if constexpr (PRE2 && SCALE == 1) {
         if (half && act_in) pre2_shift<INV>(x);  // z_r = (x_r - x_{r+1024}) w_64^i; w_2048^g follows with the inner twiddle
     }
     __builtin_amdgcn_s_setprio(0);
-    if constexpr (MODE != 2 && !(PRE2 && TF_PRE2_BURST16 == 2 && SCALE != 1)) {  // (the overlapped PRE2 load above has done this already: zeros stay zeros)
+    if constexpr (!(PRE2 && SCALE != 1)) {  // (the overlapped PRE2 load above has done this already: zeros stay zeros)
         // Levels 1-4 of the first 16 slots need only the first 16 loads: start on them while the second half of the
         // burst is still in flight (the levels below 5 never mix the two halves).  Measured: 2.56 -> 2.44 ms.
         dit_half<INV, 0, LAZY1>(x);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (MODE == 3) {
-        stamp[1] = __builtin_readcyclecounter();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp[2] = __builtin_readcyclecounter();
-    }
-    if constexpr (MODE != 2) {
+    {
         dit_half<INV, 16, LAZY1>(x);
         dit_level<INV, 5, LAZY1>(x);
         if ((LAST1024 || R1024) || A.inner_tw) {  // (the R = 1024 instantiations always have an inner table: launch_pass checks;
@@ -707,7 +524,6 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             for (int q = 0; q < 32; q += 4) mul4_inplace(x, q, tw[q], tw[q + 1], tw[q + 2], tw[q + 3]);
         }
     }
-    if constexpr (MODE == 3) { asm volatile("" :: "v"(x[0]), "v"(x[31])); stamp[3] = __builtin_readcyclecounter(); }
     // ------------------------------------------------------------------ LDS exchange, `nrounds` rounds of `cpr` columns
     // Element (k1, g) of a column goes from the thread that owns row group g to the thread that owns k1 mod P2.
     // A thread writes its 32 values and reads its 32 new values in the SAME round, so only 32 are ever live.
@@ -762,9 +578,8 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             }
         }
     }
-    if constexpr (MODE == 3) { asm volatile("" :: "v"(x[0]), "v"(x[31])); stamp[4] = __builtin_readcyclecounter(); }
     // ------------------------------------------------------------------ step 2 (radix P2 over g) + store
-    __builtin_amdgcn_s_setprio(TF_PRIO_STEP2);
+    __builtin_amdgcn_s_setprio(kPrioStep2);
     if constexpr (LAST1024) {
         // R = 1024 and nothing to multiply: level 5 is fused with the stores, four butterflies (eight outputs) at a
         // time, so the store burst overlaps the end of the arithmetic.  Slot q holds output row k = g + 32 q.
@@ -796,29 +611,21 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             tail_p5<INV, 12, true>(x, act, base, toff, A.out_rs * 8, qlim);
             return;
         }
-        const bool nts = (A.nt & 2) != 0;
-        tail_p5<INV, 0>(x, act, base, toff, A.out_rs * 8, 32, nullptr, 0, 0, nts);
-        tail_p5<INV, 4>(x, act, base, toff, A.out_rs * 8, 32, nullptr, 0, 0, nts);
-        tail_p5<INV, 8>(x, act, base, toff, A.out_rs * 8, 32, nullptr, 0, 0, nts);
-        tail_p5<INV, 12>(x, act, base, toff, A.out_rs * 8, 32, nullptr, 0, 0, nts);
+        tail_p5<INV, 0>(x, act, base, toff, A.out_rs * 8);
+        tail_p5<INV, 4>(x, act, base, toff, A.out_rs * 8);
+        tail_p5<INV, 8>(x, act, base, toff, A.out_rs * 8);
+        tail_p5<INV, 12>(x, act, base, toff, A.out_rs * 8);
         return;
     }
-    if constexpr (MODE != 2) {
-        if (p2 >= 1) dit_level<INV, 1, LAZY2>(x);
-        if (p2 >= 2) dit_level<INV, 2, LAZY2>(x);
-        if (p2 >= 3) dit_level<INV, 3, LAZY2>(x);
-        if (p2 >= 4) dit_level<INV, 4, LAZY2>(x);
-        if (p2 >= 5) dit_level<INV, 5, LAZY2>(x);
-    }
-    if constexpr (MODE == 1) {
-        u64 acc = 0;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) acc ^= x[q];
-        if (acc == 0x123456789abcdefULL) out[t] = acc;  // keeps the arithmetic live; never true in practice
-    } else if (act) {
+    if (p2 >= 1) dit_level<INV, 1, LAZY2>(x);
+    if (p2 >= 2) dit_level<INV, 2, LAZY2>(x);
+    if (p2 >= 3) dit_level<INV, 3, LAZY2>(x);
+    if (p2 >= 4) dit_level<INV, 4, LAZY2>(x);
+    if (p2 >= 5) dit_level<INV, 5, LAZY2>(x);
+    if (act) {
         const u32 toff = (u32)(((long long)ch * A.out_cs_hi + cl + (long long)g * A.out_rs) * 8);
         char* base = reinterpret_cast<char*>(out);
-        if ((COLP && MODE == 0) || (MODE != 2 && A.post_tw)) {  // (R1024 / COL are only launched with an inter-pass table)
+        if (COLP || A.post_tw) {  // (R1024 / COL are only launched with an inter-pass table)
             // inter-pass twiddle: 8 table words at a time (bounded register footprint), multiply, store
             const u32 twoff = (u32)(((long long)g * A.tw_rs + bcol) * 8);
             const u64* ptw = A.post_tw;
@@ -844,7 +651,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const long long uk = (long long)((((q + e) >> p2) << p2) + (((q + e) & (P2 - 1)) << 5));  // uniform part of k
-                        if constexpr (COLP) buf_store<TF_AUX_COL_STORE>(ro, toff, (u32)(uk * A.out_rs * 8), r4[e]);
+                        if constexpr (COLP) buf_store(ro, toff, (u32)(uk * A.out_rs * 8), r4[e]);
                         else *reinterpret_cast<u64*>(base + uk * A.out_rs * 8 + toff) = r4[e];
                     }
                 }
@@ -883,154 +690,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_pass_kernel(const NttPa
             }
         }
     }
-    if constexpr (MODE == 3) {
-        stamp[5] = __builtin_readcyclecounter();
-        if (A.dbg && (t & 63) == 0 && blockIdx.x < 4096) {
-            unsigned long long* d = A.dbg + ((size_t)blockIdx.x * 8 + (t >> 6)) * 6;
-            for (int i = 0; i < 6; ++i) d[i] = stamp[i];
-        }
-    }
 }
-
-#ifdef TF_AB_BUILD  // measured loss (2.08 / 2.21 / 2.29 ms against 1.87, profiles/r03_chain_ab.txt): laboratory build only
-// ---- the R = 1024 column pass with the NEXT tile's loads issued inside the store phase -----------------------------------
-// ntt_pass_kernel's R1024 instantiation, plain transform, as a loop over `tiles_per_wg` tiles (tile, tile + gridDim.x, ...): the
-// eight registers a store group frees are filled at once with the next tile's loads, so a workgroup's load latency (a fifth of a
-// wave's lifetime in the one-tile kernel) runs under its own stores and under the partner workgroup's arithmetic instead of in
-// front of its first butterfly.  Few tiles per workgroup keep the dispatcher's dynamic balancing (a fully static assignment
-// measured slower in round 1).  Same arithmetic, same words.  Selected by TF_NTT_PERSIST = tiles per workgroup (A/B).
-template <bool INV>
-__global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col1024_chain_kernel(const NttPassArgs A, u32 total_tiles, u32 tiles_per_wg) {
-    extern __shared__ __attribute__((aligned(16))) u64 lds[];
-    const int t = threadIdx.x, g = t >> 4, c = t & 15;
-    const int L = A.L;
-    u64* const ltw = lds + 32 * kR1024S1;
-    for (int i = t; i < 1024; i += 512) ltw[(i >> 5) * kLdsTwStride + (i & 31)] = A.inner_tw[i];
-    __syncthreads();
-    const int ch = (int)div_by_L((u32)c, L), cl = c - ch * L;
-    // per-tile quantities: input / output bases, the element column of my word-column, whether my column exists
-    struct Tile {
-        const u64* in;
-        u64* out;
-        long long bcol;
-        bool act;
-    };
-    const auto decode = [&](u32 bid) {
-        u32 i0, i1, i2;
-        if (A.xcd_order) {
-            const u32 G = (u32)A.xcd_order, xcd = bid & 7u, slot = bid >> 3, ngrp = A.d2 / (8u * G);
-            const u32 grp = A.xcd_colfast ? slot % ngrp : slot / (G * A.d01);
-            const u32 within = A.xcd_colfast ? slot / ngrp : slot % (G * A.d01);
-            i2 = ((grp << 3) | xcd) * G + within % G;
-            const u32 rest = within / G;
-            i1 = rest % A.d1;
-            i0 = rest / A.d1;
-        } else {
-            i2 = bid % A.d2;
-            const u32 rest = bid / A.d2;
-            i1 = rest % A.d1;
-            i0 = rest / A.d1;
-        }
-        Tile T;
-        T.in = A.in + (long long)i0 * A.ib0 + (long long)i1 * A.ib1 + (long long)i2 * A.ib2;
-        T.out = A.out + (long long)i0 * A.ob0 + (long long)i1 * A.ob1 + (long long)i2 * A.ob2;
-        const int col0 = (int)i2 * kR1024Nc;
-        T.act = c < min(kR1024Nc, A.col_limit - col0);
-        T.bcol = (long long)div_by_L((u32)(col0 + c), L);
-        return T;
-    };
-    const u32 toff_in = (u32)(((long long)ch * A.in_cs_hi + cl + (long long)g * A.in_rs) * 8);
-    const u32 toff_out = (u32)(((long long)ch * A.out_cs_hi + cl + (long long)g * A.out_rs) * 8);
-    const int myround = c >> 3, cc = c & 7;
-    u64* const wr = lds + g * kR1024Cpr + cc;
-    const u64* const rd = lds + cc + g * kR1024S1;
-    u64 x[32];
-#pragma unroll
-    for (int q = 0; q < 32; ++q) x[q] = 0;
-    u32 bid = blockIdx.x;
-    Tile cur = decode(bid);
-    if (cur.act) {
-        const __amdgpu_buffer_rsrc_t ri = buf_rsrc(cur.in);
-#pragma unroll
-        for (int q = 0; q < 32; ++q) x[q] = buf_load<TF_LOAD_AUX>(ri, toff_in, (u32)((long long)(brev5(q) << 5) * A.in_rs * 8));
-    }
-#pragma unroll 1
-    for (u32 k = 0;; ++k) {
-        // ---- step 1
-        dit_half<INV, 0, true>(x);
-        __builtin_amdgcn_sched_barrier(0);
-        dit_half<INV, 16, true>(x);
-        dit_level<INV, 5, true>(x);
-        {
-            const u64* tw = ltw + g * kLdsTwStride;
-#pragma unroll
-            for (int q = 0; q < 32; q += 4) mul4_inplace(x, q, tw[q], tw[q + 1], tw[q + 2], tw[q + 3]);
-        }
-        // ---- exchange (two rounds of eight columns); the barrier in front also separates it from the previous tile's reads
-        if (k) __syncthreads();
-#pragma unroll 1
-        for (int r = 0; r < kR1024Rounds; ++r) {
-            if (r) __syncthreads();
-            if (myround == r) {
-#pragma unroll
-                for (int q = 0; q < 32; ++q) wr[q * kR1024S1] = x[q];
-            }
-            __syncthreads();
-            if (myround == r) {
-#pragma unroll
-                for (int q = 0; q < 32; ++q) x[q] = rd[brev5(q) * kR1024Cpr];
-            }
-        }
-        // ---- step 2
-        dit_level<INV, 1, true>(x);
-        dit_level<INV, 2, true>(x);
-        dit_level<INV, 3, true>(x);
-        dit_level<INV, 4, true>(x);
-        dit_level<INV, 5, true>(x);
-        // ---- inter-pass twiddles, stores, and the next tile's loads into the registers the stores free
-        const u32 nbid = bid + gridDim.x;
-        const bool has_next = k + 1 < tiles_per_wg && nbid < total_tiles;  // uniform
-        Tile nxt = cur;
-        if (has_next) nxt = decode(nbid);
-        if (cur.act) {
-            const u32 twoff = (u32)(((long long)g * A.tw_rs + cur.bcol) * 8);
-            const __amdgpu_buffer_rsrc_t rt = buf_rsrc(A.post_tw), ro = buf_rsrc(cur.out), rn = buf_rsrc(nxt.in);
-#pragma unroll
-            for (int q0 = 0; q0 < 32; q0 += 8) {
-                u64 w[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) w[i] = buf_load_tab(rt, twoff, (u32)((long long)((q0 + i) << 5) * A.tw_rs * 8));
-#pragma unroll
-                for (int i = 0; i < 8; i += 4) {
-                    const int q = q0 + i;
-                    const u64 a4[4] = {x[q], x[q + 1], x[q + 2], x[q + 3]}, b4[4] = {w[i], w[i + 1], w[i + 2], w[i + 3]};
-                    u64 r4[4];
-                    gl::mont_mul4(a4, b4, r4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) buf_store<TF_AUX_COL_STORE>(ro, toff_out, (u32)((long long)((q + e) << 5) * A.out_rs * 8), r4[e]);
-                }
-                if (has_next && nxt.act) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) x[q0 + i] = buf_load<TF_LOAD_AUX>(rn, toff_in, (u32)((long long)(brev5(q0 + i) << 5) * A.in_rs * 8));
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else if (has_next && nxt.act) {
-            const __amdgpu_buffer_rsrc_t rn = buf_rsrc(nxt.in);
-#pragma unroll
-            for (int q = 0; q < 32; ++q) x[q] = buf_load<TF_LOAD_AUX>(rn, toff_in, (u32)((long long)(brev5(q) << 5) * A.in_rs * 8));
-        }
-        if (!has_next) break;
-        if (!nxt.act) {
-#pragma unroll
-            for (int q = 0; q < 32; ++q) x[q] = 0;
-        }
-        bid = nbid;
-        cur = nxt;
-    }
-}
-
-#endif  // TF_AB_BUILD
 
 // ---- a 2048-point COLUMN pass in ONE workgroup: 2048 rows x 8 word-columns (round 6, the first pass of the 2^21 / 2^22 plans) ----
 // PRE2 runs a 2048-point pass as two 1024-point workgroups that both load (and, in a coset evaluation, both SCALE) the tile's
@@ -1049,15 +709,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col1024_chain_kernel(co
 //            Then radix 32 over g' (shift-only), the inter-pass twiddle, and stores to rows k1 + 32 h + 64 k2'.
 // Global segments are 64 bytes (8 word-columns): the planner's xcd_order = 2 dispatches the two tiles that share every 128-byte line
 // back to back on one XCD.  Same words as every other plan (tests: tf_set_ntt_two_pass(3)).
-#ifndef TF_C8_LOAD_AUX
-#define TF_C8_LOAD_AUX 0  // default cache policy: the neighbouring tile's read of the other half of every 128-byte line should find it in the L2
-#endif
-#ifndef TF_C8_STORE_AUX
-#define TF_C8_STORE_AUX TF_AUX_COL_STORE
-#endif
-#ifndef TF_C8_ABLATE
-#define TF_C8_ABLATE 0  // measurement builds only (tools/build_variant.sh): 1 no scale-table loads, 2 no inter-pass table loads, 4 no arithmetic networks
-#endif
+constexpr int kC8LoadAux = 0;  // default cache policy: the neighbouring tile's read of the other half of every 128-byte line should find it in the L2
 constexpr int kC8Nc = 8, kC8Cpr = 4, kC8Rounds = 2, kC8S1 = 260;
 // A workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope fence over every address space, i.e.
 // s_waitcnt vmcnt(0): every global load in flight is waited for at the barrier -- which is what made table words requested ahead of the
@@ -1092,16 +744,8 @@ __device__ __forceinline__ void c8_combine8(u64 (&x)[32], const u64 (&w)[8], boo
         x[Q0 + 1] = gl::add(x[Q0 + 1], w[1]), x[Q0 + 3] = gl::add(x[Q0 + 3], w[3]), x[Q0 + 5] = gl::add(x[Q0 + 5], w[5]), x[Q0 + 7] = gl::add(x[Q0 + 7], w[7]);
     }
 }
-#ifndef TF_C8_LDS_BARRIER
-#define TF_C8_LDS_BARRIER 1
-#endif
-#if TF_C8_LDS_BARRIER
-#define TF_C8_BARRIER lds_barrier
-#else
-#define TF_C8_BARRIER __syncthreads
-#endif
 template <bool INV, int SCALE>
-__global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const NttPassArgs A) {
+__global__ void __launch_bounds__(512, kNttWaves) ntt_col2048_kernel(const NttPassArgs A) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     static_assert(SCALE == 0 || (SCALE == 1 && !INV), "plain passes, or the scaling / zero-padding first pass of a coset evaluation");
     const int t = threadIdx.x;
@@ -1115,23 +759,16 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
         const u32 bid = blockIdx.x;
         if (A.xcd_order) {  // (see ntt_pass_kernel)
             const u32 G = (u32)A.xcd_order, xcd = bid & 7u, slot = bid >> 3, ngrp = A.d2 / (8u * G);
-#ifndef TF_C8_XCD_SKEW
-#define TF_C8_XCD_SKEW 3  // XCD x takes column pair (x + 3 grp) mod 8 of column group grp instead of pair x of every group: its tiles then spread over
-                           // more of its L2's channels (measured 0.945-0.955 of the PRE2 time against 0.965-0.973 without, profiles/r06_c4_cols8_ab.txt)
-#endif
-#ifndef TF_C8_COLBLOCK
-#define TF_C8_COLBLOCK 1  // column groups an XCD walks interleaved (their inter-pass table slices share its L2); must divide ngrp
-#endif
+            // XCD x takes column pair (x + 3 grp) mod 8 of column group grp instead of pair x of every group: its tiles then spread over
+            // more of its L2's channels (measured 0.945-0.955 of the PRE2 time against 0.965-0.973 without, profiles/r06_c4_cols8_ab.txt)
+            constexpr u32 kC8XcdSkew = 3;
             u32 grp, within;
             if (A.xcd_colfast) {
                 grp = slot % ngrp, within = slot / ngrp;
-            } else if (TF_C8_COLBLOCK > 1 && ngrp % TF_C8_COLBLOCK == 0) {
-                const u32 per = G * A.d01 * TF_C8_COLBLOCK, blk = slot / per, r = slot % per;
-                grp = blk * TF_C8_COLBLOCK + r % TF_C8_COLBLOCK, within = r / TF_C8_COLBLOCK;
             } else {
                 grp = slot / (G * A.d01), within = slot % (G * A.d01);
             }
-            i2 = ((grp << 3) | (TF_C8_XCD_SKEW ? ((xcd + grp * TF_C8_XCD_SKEW) & 7u) : xcd)) * G + within % G;
+            i2 = ((grp << 3) | ((xcd + grp * kC8XcdSkew) & 7u)) * G + within % G;
             const u32 rest = within / G;
             i1 = rest % A.d1;
             i0 = rest / A.d1;
@@ -1181,7 +818,7 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
 #pragma unroll
     for (int q = 0; q < 32; ++q) x[q] = 0;
     // ------------------------------------------------------------------ load (+ scale) + step 1
-    __builtin_amdgcn_s_setprio(TF_PRIO_LOAD);
+    __builtin_amdgcn_s_setprio(kPrioLoad);
     if (act) {
         const u32 toff = (u32)(((long long)ch * A.in_cs_hi + cl + (long long)g * A.in_rs) * 8);
         if constexpr (SCALE == 1) {
@@ -1193,11 +830,11 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
             const __amdgpu_buffer_rsrc_t ri = buf_rsrc_n(in, nrec);
             // (the range check of a raw buffer covers the per-lane offset only: the whole offset goes through the VGPR)
 #pragma unroll
-            for (int q = 0; q < 32; ++q) x[q] = buf_load<TF_C8_LOAD_AUX>(ri, toff + (u32)((long long)(brev5(q) << 6) * A.in_rs * 8), 0);
+            for (int q = 0; q < 32; ++q) x[q] = buf_load<kC8LoadAux>(ri, toff + (u32)((long long)(brev5(q) << 6) * A.in_rs * 8), 0);
         } else {
             const __amdgpu_buffer_rsrc_t ri = buf_rsrc(in);
 #pragma unroll
-            for (int q = 0; q < 32; ++q) x[q] = buf_load<TF_C8_LOAD_AUX>(ri, toff, (u32)((long long)(brev5(q) << 6) * A.in_rs * 8));
+            for (int q = 0; q < 32; ++q) x[q] = buf_load<kC8LoadAux>(ri, toff, (u32)((long long)(brev5(q) << 6) * A.in_rs * 8));
         }
     }
 #pragma unroll
@@ -1213,61 +850,26 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
         }
     }
     __builtin_amdgcn_s_setprio(0);
-    if constexpr (!(TF_C8_ABLATE & 4)) {
-        dit_half<INV, 0, true>(x);
-        __builtin_amdgcn_sched_barrier(0);
-        dit_half<INV, 16, true>(x);
-        dit_level<INV, 5, true>(x);
-    }
-    TF_C8_BARRIER();  // the staged table is complete
+    dit_half<INV, 0, true>(x);
+    __builtin_amdgcn_sched_barrier(0);
+    dit_half<INV, 16, true>(x);
+    dit_level<INV, 5, true>(x);
+    lds_barrier();  // the staged table is complete
     {
         const u64* tw = ltw + g * kLdsTwStride;
 #pragma unroll
         for (int q = 0; q < 32; q += 4) mul4_inplace(x, q, tw[q], tw[q + 1], tw[q + 2], tw[q + 3]);
     }
-    TF_C8_BARRIER();  // every wave has read its table rows: the exchange may overwrite them
-    // the inter-pass table's first words are requested before the exchange: they arrive under it and under step 2
+    lds_barrier();  // every wave has read its table rows: the exchange may overwrite them
     const int krow = k1 + 32 * (int)half;  // slot q holds output row krow + 64 q
     const u32 twoff = (u32)(((long long)krow * A.tw_rs + bcol) * 8);
     const __amdgpu_buffer_rsrc_t rt = buf_rsrc(A.post_tw);
-#ifndef TF_C8_UV
-#define TF_C8_UV 0  // 1: T[(krow + 64 q) B + b] = T[krow B + b] * T[64 q B + b] -- ONE word per thread from its own row (with offset^b when the pass
-                    //    scales) and 32 words from rows 64 q that every thread of the tile shares (32 lines per tile instead of 2 048 32-byte
-                    //    segments), one more product per element.  MEASURED as a loss: 7.58-7.75 ms against 7.34-7.36 on BASELINE configs[3]
-                    //    (profiles/r06_c4_cols8_ab.txt); 0: one table word per element
-#endif
-    const __amdgpu_buffer_rsrc_t rtu = buf_rsrc(A.post_tw_u ? A.post_tw_u : A.post_tw);
-    const u32 uoff = (u32)(bcol * 8);
-    const auto tw_load = [&](int q) {
-        if constexpr (TF_C8_UV) return (TF_C8_ABLATE & 2) ? (u64)(q + 5) : buf_load_tab(rtu, uoff, (u32)((long long)(q << 6) * A.tw_rs * 8));
-        else return (TF_C8_ABLATE & 2) ? (u64)(q + 5) : buf_load_tab(rt, twoff, (u32)((long long)(q << 6) * A.tw_rs * 8));
-    };
-    u64 vrow = 0;
-    if constexpr (TF_C8_UV) {
-        if (act) vrow = buf_load_tab(rt, twoff, 0);
-    }
-#ifndef TF_C8_PREFETCH
-#define TF_C8_PREFETCH 0  // inter-pass table words requested ahead of step 2 (0 / 8 / 16): measured 7.60 / 7.75 / 8.04 ms on BASELINE configs[3] -- more of them in flight is SLOWER (profiles/r06_c4_cols8_ab.txt)
-#endif
-#ifndef TF_C8_PREFETCH_AT
-#define TF_C8_PREFETCH_AT 1  // 0: request them before the exchange, 1: after it (in front of step 2's networks)
-#endif
+    // One table word per element, requested in front of its products (two buffers, wa / wb), none ahead of step 2.  MEASURED on BASELINE
+    // configs[3] (profiles/r06_c4_cols8_ab.txt): 0 / 8 / 16 words requested ahead of step 2 7.60 / 7.75 / 8.04 ms -- more of them in flight is
+    // SLOWER; the factored table T[krow B + b] * T[64 q B + b] (one word per thread, 32 shared rows, one more product per element)
+    // 7.58-7.75 ms against 7.34-7.36.
+    const auto tw_load = [&](int q) { return buf_load_tab(rt, twoff, (u32)((long long)(q << 6) * A.tw_rs * 8)); };
     u64 wa[8], wb[8];
-    const auto prefetch = [&]() {
-        if constexpr (TF_C8_PREFETCH >= 8) {
-            if (act) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) wa[i] = tw_load(i);
-            }
-        }
-        if constexpr (TF_C8_PREFETCH >= 16) {
-            if (act) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) wb[i] = tw_load(8 + i);
-            }
-        }
-    };
-    if constexpr (TF_C8_PREFETCH_AT == 0) prefetch();
     // ------------------------------------------------------------------ exchange + the fused radix-2 stage
     {
         const int myround = c >> 2, cc = c & 3;
@@ -1275,12 +877,12 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
         const u64* const rd = lds + k1 * kC8S1 + cc;
 #pragma unroll 1
         for (int r = 0; r < kC8Rounds; ++r) {
-            if (r) TF_C8_BARRIER();
+            if (r) lds_barrier();
             if (myround == r) {
 #pragma unroll
                 for (int q = 0; q < 32; ++q) wr[q * kC8S1] = x[q];
             }
-            TF_C8_BARRIER();
+            lds_barrier();
             if (myround == r) {
                 const auto group = [&](auto q0c) {
                     constexpr int Q0 = decltype(q0c)::value;
@@ -1299,17 +901,14 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
             }
         }
     }
-    if constexpr (TF_C8_PREFETCH_AT == 1) prefetch();
     if (half) pre2_shift<INV>(x);
     // ------------------------------------------------------------------ step 2 (radix 32 over g') + inter-pass twiddle + store
-    __builtin_amdgcn_s_setprio(TF_PRIO_STEP2);
-    if constexpr (!(TF_C8_ABLATE & 4)) {
-        dit_level<INV, 1, true>(x);
-        dit_level<INV, 2, true>(x);
-        dit_level<INV, 3, true>(x);
-        dit_level<INV, 4, true>(x);
-        dit_level<INV, 5, true>(x);
-    }
+    __builtin_amdgcn_s_setprio(kPrioStep2);
+    dit_level<INV, 1, true>(x);
+    dit_level<INV, 2, true>(x);
+    dit_level<INV, 3, true>(x);
+    dit_level<INV, 4, true>(x);
+    dit_level<INV, 5, true>(x);
     if (act) {
         const u32 toff = (u32)(((long long)ch * A.out_cs_hi + cl + (long long)krow * A.out_rs) * 8);
         const __amdgpu_buffer_rsrc_t ro = buf_rsrc(out);
@@ -1321,22 +920,14 @@ __global__ void __launch_bounds__(512, TF_NTT_WAVES) ntt_col2048_kernel(const Nt
                 const u64 a4[4] = {x[q], x[q + 1], x[q + 2], x[q + 3]}, b4[4] = {w[i], w[i + 1], w[i + 2], w[i + 3]};
                 u64 r4[4];
                 gl::mont_mul4(a4, b4, r4);
-                if constexpr (TF_C8_UV) {
-                    const u64 c4[4] = {r4[0], r4[1], r4[2], r4[3]}, v4[4] = {vrow, vrow, vrow, vrow};
-                    gl::mont_mul4(c4, v4, r4);
-                }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) buf_store<TF_C8_STORE_AUX>(ro, toff, (u32)((long long)((q + e) << 6) * A.out_rs * 8), r4[e]);
+                for (int e = 0; e < 4; ++e) buf_store(ro, toff, (u32)((long long)((q + e) << 6) * A.out_rs * 8), r4[e]);
             }
         };
-        if constexpr (TF_C8_PREFETCH < 8) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) wa[i] = tw_load(i);
-        }
-        if constexpr (TF_C8_PREFETCH < 16) {
+        for (int i = 0; i < 8; ++i) wa[i] = tw_load(i);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) wb[i] = tw_load(8 + i);
-        }
+        for (int i = 0; i < 8; ++i) wb[i] = tw_load(8 + i);
         mul_store(0, wa);
 #pragma unroll
         for (int i = 0; i < 8; ++i) wa[i] = tw_load(16 + i);
@@ -1545,89 +1136,10 @@ struct NttRows32Args {
     int L;
 };
 
-#ifdef TF_AB_BUILD
-// ---- n = 32, contiguous transforms: one transform (one limb of it for XFE) per thread, staged through LDS ---------------
-// A thread's 32 elements are contiguous in memory, so direct loads are 8-byte pieces 256 bytes apart (1.94 ms per 2^28 words).
-// Here the workgroup streams its tile (512 BFE transforms or 170 XFE transforms = 510 limb-transforms) through LDS in two
-// halves: coalesced loads into rows of pitch 33, each thread picks up its row, transforms it in registers, puts it back, and
-// the tile leaves with coalesced stores.
-
-template <bool INV>
-__global__ void __launch_bounds__(512, 4) ntt_rows32_kernel(const NttRows32Args A) {
-    extern __shared__ __attribute__((aligned(16))) u64 lds[];
-    const int t = threadIdx.x, L = A.L;
-    const int per_tile = L == 1 ? 512 : 170;                     // transforms per workgroup
-    const long long tr0 = (long long)blockIdx.x * per_tile;
-    const int ntr = (int)min((long long)per_tile, A.total_transforms - tr0);
-    const int nlt = ntr * L;                                     // limb-transforms (threads with work)
-    const int half_lt = L == 1 ? 256 : 255;                      // first half: limb-transforms [0, half_lt)
-    const u64* src = A.in + tr0 * 32 * L;
-    u64* dst = A.out + tr0 * 32 * L;
-    const int words = nlt * 32;
-    const int split = min(words, half_lt * 32);                  // words of the first half (whole transforms)
-    u64 x[32];
-#pragma unroll
-    for (int q = 0; q < 32; ++q) x[q] = 0;
-    const int myhalf = t >= half_lt ? 1 : 0;
-    const int row = t - myhalf * half_lt;
-#pragma unroll 1
-    for (int h = 0; h < 2; ++h) {
-        const int w0 = h ? split : 0, w1 = h ? words : split;
-        if (h) __syncthreads();
-        for (int w = w0 + t; w < w1; w += 512) {
-            int lt, e;
-            if (L == 1) {
-                lt = w >> 5;
-                e = w & 31;
-            } else {
-                const int el = (int)__umulhi((u32)w, 0x55555556u), limb = w - 3 * el;
-                lt = (el >> 5) * 3 + limb;
-                e = el & 31;
-            }
-            lds[(lt - h * half_lt) * 33 + e] = src[w];
-        }
-        __syncthreads();
-        if (myhalf == h && t < nlt) {
-#pragma unroll
-            for (int q = 0; q < 32; ++q) x[q] = lds[row * 33 + brev5(q)];
-        }
-    }
-    dit_half<INV, 0, INV>(x);   // the inverse multiplies every word by 32^-1 afterwards: lazy network
-    dit_half<INV, 16, INV>(x);
-    dit_level<INV, 5, INV>(x);
-    if (INV) {
-#pragma unroll
-        for (int q = 0; q < 32; q += 4) mul4_inplace(x, q, A.scale, A.scale, A.scale, A.scale);
-    }
-#pragma unroll 1
-    for (int h = 0; h < 2; ++h) {
-        const int w0 = h ? split : 0, w1 = h ? words : split;
-        __syncthreads();
-        if (myhalf == h && t < nlt) {
-#pragma unroll
-            for (int q = 0; q < 32; ++q) lds[row * 33 + q] = x[q];
-        }
-        __syncthreads();
-        for (int w = w0 + t; w < w1; w += 512) {
-            int lt, e;
-            if (L == 1) {
-                lt = w >> 5;
-                e = w & 31;
-            } else {
-                const int el = (int)__umulhi((u32)w, 0x55555556u), limb = w - 3 * el;
-                lt = (el >> 5) * 3 + limb;
-                e = el & 31;
-            }
-            dst[w] = lds[(lt - h * half_lt) * 33 + e];
-        }
-    }
-}
-#endif
-
 // ---- n <= 64, wave-private tiles ----------------------------------------------------------------------------------------------
 // A thread's 32 elements are contiguous in memory, so direct loads would be 8-byte pieces 256 bytes apart (1.94 ms per 2^28 words),
 // and a workgroup that moves its tile through LDS in barrier-separated phases (load | pick up rows | transform | put rows back |
-// store; round 2's ntt_rows32_kernel, kept in the laboratory build) leaves the memory pipe or the vector ALU idle in every phase:
+// store; round 2's ntt_rows32_kernel) leaves the memory pipe or the vector ALU idle in every phase:
 // 1.21 ms per 2^28 words against the 0.87 ms of one coalesced round trip.  Here a WAVE owns its tile -- 64 BFieldElement transforms,
 // or 21 XFieldElement transforms = 63 limb-transforms (a limb-transform is what one lane computes) -- and its own 64 x 33 words of
 // LDS: no barrier anywhere, and the loads of the wave's next tile are issued before the current one is touched, so every wave keeps

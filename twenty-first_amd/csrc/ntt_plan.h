@@ -32,13 +32,12 @@ enum class NttRoute {
 struct NttPlan {
     NttRoute route = NttRoute::Passes;
     int wg = 512;         // threads per workgroup of the pass kernels in this call: 512, or 256 for the narrow tiles
-    bool narrow = false;  // the narrow tiles were CHOSEN for this call (too little work for the wide ones), not forced by TF_NTT_WG_THREADS
+    bool narrow = false;  // the narrow tiles were chosen for this call (too little work for the wide ones)
     // Passes only
     int P = 0;                                    // global passes
     int a[4] = {0, 0, 0, 0};                      // log2 of each pass's radix; sum = log2 n
     bool pre2[4] = {false, false, false, false};  // pass i is a 2048-point pass run as pairs of 1024-point workgroups (PRE2)
     bool c8 = false;                              // the first pass is the one-workgroup 2048-point column pass (ntt_col2048_kernel)
-    bool pre4_last = false;                       // the last pass is a 4096-point one in four classes (PRE4, laboratory build)
     bool plain1024 = false;                       // the last pass takes the plain R = 1024 kernel (LAST1024) ...
     int words = 0;                                // ... and its tiles are this many adjacent output words (0: whole elements)
     size_t tb = 0, ntiles = 0;                    // polynomials per batch tile (after the equal-tiles rebalance), tiles
@@ -62,15 +61,5 @@ bool lat2_wanted(int log_n, size_t batch, int L);
 // fast_coset_evaluate: the number of cosets of the padded coefficient length the evaluation is split into (1: the plain plan)
 constexpr size_t kMaxCosetSplit = 64;
 size_t coset_split(size_t n_coeffs, size_t order, size_t batch, int L);
-// A/B switches and ablation modes that the pass launchers read as well
-bool last1024_enabled(bool narrow);
-bool scaled_last1024_enabled();
-bool col_enabled();
-const char* exp_env(const char* name);
-#ifdef TF_AB_BUILD
-int ablate_mode();
-#else
-constexpr int ablate_mode() { return 0; }  // the ablated kernels (no memory / no arithmetic / phase stamps) are laboratory instantiations
-#endif
 
 }  // namespace tfi

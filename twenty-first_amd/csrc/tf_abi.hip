@@ -194,12 +194,6 @@ size_t tf_get_ntt_tile_bytes(void) {
     return g_tile_bytes;
 }
 void tf_set_batch_eval_route(int route) { g_batch_eval_route.store(route == 1 || route == 2 ? route : 0, std::memory_order_relaxed); }
-#ifdef TF_AB_BUILD
-void tf_set_ntt_nt(int mask) {
-    read_env();
-    g_nt.store(mask & 3, std::memory_order_relaxed);
-}
-#endif
 void tf_set_ntt_pipe(int streams) {
     read_env();
     g_pipe.store(std::min(std::max(streams, 0), kMaxPipe), std::memory_order_relaxed);  // 0 = automatic
@@ -301,25 +295,7 @@ int tf_debug_force_temp_tables(int on) try {
     return force_temp_tables(on);
 } TF_ABI_CATCH
 
-#ifdef TF_AB_BUILD
-// measurement helper (not part of the drop-in boundary): allocate / fetch the MODE-3 stamp buffer
-int tf_debug_stamps(unsigned long long* host_out, size_t words) try {
-    if (!g_dbg_buf) {
-        if (hipMalloc(reinterpret_cast<void**>(&g_dbg_buf), 4096 * 8 * 6 * 8) != hipSuccess) return TF_ERR_HIP;
-        (void)hipMemset(g_dbg_buf, 0, 4096 * 8 * 6 * 8);
-    }
-    if (host_out && words) {
-        if (hipDeviceSynchronize() != hipSuccess) return TF_ERR_HIP;
-        if (hipMemcpy(host_out, g_dbg_buf, std::min<size_t>(words, 4096 * 8 * 6) * 8, hipMemcpyDeviceToHost) != hipSuccess) return TF_ERR_HIP;
-    }
-    return TF_OK;
-} TF_ABI_CATCH
-#endif
-
 void tf_set_ntt_min_passes(int passes) { g_min_passes.store(passes, std::memory_order_relaxed); }
-#ifdef TF_AB_BUILD
-void tf_set_ntt_chain(int tiles_per_workgroup) { g_chain.store(std::max(0, tiles_per_workgroup), std::memory_order_relaxed); }
-#endif
 void tf_set_ntt_latency_kernel(int mode) { g_lat_mode.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); }
 void tf_set_ntt_two_pass(int mode) { g_pre2_mode.store(mode < 0 ? -1 : (mode > 3 ? 1 : mode), std::memory_order_relaxed); }
 void tf_set_ntt_small_launch(int mode) { g_small_launch_mode.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); }

@@ -99,17 +99,16 @@ int launch_degree(const u64* a, size_t na, int w, size_t batch, long long* deg, 
     return TF_OK;
 }
 
-template <bool PLAIN>
 int launch_lincomb_t(const u64* polys, size_t n, int wp, size_t stride, size_t k, const u64* w, int ww, u64* out, hipStream_t s) {
     long long items = (long long)n;
     if (wp == 3 && ww == 1) items *= 3, wp = 1;  // BFieldElement weights: the limbs of a column are independent words
     const dim3 grid(blocks_for(items));
     if (wp == 1 && ww == 1)
-        hipLaunchKernelGGL((tfk::poly_lincomb_kernel<1, 1, PLAIN>), grid, dim3(T), 0, s, polys, items, (long long)stride, (int)k, w, out);
+        hipLaunchKernelGGL((tfk::poly_lincomb_kernel<1, 1>), grid, dim3(T), 0, s, polys, items, (long long)stride, (int)k, w, out);
     else if (wp == 1)
-        hipLaunchKernelGGL((tfk::poly_lincomb_kernel<1, 3, PLAIN>), grid, dim3(T), 0, s, polys, items, (long long)stride, (int)k, w, out);
+        hipLaunchKernelGGL((tfk::poly_lincomb_kernel<1, 3>), grid, dim3(T), 0, s, polys, items, (long long)stride, (int)k, w, out);
     else
-        hipLaunchKernelGGL((tfk::poly_lincomb_kernel<3, 3, PLAIN>), grid, dim3(T), 0, s, polys, items, (long long)stride, (int)k, w, out);
+        hipLaunchKernelGGL((tfk::poly_lincomb_kernel<3, 3>), grid, dim3(T), 0, s, polys, items, (long long)stride, (int)k, w, out);
     HIPCHK(hipGetLastError());
     return TF_OK;
 }
@@ -119,11 +118,7 @@ int launch_lincomb(const u64* polys, size_t n, int wp, size_t stride, size_t k, 
         HIPCHK(hipMemsetAsync(out, 0, n * (size_t)std::max(wp, ww) * sizeof(u64), s));
         return TF_OK;
     }
-#ifdef TF_AB_BUILD
-    const bool plain = ab_env("TF_LINCOMB_PLAIN") != nullptr;  // one product and one modular addition per term; read per call, so one process can time both
-    if (plain) return launch_lincomb_t<true>(polys, n, wp, stride, k, w, ww, out, s);
-#endif
-    return launch_lincomb_t<false>(polys, n, wp, stride, k, w, ww, out, s);
+    return launch_lincomb_t(polys, n, wp, stride, k, w, ww, out, s);
 }
 
 int need_device() {

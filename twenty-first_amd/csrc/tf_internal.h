@@ -63,16 +63,9 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
         if (rc_) return rc_; \
     } while (0)
 
-// The product library has ONE plan: every A/B switch and diagnostic knob of the laboratory (the TF_* environment variables of
-// DESIGN_HISTORY.md, the measured-loser kernels, the ablation modes) exists only in the TF_AB_BUILD library (make ab ->
-// libtf_hip_ab.so).  In the product build ab_env() is a constant null pointer, so every switch folds away at compile time; the
-// product reads exactly two environment variables, both deployment settings: TF_NTT_TILE_BYTES (scratch budget between the passes)
-// and TF_NTT_PIPE (side streams for pipelined batch tiles).
-#ifdef TF_AB_BUILD
-inline const char* ab_env(const char* name) { return getenv(name); }
-#else
-constexpr const char* ab_env(const char*) { return nullptr; }
-#endif
+// The library has ONE plan and one set of kernels (the variants that lost their measurements are listed in DESIGN_HISTORY.md, with
+// their records under profiles/).  It reads exactly two environment variables, both deployment settings: TF_NTT_TILE_BYTES (scratch
+// budget between the passes) and TF_NTT_PIPE (side streams for pipelined batch tiles).
 
 u64 root_of_unity_mont(int log_n);
 
@@ -103,11 +96,11 @@ constexpr int kMaxDevices = 64;
 extern DeviceCtx g_ctx[kMaxDevices];
 
 // ------------------------------------------------------------------------------------ tf_plan.hip
-// the planner's functions: ntt_plan.h.  Configuration (tf_set_* hooks of the ABI; TF_* environment variables read once by read_env):
+// the planner's functions: ntt_plan.h.  Configuration (tf_set_* hooks of the ABI; the two TF_NTT_* settings read once by read_env):
 constexpr int kMaxPipe = 4;
 void read_env();
 extern size_t g_tile_bytes;
-extern std::atomic<int> g_pipe, g_nt, g_min_passes, g_lat_mode, g_pre2_mode, g_small_launch_mode;
+extern std::atomic<int> g_pipe, g_min_passes, g_lat_mode, g_pre2_mode, g_small_launch_mode;
 
 // ------------------------------------------------------------------------------------ tf_ntt.hip
 int current_ctx(DeviceCtx** out);
@@ -135,11 +128,6 @@ int temp_guard_selftest(int defect, size_t n_words, uint64_t* out_word);
 int ensure_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done_mask);
 int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, const u64** out, bool* temp, size_t cosets = 1, int log_order = 0);
 void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t stream);  // after the launches that read a table get_pow_table returned
-
-#ifdef TF_AB_BUILD
-extern std::atomic<int> g_chain;
-extern unsigned long long* g_dbg_buf;
-#endif
 
 // keys of DeviceCtx::tables
 enum : u64 { TAG_INNER = 1, TAG_POST = 2, TAG_TINY = 3, TAG_BLOCK1 = 4, TAG_BLOCK2 = 5, TAG_LAT = 6 };
@@ -215,8 +203,7 @@ static_assert(kCoopMaxCount >= 64 && (kCoopMaxCount & (kCoopMaxCount - 1)) == 0,
 // PAIR instead (tip5_permutation_coop2: the circulant's sixteen rotation terms split over the two rows; 2.01 -> 1.68 us per permutation,
 // profiles/r06_microbench_coop2.txt).  A workgroup then holds 8 chains, so up to this count every workgroup still has a CU of its own.
 inline bool coop_two_rows(long long chains) {
-    static const bool off = ab_env("TF_TIP5_NO_COOP2") != nullptr;  // A/B switch
-    return !off && chains <= 8ll * device_cus();
+    return chains <= 8ll * device_cus();
 }
 // grid of a matrix-pipe launch: one workgroup (4 waves x 16 permutations) per 64 items, capped at kMxBlocksPerCu per CU -- beyond
 // that the waves walk the items with a grid stride, so the tables are staged once per wave and not once per 16 items (8 workgroups

@@ -11,16 +11,6 @@ namespace {
 template <int L, bool OR_ZERO>
 int launch_inverse(const u64* in, size_t n, u64* out, int* status, hipStream_t s) {
     const long long cap = (long long)device_cus() * 8;
-#ifdef TF_AB_BUILD
-    static const bool per_element = ab_env("TF_BATCH_INV_PER_ELEMENT") != nullptr;
-    if (per_element) {
-        const long long blocks = std::min<long long>(((long long)n + 255) / 256, cap * 4);
-        hipLaunchKernelGGL((tfk::per_element_inverse_kernel<L, OR_ZERO>), dim3((unsigned)blocks), dim3(256), 0, s, in, (long long)n, out, status,
-                           (int)TF_ERR_INVERSE_OF_ZERO);
-        HIPCHK(hipGetLastError());
-        return TF_OK;
-    }
-#endif
     const long long chunks = ((long long)n + tfk::InvGeom<L>::CHUNK - 1) / tfk::InvGeom<L>::CHUNK;
     const long long blocks = std::min<long long>((chunks + 3) / 4, cap);
     hipLaunchKernelGGL((tfk::batch_inverse_kernel<L, OR_ZERO>), dim3((unsigned)blocks), dim3(256), 0, s, in, (long long)n, out, status,

@@ -109,40 +109,16 @@ int launch_tree_level_t(const tfk::TreeLevelArgs& a, hipStream_t stream) {
     HIPCHK(hipGetLastError());
     return TF_OK;
 }
-#ifdef TF_AB_BUILD
-template <int LOGN, bool UP>
-int launch_tree_level_xfe_t(const tfk::TreeLevelArgs& a, hipStream_t stream) {
-    using G = tfk::TreeXfeGeom<LOGN>;
-    constexpr size_t lds = size_t(UP ? 3 : 2) * G::BUF * sizeof(u64);
-    static_assert(lds <= 160 * 1024, "level too long for one workgroup");
-    const void* fn = UP ? reinterpret_cast<const void*>(&tfk::tree_up_level_xfe_kernel<LOGN>) : reinterpret_cast<const void*>(&tfk::tree_down_level_xfe_kernel<LOGN>);
-    if constexpr (lds > 48 * 1024) {
-        static std::atomic<unsigned long long> done_mask{0};
-        if (int rc_attr = ensure_dynamic_lds(fn, (int)lds, done_mask)) return rc_attr;
-    }
-    const long long blocks = (a.lines + G::T - 1) / G::T;
-    if (UP) hipLaunchKernelGGL((tfk::tree_up_level_xfe_kernel<LOGN>), dim3((unsigned)blocks), dim3(G::WG), lds, stream, a);
-    else hipLaunchKernelGGL((tfk::tree_down_level_xfe_kernel<LOGN>), dim3((unsigned)blocks), dim3(G::WG), lds, stream, a);
-    HIPCHK(hipGetLastError());
-    return TF_OK;
-}
-#endif
 // When: the level's transforms are the latency-shaped kernel's anyway AND the level is small enough that launches, not work,
-// are what it costs (measured crossover, tools/tree_latency.py / profiles/r03_tree_level_ab.txt).  TF_TREE_NO_LEVEL: A/B switch.
+// are what it costs (measured crossover, tools/tree_latency.py / profiles/r03_tree_level_ab.txt).
 bool tree_level_wanted(long long order, long long lines, int L, bool up) {
-    static const bool off = ab_env("TF_TREE_NO_LEVEL") != nullptr;
-    static const bool on_xfe = ab_env("TF_TREE_LEVEL_XFE") != nullptr;  // measured loss, opt-in (below)
-    static const long long limit = [] {
-        const char* e = ab_env("TF_TREE_LEVEL_MAX_WORDS");
-        return e ? atoll(e) : (1ll << 22);  // (every width the latency-shaped transform serves: faster at each, profiles/r03_tree_level_ab.txt)
-    }();
-    if (off || order < 64 || order > 4096 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;
-    // XFieldElement (tree_*_level_xfe_kernel: three thread groups per line; 2d <= 2048 fits a workgroup on the way down, 2d <= 1024
-    // on the way up) is a measured LOSS and off unless TF_TREE_LEVEL_XFE is set: prepared tree, 2^12 points, evaluate 243 -> 258 us,
-    // interpolate 160 -> 201 us (profiles/r03_tree_level_ab.txt) -- the extension-field products between the transforms are up to
-    // five base-field products per element and limb, 8 elements per thread: they lengthen the one instruction stream that bounds a
-    // level, where the separate pointwise kernels spread them over one thread per element.
-    if (L == 3 && (!on_xfe || order > (up ? 1024 : 2048))) return false;
+    constexpr long long limit = 1ll << 22;  // (every width the latency-shaped transform serves: faster at each, profiles/r03_tree_level_ab.txt)
+    if (order < 64 || order > 4096 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;
+    // BFieldElement only.  XFieldElement level kernels (three thread groups per line) were a measured LOSS: prepared tree, 2^12 points,
+    // evaluate 243 -> 258 us, interpolate 160 -> 201 us (profiles/r03_tree_level_ab.txt) -- the extension-field products between the
+    // transforms are up to five base-field products per element and limb, 8 elements per thread: they lengthen the one instruction
+    // stream that bounds a level, where the separate pointwise kernels spread them over one thread per element.
+    if (L == 3) return false;
     if (!lat_wanted(ilog2((size_t)order), (size_t)lines, L)) return false;
     return lines * order * L <= limit;
 }
@@ -152,22 +128,7 @@ int launch_tree_level(DeviceCtx* ctx, int log_n, tfk::TreeLevelArgs a, hipStream
     if (!rc) rc = get_lat_table(ctx, log_n, true, &a.tw_i);
     if (rc) return rc;
     a.ninv = gl::mont_inverse(gl::to_mont(u64(1) << log_n));
-#ifdef TF_AB_BUILD
-    if (L == 3) {
-        switch (log_n) {
-            case 6: return launch_tree_level_xfe_t<6, UP>(a, s);
-            case 7: return launch_tree_level_xfe_t<7, UP>(a, s);
-            case 8: return launch_tree_level_xfe_t<8, UP>(a, s);
-            case 9: return launch_tree_level_xfe_t<9, UP>(a, s);
-            case 10: return launch_tree_level_xfe_t<10, UP>(a, s);
-            case 11:
-                if constexpr (!UP) return launch_tree_level_xfe_t<11, false>(a, s);
-        }
-        return TF_ERR_HIP;
-    }
-#else
-    if (L == 3) return TF_ERR_HIP;  // (tree_level_wanted never says yes: the XFieldElement level kernels are a measured loss, TF_AB_BUILD)
-#endif
+    if (L == 3) return TF_ERR_HIP;  // (tree_level_wanted never says yes for XFieldElement)
     switch (log_n) {
         case 6: return launch_tree_level_t<6, UP>(a, s);
         case 7: return launch_tree_level_t<7, UP>(a, s);
@@ -197,15 +158,11 @@ int launch_tree_build_level_t(const tfk::TreeBuildArgs& a, hipStream_t stream) {
     HIPCHK(hipGetLastError());
     return TF_OK;
 }
-// When: a small tree (the build of 2^12 points was 58 launches, 378 of the 655 us of a one-shot interpolation).  TF_TREE_NO_BUILD_LEVEL:
-// A/B switch; TF_TREE_BUILD_MAX_WORDS: sweep hook (words of one level's transforms, 2 M).
+// When: a small tree (the build of 2^12 points was 58 launches, 378 of the 655 us of a one-shot interpolation).
 bool tree_build_level_wanted(long long order, long long parents) {
-    static const bool off = ab_env("TF_TREE_NO_BUILD_LEVEL") != nullptr;
-    static const long long limit = [] {
-        const char* e = ab_env("TF_TREE_BUILD_MAX_WORDS");
-        return e ? atoll(e) : (1ll << 22);  // (2^16 / 2^18 words lose 7 % / 5 % on one-shot calls at 2^16 / 2^18 points; 2^20 and 2^22 level)
-    }();
-    if (off || order < 128 || order > 2048 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;
+    // words of one level's transforms (2^16 / 2^18 words lose 7 % / 5 % on one-shot calls at 2^16 / 2^18 points; 2^20 and 2^22 level)
+    constexpr long long limit = 1ll << 22;
+    if (order < 128 || order > 2048 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;
     if (g_lat_mode.load(std::memory_order_relaxed) == 0 || !lat_wanted(ilog2((size_t)order), (size_t)(2 * parents), 1)) return false;
     return 2 * parents * order <= limit;
 }
@@ -250,11 +207,8 @@ int launch_lat2_dir(int log_n, const tfk::NttLat2Args& a, size_t batch, hipStrea
         case 7: return launch_lat2_t<7, INV, LAST>(a, batch, s);
         case 8: return launch_lat2_t<8, INV, LAST>(a, batch, s);
         case 9: return launch_lat2_t<9, INV, LAST>(a, batch, s);
-        case 10: {
-            // 1024-point lines: 512-thread workgroups take four lines instead of two (32-byte segments on the column side)
-            static const bool wide = ab_env("TF_NTT_LAT2_NO_WIDE") == nullptr;  // A/B switch
-            return wide ? launch_lat2_t<10, INV, LAST, 512>(a, batch, s) : launch_lat2_t<10, INV, LAST>(a, batch, s);
-        }
+        // 1024-point lines: 512-thread workgroups take four lines instead of two (32-byte segments on the column side)
+        case 10: return launch_lat2_t<10, INV, LAST, 512>(a, batch, s);
     }
     return TF_ERR_HIP;
 }

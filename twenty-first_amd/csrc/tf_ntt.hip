@@ -108,7 +108,6 @@ int current_ctx(DeviceCtx** out) {
                 uint64_t thr = UINT64_MAX;
                 if (own) (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr);
                 int follow = 0;
-                if (const char* e = ab_env("TF_POOL_REUSE_FOLLOW_EVENTS")) follow = atoi(e);  // (to reproduce the failure)
                 (void)hipMemPoolSetAttribute(pool, hipMemPoolReuseFollowEventDependencies, &follow);
             }
             (void)hipGetLastError();
@@ -316,13 +315,11 @@ void split_powers(u64 base, int log_total, int* h_out, std::vector<u64>* hi, std
 // (table keys: tf_internal.h)
 
 // inner[g*32 + k1] = w_R^(+-g*k1) * (scale_log_n ? n^-1 : 1),  R = 32 << p2
-// pre = 2 or 4 (a = 10 only): the pass is a 2048- / 4096-point DFT run as `pre` 1024-point workgroups per tile (ntt_kernels.h, PRE2 /
-// PRE4); `pre` tables back to back, table q: inner[q * 1024 + g*32 + k1] = w_1024^(+-g k1) * w_{1024 pre}^(+-q g) * scale -- the part
-// of the radix-`pre` stage's twiddle that depends on g rides on the inner twiddle.  pre = 4: 64 more words follow,
-// stw[(q >> 1) * 32 + i] = w_128^(+-q i), q = 1, 3: the per-slot part of w_4096^(q c), c = g + 32 i (*stw_out).
-int get_inner_table(DeviceCtx* ctx, int a, bool inverse, int scale_log_n, const u64** out, int pre = 1, const u64** stw_out = nullptr) {
+// pre = 2 (a = 10 only): the pass is a 2048-point DFT run as two 1024-point workgroups per tile (ntt_kernels.h, PRE2); two tables
+// back to back, table q: inner[q * 1024 + g*32 + k1] = w_1024^(+-g k1) * w_2048^(+-q g) * scale -- the part of the radix-2 stage's
+// twiddle that depends on g rides on the inner twiddle.
+int get_inner_table(DeviceCtx* ctx, int a, bool inverse, int scale_log_n, const u64** out, int pre = 1) {
     const int p2 = a - 5;
-    if (stw_out) *stw_out = nullptr;
     if (p2 == 0 && scale_log_n == 0) {
         *out = nullptr;
         return TF_OK;
@@ -333,7 +330,6 @@ int get_inner_table(DeviceCtx* ctx, int a, bool inverse, int scale_log_n, const 
     auto it = ctx->tables.find(key);
     if (it != ctx->tables.end()) {
         *out = it->second;
-        if (stw_out && pre == 4) *stw_out = it->second + size_t(P2) * 32 * 4;
         return TF_OK;
     }
     u64 w = root_of_unity_mont(a);
@@ -351,9 +347,9 @@ int get_inner_table(DeviceCtx* ctx, int a, bool inverse, int scale_log_n, const 
         wg = gl::mont_mul(wg, w);
     }
     if (pre > 1) {
-        u64 wp = root_of_unity_mont(a + (pre == 4 ? 2 : 1));  // w_{R pre}
+        u64 wp = root_of_unity_mont(a + 1);  // w_{R pre}
         if (inverse) wp = gl::mont_inverse(wp);
-        t.resize(size_t(P2) * 32 * pre + (pre == 4 ? 64 : 0));
+        t.resize(size_t(P2) * 32 * pre);
         u64 wq = wp;  // w_{R pre}^q
         for (int q = 1; q < pre; ++q) {
             u64 wqg = gl::ONE;  // w_{R pre}^(q g)
@@ -363,24 +359,12 @@ int get_inner_table(DeviceCtx* ctx, int a, bool inverse, int scale_log_n, const 
             }
             wq = gl::mont_mul(wq, wp);
         }
-        if (pre == 4) {
-            const u64 w128 = gl::mont_pow(wp, u64(P2));  // w_{R pre}^32 = w_{R pre / 32}: w_128 for R = 1024
-            for (int h = 0; h < 2; ++h) {
-                const u64 step = gl::mont_pow(w128, u64(2 * h + 1));
-                u64 acc = gl::ONE;
-                for (int i = 0; i < 32; ++i) {
-                    t[size_t(P2) * 32 * 4 + size_t(h) * 32 + i] = acc;
-                    acc = gl::mont_mul(acc, step);
-                }
-            }
-        }
     }
     u64* d = nullptr;
     int rc = upload_table(t, &d);
     if (rc) return rc;
     ctx->tables[key] = d;
     *out = d;
-    if (stw_out && pre == 4) *stw_out = d + size_t(P2) * 32 * 4;
     return TF_OK;
 }
 
@@ -737,14 +721,7 @@ int pad_to_residue(int base, int residue) {  // smallest s >= base with s == res
 
 // Words per exchange round of a workgroup of g.wg threads (NttPlan::wg: 512, or 256 for the narrow tiles; tf_plan.hip has the
 // geometry and its measurements)
-int round_elems(const NttPlan& g) {
-    static const int v = [] {
-        const char* e = ab_env("TF_NTT_ROUND_ELEMS");
-        const int r = e ? atoi(e) : 0;
-        return r >= 1024 ? r : 0;
-    }();
-    return v ? v : g.wg * 16;
-}
+int round_elems(const NttPlan& g) { return g.wg * 16; }
 
 // thread / LDS geometry shared by all pass types: nc columns, exchanged in rounds of cpr columns
 void finish_geometry(Launch* l, int nc, int p2, const NttPlan& g) {
@@ -831,7 +808,7 @@ bool fits_buffer_offsets(const Launch& l) {
     // (a PRE2 launch also reads the partner rows, 1024 rows further; the one-workgroup 2048-point column pass, p2 = 6, spans 2048 rows
     //  on every side)
     const unsigned long long rows = l.a.p2 == 6 ? 2048ull : 1024ull;
-    return ok(l.a.in_rs, l.a.in_cs_hi, l.a.pre2_map ? (l.a.pre4_stw ? 4096ull : 2048ull) : rows) && ok(l.a.out_rs, l.a.out_cs_hi, rows) && ok(l.a.tw_rs, 0, rows);
+    return ok(l.a.in_rs, l.a.in_cs_hi, l.a.pre2_map ? 2048ull : rows) && ok(l.a.out_rs, l.a.out_cs_hi, rows) && ok(l.a.tw_rs, 0, rows);
 }
 
 // rows (independent DFTs) per tile for the passes whose columns are whole rows of elements
@@ -852,8 +829,8 @@ Launch plan_transpose_pass(const NttPlan& g, const u64* in, u64* out, long long 
                            long long Q, int L, long long split = 0, int words = 0, int pre = 1) {
     Launch l{};
     tfk::NttPassArgs& A = l.a;
-    const int p2 = a - (pre == 4 ? 2 : (pre == 2 ? 1 : 0)) - 5, P2 = 1 << p2;
-    const long long R = 1ll << a;  // elements per row (pre = 2 / 4: 2048 / 4096, transformed as two / four interleaved 1024-point classes)
+    const int p2 = a - (pre == 2 ? 1 : 0) - 5, P2 = 1 << p2;
+    const long long R = 1ll << a;  // elements per row (pre = 2: 2048, transformed as two interleaved 1024-point classes)
     int T = rows_per_tile(g, P2, L, N1);
     {
         // the kernel addresses its loads as uniform 64-bit base + 32-bit per-thread byte offset; the offset spans the
@@ -940,8 +917,7 @@ Launch plan_row_pass(const NttPlan& g, const u64* in, u64* out, long long in_bs,
     A.js_k = 1;  // single pass: output element index = k
     A.xcd_order = 0;
     finish_geometry(&l, nc, p2, g);
-    static const bool no_gfast = ab_env("TF_NTT_NO_GFAST") != nullptr;  // A/B switch
-    if (p2 >= 1 && !no_gfast) {
+    if (p2 >= 1) {
         // rows are contiguous: put the lanes along the row (8 * P2-byte pieces become P2 times longer).  Exchange layout
         // idx = k1 * s1 + cc * P2 + g with s1 = 1 (mod 32): a half-wave writes 32 consecutive words and reads
         // g' * s1 + cc * P2 = g' + cc * P2 (mod 32), all different.
@@ -971,15 +947,15 @@ int ensure_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long
     return TF_OK;
 }
 
-template <bool INV, int SCALE, int MODE, bool LAST1024 = false, bool R1024 = false, bool COL = false, bool PRE2 = false, bool PRE4 = false>
+template <bool INV, int SCALE, bool LAST1024 = false, bool R1024 = false, bool COL = false, bool PRE2 = false>
 int launch_pass_t(const Launch& l, hipStream_t stream) {
     // one attribute call per (instantiation, device): the kernels use up to the full 160 KiB of dynamic LDS
     static std::atomic<unsigned long long> done_mask{0};
-    if (int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::ntt_pass_kernel<INV, SCALE, MODE, LAST1024, R1024, COL, PRE2, PRE4>), (int)(160 * 1024), done_mask)) return rc_attr;
+    if (int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::ntt_pass_kernel<INV, SCALE, LAST1024, R1024, COL, PRE2>), (int)(160 * 1024), done_mask)) return rc_attr;
     // the R = 1024 column-pass instantiation stages its inner twiddle table behind the exchange buffer (LAST1024: part of
     // kLast1024LdsBytes already)
-    const size_t lds_bytes = l.lds_bytes + ((TF_LDS_TW && !LAST1024 && MODE == 0 && l.a.inner_tw) ? (size_t(1) << l.a.p2) * tfk::kLdsTwStride * sizeof(u64) : 0);
-    hipLaunchKernelGGL((tfk::ntt_pass_kernel<INV, SCALE, MODE, LAST1024, R1024, COL, PRE2, PRE4>), dim3(l.tiles), dim3(l.threads), lds_bytes, stream,
+    const size_t lds_bytes = l.lds_bytes + ((TF_LDS_TW && !LAST1024 && l.a.inner_tw) ? (size_t(1) << l.a.p2) * tfk::kLdsTwStride * sizeof(u64) : 0);
+    hipLaunchKernelGGL((tfk::ntt_pass_kernel<INV, SCALE, LAST1024, R1024, COL, PRE2>), dim3(l.tiles), dim3(l.threads), lds_bytes, stream,
                        l.a);
     HIPCHK(hipGetLastError());
     return TF_OK;
@@ -996,38 +972,6 @@ int launch_col2048_t(const Launch& l, hipStream_t stream) {
     return TF_OK;
 }
 
-#ifdef TF_AB_BUILD
-// the R = 1024 column pass as a chain of `k` tiles per workgroup with the next tile's loads inside the store phase
-// (ntt_col1024_chain_kernel); k from TF_NTT_PERSIST / tf_set_ntt_chain (0 or 1: the one-tile kernel)
-std::atomic<int> g_chain{-1};
-int chain_tiles() {
-    int v = g_chain.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = ab_env("TF_NTT_PERSIST");
-        v = e ? std::max(0, atoi(e)) : 0;
-        g_chain.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-template <bool INV>
-int launch_chain_t(const Launch& l, int k, hipStream_t stream) {
-    static std::atomic<unsigned long long> done_mask{0};
-    if (int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::ntt_col1024_chain_kernel<INV>), (int)(160 * 1024), done_mask)) return rc_attr;
-    const size_t lds_bytes = l.lds_bytes + size_t(32) * tfk::kLdsTwStride * sizeof(u64);
-    unsigned grid = (l.tiles + (unsigned)k - 1) / (unsigned)k;
-    grid = (grid + 7u) & ~7u;  // block id mod 8 is the XCD: tile, tile + grid, ... stay on one XCD
-    grid = std::min(grid, l.tiles);
-    hipLaunchKernelGGL((tfk::ntt_col1024_chain_kernel<INV>), dim3(grid), dim3(512), lds_bytes, stream, l.a, l.tiles, (unsigned)k);
-    HIPCHK(hipGetLastError());
-    return TF_OK;
-}
-#else
-constexpr int chain_tiles() { return 0; }  // (ntt_col1024_chain_kernel: a measured loss, laboratory build only)
-#endif
-
-#ifdef TF_AB_BUILD
-unsigned long long* g_dbg_buf = nullptr;  // TF_NTT_ABLATE=3: per-wave phase stamps of the last launch (tf_debug_stamps)
-#endif
 constexpr size_t kLast1024LdsBytes = (size_t(tfk::kL1024ExchangeWords) + (TF_LDS_TW ? 32 * tfk::kLdsTwStride : 0)) * sizeof(u64);
 
 int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
@@ -1036,7 +980,6 @@ int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
         t_last_error = "NTT planner self-check failed (thread-to-column division is not exact for this geometry)";
         return TF_ERR_HIP;
     }
-    const int g_ablate = ablate_mode();
     if (l.a.p2 == 5 && !l.a.inner_tw) {  // the R = 1024 instantiations run lazy networks and rely on the product that follows
         t_last_error = "internal: R = 1024 pass without its inner twiddle table";
         return TF_ERR_HIP;
@@ -1047,14 +990,14 @@ int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
     const bool std_geo = l.threads == 512 && l.a.nc == tfk::kR1024Nc && l.a.cpr == tfk::kR1024Cpr && l.a.nrounds == tfk::kR1024Rounds &&
                          l.a.s1 == tfk::kR1024S1 && l.a.s2 == tfk::kR1024Cpr && l.a.s3 == 1 && !l.a.gfast;
     const bool plain_last1024 = l.a.p2 == 5 && !l.a.post_tw && !l.a.gfast && !l.a.pre_scale && l.a.n_coeffs < 0 && !l.a.in2 &&
-                                (!l.a.post_scale || (inverse && scaled_last1024_enabled())) && last1024_enabled(l.narrow) && fits;
+                                (!l.a.post_scale || inverse) && !l.narrow && fits;
     if (l.a.p2 == 6) {
         // a 2048-point column pass in ONE workgroup of 2048 rows x 8 word-columns (ntt_kernels.h, ntt_col2048_kernel): planned by
         // run_ntt only, with exactly the geometry the kernel's immediates assume
         const bool geo = l.threads == 512 && l.a.nc == tfk::kC8Nc && l.a.cpr == tfk::kC8Cpr && l.a.nrounds == tfk::kC8Rounds && l.a.s1 == tfk::kC8S1 &&
                          l.a.s2 == tfk::kC8Cpr && l.a.s3 == 1 && !l.a.gfast && !l.a.wtiles;
         const bool load_work = l.a.pre_scale || l.a.n_coeffs >= 0;
-        if (!geo || !fits || g_ablate || !l.a.post_tw || !l.a.inner_tw || l.a.in2 || l.a.n_out >= 0 || l.a.post_scale || l.a.pre2_map ||
+        if (!geo || !fits || !l.a.post_tw || !l.a.inner_tw || l.a.in2 || l.a.n_out >= 0 || l.a.post_scale || l.a.pre2_map ||
             (load_work && inverse) || (l.a.pre_scale && l.a.ps_col)) {
             t_last_error = "internal: one-workgroup 2048-point column pass outside the shapes it supports";
             return TF_ERR_HIP;
@@ -1062,41 +1005,24 @@ int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
         if (load_work) return launch_col2048_t<false, 1>(l, stream);
         return inverse ? launch_col2048_t<true, 0>(l, stream) : launch_col2048_t<false, 0>(l, stream);
     }
-    if (l.a.pre2_map && l.a.pre4_stw) {
-        // a 4096-point last pass as four 1024-point classes per tile (ntt_kernels.h, PRE4): forward, plain, planned by run_ntt only
-        if (l.a.p2 != 5 || !fits || g_ablate || l.a.in2 || l.a.n_out >= 0 || l.a.gfast || l.a.post_tw || l.a.pre_scale || l.a.n_coeffs >= 0 ||
-            l.a.post_scale || inverse || l.a.col_shift0 || l.a.col_shift_i0) {
-            t_last_error = "internal: radix-4 last pass (PRE4) launch outside the shapes it supports";
-            return TF_ERR_HIP;
-        }
-#ifdef TF_AB_BUILD
-        Launch l2 = l;
-        l2.lds_bytes = std::max(l.lds_bytes, kLast1024LdsBytes);
-        l2.threads = 512;
-        return launch_pass_t<false, 0, 0, true, false, false, false, true>(l2, stream);
-#else
-        t_last_error = "internal: radix-4 last pass (PRE4) planned in the product build";
-        return TF_ERR_HIP;
-#endif
-    }
     if (l.a.pre2_map) {
         // a 2048-point pass as two 1024-point halves per tile (ntt_kernels.h, PRE2): only planned by run_ntt when all of this holds
         const bool column = l.a.post_tw != nullptr;
-        if (l.a.p2 != 5 || !fits || g_ablate || l.a.in2 || l.a.n_out >= 0 || l.a.gfast || (column && !std_geo) ||
+        if (l.a.p2 != 5 || !fits || l.a.in2 || l.a.n_out >= 0 || l.a.gfast || (column && !std_geo) ||
             (!column && (l.a.pre_scale || l.a.n_coeffs >= 0)) || (l.a.post_scale && (column || !inverse)) ||
             ((l.a.pre_scale || l.a.n_coeffs >= 0) && inverse)) {
             t_last_error = "internal: two-pass (PRE2) launch outside the shapes it supports";
             return TF_ERR_HIP;
         }
         if (column) {
-            if (l.a.pre_scale || l.a.n_coeffs >= 0) return launch_pass_t<false, 1, 0, false, true, false, true>(l, stream);
-            return inverse ? launch_pass_t<true, 0, 0, false, true, false, true>(l, stream) : launch_pass_t<false, 0, 0, false, true, false, true>(l, stream);
+            if (l.a.pre_scale || l.a.n_coeffs >= 0) return launch_pass_t<false, 1, false, true, false, true>(l, stream);
+            return inverse ? launch_pass_t<true, 0, false, true, false, true>(l, stream) : launch_pass_t<false, 0, false, true, false, true>(l, stream);
         }
         Launch l2 = l;
         l2.lds_bytes = std::max(l.lds_bytes, kLast1024LdsBytes);
         l2.threads = 512;
-        if (l.a.post_scale) return launch_pass_t<true, 2, 0, true, false, false, true>(l2, stream);
-        return inverse ? launch_pass_t<true, 0, 0, true, false, false, true>(l2, stream) : launch_pass_t<false, 0, 0, true, false, false, true>(l2, stream);
+        if (l.a.post_scale) return launch_pass_t<true, 2, true, false, false, true>(l2, stream);
+        return inverse ? launch_pass_t<true, 0, true, false, false, true>(l2, stream) : launch_pass_t<false, 0, true, false, false, true>(l2, stream);
     }
     if ((l.a.n_out >= 0 || l.a.col_shift0 || l.a.col_shift_i0) && !plain_last1024) {  // anything else would overrun the caller's buffer
         t_last_error = "internal: truncated output or shifted tiles requested from a pass that does not support them";
@@ -1105,52 +1031,37 @@ int launch_pass(const Launch& l, bool inverse, hipStream_t stream) {
     if (l.a.pre_scale || l.a.n_coeffs >= 0 || l.a.in2) {
         // work on load: coset scaling, zero padding, or the pointwise product with a second operand (forward or inverse;
         // constant-P2 variant for a forward first pass with R = 1024)
-        static const bool no_r1024_scale = ab_env("TF_NTT_NO_R1024") != nullptr;
-        if (inverse) return launch_pass_t<true, 1, 0>(l, stream);
-        if (l.a.p2 == 5 && l.a.post_tw && !no_r1024_scale && fits && std_geo) return launch_pass_t<false, 1, 0, false, true>(l, stream);
-        if (l.a.post_tw && fits && !l.a.gfast && col_enabled()) return launch_pass_t<false, 1, 0, false, false, true>(l, stream);
-        return launch_pass_t<false, 1, 0>(l, stream);
+        if (inverse) return launch_pass_t<true, 1>(l, stream);
+        if (l.a.p2 == 5 && l.a.post_tw && fits && std_geo) return launch_pass_t<false, 1, false, true>(l, stream);
+        if (l.a.post_tw && fits && !l.a.gfast) return launch_pass_t<false, 1, false, false, true>(l, stream);
+        return launch_pass_t<false, 1>(l, stream);
     }
     if (l.a.post_scale) {  // coset interpolation: inverse, scale on store
         if (plain_last1024) {  // R = 1024 last pass: the specialised kernel with the multiplication in its fused tail
             Launch l2 = l;
             l2.lds_bytes = std::max(l.lds_bytes, kLast1024LdsBytes);
             l2.threads = 512;
-            return launch_pass_t<true, 2, 0, true>(l2, stream);
+            return launch_pass_t<true, 2, true>(l2, stream);
         }
-        return launch_pass_t<true, 2, 0>(l, stream);
+        return launch_pass_t<true, 2>(l, stream);
     }
     // last pass of a plain transform with R = 1024: specialised kernel (constant P2, stores fused with level 5)
     // (not for single-pass transforms: their stores run along the row as well, which only the gfast roles give -- 1.05 vs 1.20 ms)
-    const bool last1024 = l.a.p2 == 5 && !l.a.post_tw && last1024_enabled(l.narrow) && !l.a.gfast && fits;
-    static const bool no_r1024 = ab_env("TF_NTT_NO_R1024") != nullptr;  // A/B switch
-    const bool r1024 = l.a.p2 == 5 && l.a.post_tw && g_ablate == 0 && !no_r1024 && fits && std_geo;  // column pass with R = 1024
+    const bool last1024 = l.a.p2 == 5 && !l.a.post_tw && !l.narrow && !l.a.gfast && fits;
+    const bool r1024 = l.a.p2 == 5 && l.a.post_tw && fits && std_geo;  // column pass with R = 1024
     if (last1024) {  // this instantiation lays its exchange buffer out itself (32 x 289 words, ntt_kernels.h)
         Launch l2 = l;
         l2.lds_bytes = std::max(l.lds_bytes, kLast1024LdsBytes);
         l2.threads = 512;  // 16 column slots x 32, also for tiles of 15 word-columns (XFE)
-        return inverse ? launch_pass_t<true, 0, 0, true>(l2, stream) : launch_pass_t<false, 0, 0, true>(l2, stream);
+        return inverse ? launch_pass_t<true, 0, true>(l2, stream) : launch_pass_t<false, 0, true>(l2, stream);
     }
     // any other column pass whose offsets fit: the same treatment with a run-time P2 (COL)
-    const bool col = l.a.post_tw && !r1024 && fits && !l.a.gfast && g_ablate == 0 && col_enabled();
-#ifdef TF_AB_BUILD
-    if (r1024 && chain_tiles() > 1 && l.tiles >= 1024 && !l.a.dbg)
-        return inverse ? launch_chain_t<true>(l, chain_tiles(), stream) : launch_chain_t<false>(l, chain_tiles(), stream);
-#endif
-    if (inverse) return r1024 ? launch_pass_t<true, 0, 0, false, true>(l, stream)
-                              : (col ? launch_pass_t<true, 0, 0, false, false, true>(l, stream) : launch_pass_t<true, 0, 0>(l, stream));
-    if (r1024) return launch_pass_t<false, 0, 0, false, true>(l, stream);
-    if (col) return launch_pass_t<false, 0, 0, false, false, true>(l, stream);
-#ifdef TF_AB_BUILD
-    if (g_ablate == 1) return launch_pass_t<false, 0, 1>(l, stream);
-    if (g_ablate == 2) return launch_pass_t<false, 0, 2>(l, stream);
-    if (g_ablate == 3) {
-        Launch l2 = l;
-        l2.a.dbg = g_dbg_buf;
-        return launch_pass_t<false, 0, 3>(l2, stream);
-    }
-#endif
-    return launch_pass_t<false, 0, 0>(l, stream);
+    const bool col = l.a.post_tw && !r1024 && fits && !l.a.gfast;
+    if (inverse) return r1024 ? launch_pass_t<true, 0, false, true>(l, stream)
+                              : (col ? launch_pass_t<true, 0, false, false, true>(l, stream) : launch_pass_t<true, 0>(l, stream));
+    if (r1024) return launch_pass_t<false, 0, false, true>(l, stream);
+    if (col) return launch_pass_t<false, 0, false, false, true>(l, stream);
+    return launch_pass_t<false, 0>(l, stream);
 }
 
 int check_len(size_t n) {
@@ -1158,18 +1069,6 @@ int check_len(size_t n) {
     if (n > (size_t(1) << 31)) return TF_ERR_LEN_TOO_LARGE;           // ntt.rs:134-139: lengths beyond u32::MAX panic
     return TF_OK;
 }
-
-#ifdef TF_AB_BUILD
-// n = 32, contiguous transforms: LDS-staged rows (ntt_rows32_kernel)
-template <bool INV>
-int launch_rows32_t(const tfk::NttRows32Args& a, unsigned grid, hipStream_t stream) {
-    static std::atomic<unsigned long long> done_mask{0};
-    if (int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::ntt_rows32_kernel<INV>), (int)(160 * 1024), done_mask)) return rc_attr;
-    hipLaunchKernelGGL((tfk::ntt_rows32_kernel<INV>), dim3(grid), dim3(512), size_t(256) * 33 * sizeof(u64), stream, a);
-    HIPCHK(hipGetLastError());
-    return TF_OK;
-}
-#endif
 
 // n <= 32: wave-private tiles (ntt_rows32w_kernel), a grid-stride walk of two workgroups per CU
 template <bool INV, int L, int LOGN>
@@ -1196,25 +1095,6 @@ int launch_rows32w_n(const tfk::NttRows32Args& a, unsigned grid, int log_n, hipS
 
 // batch contiguous transforms of n = 2^log_n <= 32 points (BFieldElement: <= 64)
 int launch_rows32(const u64* in, u64* out, size_t batch, int L, int log_n, bool inverse, hipStream_t stream) {
-#ifdef TF_AB_BUILD
-    if (log_n == 5 && ab_env("TF_NTT_ROWS32_WG")) {  // round 2's workgroup-tile kernel (1.21 vs 0.87 ms per 2^28 words, profiles/r05_rows32_ab.txt)
-        const size_t per_tile = L == 1 ? 512 : 170;
-        const size_t max_grid = size_t(1) << 30;
-        for (size_t b0 = 0; b0 < batch; b0 += max_grid * per_tile) {
-            const size_t nb = std::min(batch - b0, max_grid * per_tile);
-            tfk::NttRows32Args a{};
-            a.in = in + b0 * 32 * L;
-            a.out = out + b0 * 32 * L;
-            a.total_transforms = (long long)nb;
-            a.scale = inverse ? gl::mont_inverse(gl::to_mont(32)) : 0;
-            a.L = L;
-            const unsigned grid = (unsigned)((nb + per_tile - 1) / per_tile);
-            int rc = inverse ? launch_rows32_t<true>(a, grid, stream) : launch_rows32_t<false>(a, grid, stream);
-            if (rc) return rc;
-        }
-        return TF_OK;
-    }
-#endif
     const int cus = device_cus();
     tfk::NttRows32Args a{};
     a.in = in;
@@ -1421,35 +1301,27 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
     const int P = plan.P, L = c.L, log_n = c.log_n;
     const int (&a)[4] = plan.a;
     const bool (&pre2)[4] = plan.pre2;
-    const bool inverse = c.inverse, c8 = plan.c8, pre4_last = plan.pre4_last;
+    const bool inverse = c.inverse, c8 = plan.c8;
     const size_t n = c.n, cosets = c.cosets;
     const long long n_coeffs = c.n_coeffs, n_out = c.n_out;
     const u64 *const pre_scale = c.pre_scale, *const post_scale = c.post_scale;
-    const u64* pre4_stw = nullptr;
     const u64* inner[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < P; ++i) {
-        const bool p4 = pre4_last && i == P - 1;
-        TRY(get_inner_table(ctx, (pre2[i] || p4) ? 10 : a[i], inverse, (i == P - 1 && inverse) ? log_n : 0, &inner[i], p4 ? 4 : (pre2[i] ? 2 : 1),
-                            p4 ? &pre4_stw : nullptr));  // n^-1 rides on the last pass
-    }
+    for (int i = 0; i < P; ++i)
+        TRY(get_inner_table(ctx, pre2[i] ? 10 : a[i], inverse, (i == P - 1 && inverse) ? log_n : 0, &inner[i], pre2[i] ? 2 : 1));  // n^-1 rides on the last pass
     const u64* post[3] = {nullptr, nullptr, nullptr};
-    const u64* post_u = nullptr;  // the plain table beside a scaled post[0] (one-workgroup scaling first pass)
     // tables too large to cache: given back on the caller's stream when the call returns, behind the join of the tile streams
-    DevTemp post_own[3] = {DevTemp(c.stream), DevTemp(c.stream), DevTemp(c.stream)}, post_u_own(c.stream);
+    DevTemp post_own[3] = {DevTemp(c.stream), DevTemp(c.stream), DevTemp(c.stream)};
     {
         int rest = log_n;
         for (int i = 0; i + 1 < P; ++i) {
-            if (i == 0 && c8 && pre_scale) {
-                // the scaled table for every thread's own row, the plain one for the rows all threads share (ntt_col2048_kernel, TF_C8_UV)
+            if (i == 0 && c8 && pre_scale) {  // the table with offset^b folded in (ntt_col2048_kernel)
                 TRY(get_scaled_post_table(ctx, rest, a[i], *c.coset_offset, c.stream, &post[i], &post_own[i]));
-                TRY(get_post_table(ctx, rest, a[i], inverse, c.stream, &post_u, &post_u_own));
             } else {
                 TRY(get_post_table(ctx, rest, a[i], inverse, c.stream, &post[i], &post_own[i]));
             }
             rest -= a[i];
         }
     }
-    static const bool no_col_shift = ab_env("TF_NTT_NO_COL_SHIFT") != nullptr;  // A/B switch
     const size_t poly_bytes = n * cosets * size_t(L) * sizeof(u64), tb = plan.tb;
     // pipelined tiles: tile t runs on side stream t % K with scratch tile t % K; the caller's stream forks into the side streams
     // before the first tile and joins them after the last
@@ -1496,12 +1368,10 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
             Launch p = plan_column_pass(plan, src, dst, src_bs, dst_bs, nb, (i == 0) ? (long long)cosets : outer, a[i], B, L, pre2[i]);
             p.a.inner_tw = inner[i];
             p.a.post_tw = post[i];
-            p.a.post_tw_u = (i == 0 && post_u) ? post_u : nullptr;
             if (pre2[i]) {
                 // partner coefficients are n / 2 apart: offset^(n/2) is word n / 2 of the scale table when the polynomial is that long
                 p.a.pre2_cp = pre_scale ? pre_scale + ((long long)(n / 2) < n_coeffs ? (long long)(n / 2) : 0) : nullptr;
             }
-            if (i == 0 && src != dst) p.a.nt = g_nt.load(std::memory_order_relaxed) & 1;  // the caller's input is read once
             if (i == 0) {
                 p.a.pre_scale = pre_scale;
                 if (c8 && pre_scale) p.a.ps_col = 0;  // the column part offset^b of the scaling comes with the inter-pass table
@@ -1524,13 +1394,11 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
         if (P < 4) {
             // (plan.words: XFieldElement rows in word-granular tiles, whole 128-byte lines on the output side)
             Launch pl = plan_transpose_pass(plan, scratch, tout, sbs, c.out_bs, nb, a[P - 1], N[0] * (long long)cosets, P == 3 ? N[1] : 1, L, 0,
-                                            plan.words, pre4_last ? 4 : (pre2[P - 1] ? 2 : 1));
+                                            plan.words, pre2[P - 1] ? 2 : 1);
             pl.a.inner_tw = inner[P - 1];
-            pl.a.pre4_stw = pre4_last ? pre4_stw : nullptr;
             pl.a.post_scale = post_scale;
             pl.a.n_out = n_out;
-            pl.a.nt = g_nt.load(std::memory_order_relaxed) & 2;  // the result is written once
-            if (plan.plain1024 && !pre4_last && pl.a.nc == 16 && !no_col_shift && (unsigned long long)n * L * sizeof(u64) < (1ull << 32)) {
+            if (plan.plain1024 && pl.a.nc == 16 && (unsigned long long)n * L * sizeof(u64) < (1ull << 32)) {
                 // The R = 1024 last pass stores 128-byte segments of 16 adjacent output words.  When the output of batch entry
                 // b does not start on a cache line (a truncated product: stride n_out = na + nb - 1 words, or a caller's
                 // unaligned pointer) every segment would straddle two lines written by workgroups on different XCDs: shift

@@ -18,7 +18,6 @@ size_t g_tile_bytes = 0;
 // each with its own scratch tile, so that the column pass of tile t + 1 runs beside the transposing pass of tile t: the
 // launches' tails fill each other and a tile sized for the 256 MiB Infinity Cache is re-read out of it.  1 = one stream.
 std::atomic<int> g_pipe{0};
-std::atomic<int> g_nt{-1};  // TF_NTT_NT / tf_set_ntt_nt: bit 0 non-temporal input loads (first pass), bit 1 non-temporal output stores (last pass)
 std::once_flag g_env_once;
 void read_env() {
     std::call_once(g_env_once, [] {
@@ -31,107 +30,47 @@ void read_env() {
             const char* s = getenv("TF_NTT_PIPE");
             if (s && atoi(s) > 0) g_pipe.store(std::min(atoi(s), kMaxPipe));
         }
-        if (g_nt.load() < 0) {
-            const char* s = ab_env("TF_NTT_NT");
-            g_nt.store(s ? (atoi(s) & 3) : 0);
-        }
     });
 }
 
-// ------------------------------------------------------------------------------------ test hooks and A/B switches
+// ------------------------------------------------------------------------------------ test hooks
 std::atomic<int> g_min_passes{0};          // tf_set_ntt_min_passes
-std::atomic<int> g_lat_mode{-1};           // tf_set_ntt_latency_kernel: -1 automatic (TF_NTT_NO_LAT disables), 0 never, 1 whenever the shape allows
-std::atomic<int> g_pre2_mode{-1};          // tf_set_ntt_two_pass: -1 automatic (TF_NTT_NO_PRE2 disables), 0 never, 1 whenever supported (pairs), 3 (one-workgroup first pass)
+std::atomic<int> g_lat_mode{-1};           // tf_set_ntt_latency_kernel: -1 automatic, 0 never, 1 whenever the shape allows
+std::atomic<int> g_pre2_mode{-1};          // tf_set_ntt_two_pass: -1 automatic, 0 never, 1 or 2 whenever supported (pairs), 3 (one-workgroup first pass)
 std::atomic<int> g_small_launch_mode{-1};  // tf_set_ntt_small_launch: -1 automatic, 0 never, 1 always (tests)
 
-// Experiment switches for tools/split3.py: looked up on every call only when TF_NTT_EXPERIMENT is set at load time
-// (the sweep tool changes them while the process runs); otherwise the planner never touches the environment.
-const char* exp_env(const char* name) {
-    static const bool enabled = ab_env("TF_NTT_EXPERIMENT") != nullptr;
-    return enabled ? ab_env(name) : nullptr;
-}
-
-#ifdef TF_AB_BUILD
-std::atomic<int> g_ablate_cfg{-1};  // measurement only (TF_NTT_ABLATE=1|2 selects an ablated forward kernel; results are then garbage)
-int ablate_mode() {
-    int v = g_ablate_cfg.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = ab_env("TF_NTT_ABLATE");
-        v = e ? atoi(e) : 0;
-        g_ablate_cfg.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-#endif
-
-// the specialised R = 1024 last-pass kernel (LAST1024) is available unless an A/B switch or an ablation run disables it, or the
-// call is planned with the narrow tiles (which take the generic last pass, below)
-bool last1024_enabled(bool narrow) {
-    static const bool off = ab_env("TF_NTT_NO_LAST1024") != nullptr;
-    return !off && ablate_mode() == 0 && !narrow;
-}
-
-bool col_enabled() {
-    static const bool off = ab_env("TF_NTT_NO_COL") != nullptr;  // A/B switch
-    return !off;
-}
-
-// ... and its variant that multiplies on store (fast_coset_interpolate)
-bool scaled_last1024_enabled() {
-    static const bool off = ab_env("TF_NTT_NO_SCALED_LAST1024") != nullptr;  // A/B switch
-    return !off;
-}
-
 // ------------------------------------------------------------------------------------ workgroup geometry
-// Workgroup geometry (tunable for A/B runs through TF_NTT_WG_THREADS = 256 | 512):
+// Workgroup geometry:
 //   512 threads: 16 columns per tile (128-byte segments), 64 KiB exchange rounds, 2 workgroups per CU;
 //   256 threads:  8 columns per tile (64-byte segments, adjacent tiles paired on one XCD), 32 KiB rounds, 4 per CU.
 // A call with too little work to fill the chip with 512-thread tiles (a single slice of <= 2^20 points: 64 tiles for 256 CUs) is
 // planned with 256-thread workgroups and the generic last pass instead -- twice as many tiles of half the width: 2^16 44 -> 37 us,
 // 2^18 47.5 -> 39.7, 2^20 51.8 -> 43.8 us per call; from 2^22 words per call on the wide tiles win (tools/small_batch.py).
 // plan_ntt decides per call (NttPlan::wg, NttPlan::narrow) and the width travels with the plan.
-static int wg_env() {
-    static const int v = [] {
-        const char* e = ab_env("TF_NTT_WG_THREADS");
-        return (e && atoi(e) == 256) ? 256 : ((e && atoi(e) == 512) ? 512 : 0);
-    }();
-    return v;
-}
 
 // Whether a multi-pass call is planned with the narrow (256-thread) tiles: too little work to fill the chip with 512-thread ones;
 // a truncating call keeps the R = 1024 last pass its caller planned for.
 static bool small_launch_for(const NttShape& s) {
     const int small_mode = g_small_launch_mode.load(std::memory_order_relaxed);
-    static const bool no_small = ab_env("TF_NTT_NO_SMALL_LAUNCH") != nullptr;  // A/B switch
     const bool small_call = (unsigned long long)s.n * s.cosets * s.batch * s.L <= (1ull << 21);
-    return s.n_out < 0 && !wg_env() && (small_mode == 1 || (small_mode < 0 && small_call && !no_small));
+    return s.n_out < 0 && (small_mode == 1 || (small_mode < 0 && small_call));
 }
 
 // ------------------------------------------------------------------------------------ the latency-shaped kernels
 // When: the call holds too little work to fill the chip with 32-element threads (measured crossover, tools/lat_sweep.py).
 bool lat_wanted(int log_n, size_t batch, int L) {
-    static const bool off = ab_env("TF_NTT_NO_LAT") != nullptr;  // A/B switch
     // measured crossover against the pass / block kernels (tools/lat_sweep.py, profiles/r03_lat_sweep_*.txt): 2.0 - 2.9 x faster up
     // to 2^20 words per call, level at 2^22 words (BFieldElement) / 1.5 x 2^20 words (XFieldElement: its loads step 24 bytes)
-    static const long long env_limit = [] {
-        const char* e = ab_env("TF_NTT_LAT_MAX_WORDS");
-        return e ? atoll(e) : 0ll;
-    }();
-    const long long limit = env_limit ? env_limit : (L == 1 ? (1ll << 22) : (3ll << 19));
+    const long long limit = L == 1 ? (1ll << 22) : (3ll << 19);
     const int mode = g_lat_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || (mode < 0 && off)) return false;
+    if (mode == 0) return false;
     if (log_n < 6 || log_n > 12) return false;
     if (mode == 1) return true;
     return (long long)(batch * size_t(L)) << log_n <= limit;
 }
 bool lat2_wanted(int log_n, size_t batch, int L) {
-    static const bool off = ab_env("TF_NTT_NO_LAT") != nullptr || ab_env("TF_NTT_NO_LAT2") != nullptr;  // A/B switches
-    static const long long env_limit = [] {
-        const char* e = ab_env("TF_NTT_LAT2_MAX_WORDS");
-        return e ? atoll(e) : 0ll;
-    }();
     const int mode = g_lat_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || (mode < 0 && off)) return false;
+    if (mode == 0) return false;
     if (log_n < 13 || log_n > 20) return false;
     if (mode == 1) return true;
     // measured crossover against the pass / block kernels, words per call (tools/lat_sweep.py 13 20, profiles/r03_lat2_sweep_*.txt):
@@ -139,7 +78,7 @@ bool lat2_wanted(int log_n, size_t batch, int L) {
     // leaves two lines per workgroup: 16-byte segments)
     static const long long lim1[8] = {1ll << 21, 1ll << 21, 1ll << 21, 1ll << 21, 1ll << 21, 1ll << 20, 1ll << 20, 1ll << 20};  // log_n = 13 .. 20
     static const long long lim3[8] = {3ll << 20, 3ll << 20, 3ll << 19, 3ll << 20, 3ll << 19, 3ll << 18, 0, 0};
-    const long long limit = env_limit ? env_limit : (L == 1 ? lim1 : lim3)[log_n - 13];
+    const long long limit = (L == 1 ? lim1 : lim3)[log_n - 13];
     return (long long)(batch * size_t(L)) << log_n <= limit;
 }
 
@@ -155,10 +94,10 @@ int pass_count(int log_n) {  // global passes of a transform with log_n > 10
 void choose_split(int log_n, int P, int L, int (&a)[4]) {
     // The last pass gets the largest radix it can (R = 1024 whenever possible: the specialised kernel with constant P2
     // and stores fused into level 5, 128-byte output segments); the column passes share the rest evenly, larger first.
-    // Measured against the even split (tools/split3.py, 2^28 words per call): 2^15 1.92 vs 2.62 ms, 2^18 2.20 vs 2.48,
+    // Measured against the even split (2^28 words per call): 2^15 1.92 vs 2.62 ms, 2^18 2.20 vs 2.48,
     // 2^22 3.18 vs 3.49, 2^24 3.31 vs 4.15, 2^26 3.58 vs 3.99.
     // XFieldElement slices (L = 3) follow the same rule for n = 2^15, 2^20 and n >= 2^23 now that the R = 1024 kernel tiles
-    // their rows by whole 128-byte lines (tools/xfe_sweep.sh: 2^15 1.62 vs 1.83 ms, 2^23 2.62 vs 2.71, 2^25 2.71 vs 2.86 per
+    // their rows by whole 128-byte lines (a sweep of the last radix: 2^15 1.62 vs 1.83 ms, 2^23 2.62 vs 2.71, 2^25 2.71 vs 2.86 per
     // 3 * 2^26 words); the sweep still prefers R = 32 for n < 2^15 and R = 512 for 2^16 .. 2^19 (all within 1 % of R = 1024).
     int last = std::min(10, log_n - 5 * (P - 1));
     // (round 5, profiles/r05_xfe_split2_sweep.txt: 2^13 has no better split than (8, 5) -- 1.61 ms against 1.61-1.75 for every other --
@@ -167,13 +106,13 @@ void choose_split(int log_n, int P, int L, int (&a)[4]) {
     a[P - 1] = last;
     int rest = log_n - last;
     if (P == 3 && last == 10 && log_n <= (L == 3 ? 25 : 23)) {
-        // (log_n - 15, 5, 10): an exchange-free radix-32 pass in the middle (tools/split3.py: XFE 2^21 2.26 vs 2.33 ms,
+        // (log_n - 15, 5, 10): an exchange-free radix-32 pass in the middle (XFE 2^21 2.26 vs 2.33 ms,
         // 2^23 2.34 vs 2.45, 2^25 2.49 vs 2.51 per 3 * 2^26 words; BFE 2^22 2.90 vs 3.04, 2^23 3.01 vs 3.09 per 2^28)
         a[1] = 5;
         a[0] = rest - 5;
         // BFieldElement 2^21 / 2^22: the radix-32 pass first, (5, log_n - 15, 10) -- since the column passes run lazy networks
         // through buffer addressing (COL) the order matters only there: 2^21 2.49 vs 2.71 ms, 2^22 2.54 vs 2.59 ms per 2^28
-        // words; from 2^23 on and for XFieldElement slices both orders measure the same (tools/split3_ab.py)
+        // words; from 2^23 on and for XFieldElement slices both orders measure the same
         if (L == 1 && log_n <= 22) a[0] = 5, a[1] = rest - 5;
     } else {
         for (int i = 0; i + 1 < P; ++i) {
@@ -181,57 +120,19 @@ void choose_split(int log_n, int P, int L, int (&a)[4]) {
             rest -= a[i];
         }
     }
-    if (const char* e2 = exp_env("TF_NTT_SPLIT2")) {  // experiment: a0 for two-pass plans
-        const int x0 = atoi(e2);
-        if (P == 2 && x0 >= 5 && x0 <= 10 && log_n - x0 >= 5 && log_n - x0 <= 10) a[0] = x0, a[1] = log_n - x0;
-    }
-    if (const char* e = exp_env("TF_NTT_SPLIT3")) {  // experiment: "a0,a1" for three-pass plans
-        int x0 = 0, x1 = 0;
-        if (P == 3 && sscanf(e, "%d,%d", &x0, &x1) == 2 && x0 >= 5 && x0 <= 10 && x1 >= 5 && x1 <= 10 && log_n - x0 - x1 >= 5 &&
-            log_n - x0 - x1 <= 10) {
-            a[0] = x0, a[1] = x1, a[2] = log_n - x0 - x1;
-        }
-    }
 }
 
 // Two-pass plans for 2^21 / 2^22 points (a 2048-point pass = pairs of 1024-point workgroups, ntt_kernels.h PRE2).  Plain
 // transforms, coset evaluation (forward) and coset interpolation (inverse), on the wide tiles only (g: the call's geometry).
-#ifndef TF_C8_DEFAULT
-#define TF_C8_DEFAULT 1
-#endif
-constexpr bool kC8Default = TF_C8_DEFAULT != 0;
 static bool pre2_plan_ok(const NttShape& s, int log_n, const NttPlan& g) {
-    static const bool off = ab_env("TF_NTT_NO_PRE2") != nullptr;  // A/B switch
     const int mode = g_pre2_mode.load(std::memory_order_relaxed);
-    if (mode == 0 || (mode < 0 && off)) return false;  // (mode 2: the radix-4 plan where it applies, this one elsewhere)
+    if (mode == 0) return false;
     if (log_n < 21 || log_n > 22 || s.cosets != 1 || s.in2 || s.n_out >= 0) return false;
     const bool load_work = s.pre_scale || s.n_coeffs >= 0;
     if ((load_work && s.inverse) || (s.post_scale && !s.inverse)) return false;      // shapes no caller produces
-    if (!last1024_enabled(g.narrow) || ablate_mode() != 0 || g.wg != 512) return false;
+    if (g.narrow || g.wg != 512) return false;  // (the narrow tiles take the generic last pass, not LAST1024)
     if (g_min_passes.load(std::memory_order_relaxed) > 2) return false;
     return (unsigned long long)s.n * s.L * 8 + (1ull << 20) < (1ull << 32);          // buffer addressing (fits_buffer_offsets)
-}
-// 2^22 points as 1024 x 4096 with the 4096-point LAST pass run as four 1024-point classes per tile (ntt_kernels.h, PRE4) -- round 4's
-// attempt on BASELINE configs[3]: the first pass of a coset evaluation is then an ordinary 1024-point column pass that scales every
-// coefficient once, where the 2048 x 2048 plan scales it in both workgroups of a PRE2 pair.  MEASURED (profiles/r04_c4_plan_ab.txt,
-// 64 x 2^22 XFE, per 16-polynomial tile): the first pass does get cheaper, 1 194 -> 981 us, but the radix-4 load stage costs the last
-// pass more than that, 752 -> 1 047 us (four reads of every input through the L2 in bursts of 16, 27 more instructions per element):
-// 7.9 ms against 7.6 -- a loss, so the product never plans it.  Laboratory build: TF_NTT_PRE4 in the environment makes it the
-// automatic plan of fast_coset_evaluate at 2^22, tf_set_ntt_two_pass(2) of every forward 2^22-point transform.
-static bool pre4_plan_ok(const NttShape& s, int log_n, const NttPlan& g) {
-#ifdef TF_AB_BUILD
-    static const bool on = ab_env("TF_NTT_PRE4") != nullptr;
-    const int mode = g_pre2_mode.load(std::memory_order_relaxed);
-    const bool load_work = s.pre_scale || s.n_coeffs >= 0;
-    if (mode == 0 || mode == 1 || mode == 3 || (mode < 0 && !(on && load_work))) return false;
-    if (log_n != 22 || s.cosets != 1 || s.in2 || s.n_out >= 0 || s.inverse || s.post_scale) return false;
-    if (!last1024_enabled(g.narrow) || ablate_mode() != 0 || g.wg != 512) return false;
-    if (g_min_passes.load(std::memory_order_relaxed) > 2) return false;
-    return (unsigned long long)s.n * s.L * 8 + (1ull << 20) < (1ull << 32);          // buffer addressing (fits_buffer_offsets)
-#else
-    (void)s, (void)log_n, (void)g;
-    return false;
-#endif
 }
 // Round 6: the FIRST pass of a two-pass plan as ONE workgroup per 2048 x 8 tile (ntt_col2048_kernel): every element is loaded (and,
 // in a coset evaluation, scaled) once, where a PRE2 pair does both twice.  2^22 = 2048 (this kernel) x 2048 (the PRE2 last pass);
@@ -245,15 +146,12 @@ static bool c8_first_pass(int log_n, bool scaled) {
     const int mode = g_pre2_mode.load(std::memory_order_relaxed);
     if (mode == 3) return true;
     if (mode >= 0) return false;
-    return kC8Default && log_n == 22 && scaled;
+    return log_n == 22 && scaled;
 }
 static void pre2_split(int log_n, int (&a)[4], bool c8) {
     // 2^21: the 2048-point pass last (the first pass of a coset evaluation then scales every coefficient once); 2^22: both
     a[0] = log_n == 22 ? 11 : 10, a[1] = 11, a[2] = a[3] = 0;
     if (c8) a[0] = 11, a[1] = log_n - 11;
-    if (const char* e = exp_env("TF_NTT_PRE2_FIRST")) {
-        if (log_n == 21 && atoi(e)) a[0] = 11, a[1] = 10;
-    }
 }
 
 // ------------------------------------------------------------------------------------ the plan of one call
@@ -264,7 +162,7 @@ static NttPlan plan_call(const NttShape& s, bool large) {
     const int log_n = ilog2(s.n);
     const int min_passes = g_min_passes.load(std::memory_order_relaxed);
     const bool load_work = s.pre_scale || s.n_coeffs >= 0;
-    p.wg = wg_env() ? wg_env() : 512;  // (every route but Passes runs on the wide geometry, the single-pass Row route included)
+    p.wg = 512;  // (every route but Passes runs on the wide geometry, the single-pass Row route included)
     const auto take = [&p](NttRoute route, size_t launches) {
         p.route = route;
         p.launches = (int)launches;
@@ -272,10 +170,8 @@ static NttPlan plan_call(const NttShape& s, bool large) {
     };
     // batches of short contiguous transforms: wave-private tiles, one coalesced round trip (a handful of them stay on the tiny kernel)
     if (log_n >= 1 && (log_n <= 5 || (log_n == 6 && s.L == 1)) && !load_work && !s.post_scale && !s.in2 && s.n_out < 0 && s.packed &&
-        (log_n == 5 || (s.batch << log_n) * size_t(s.L) >= 4096)) {
-        static const bool no_rows32 = ab_env("TF_NTT_NO_ROWS32") != nullptr;  // A/B switch
-        if (!no_rows32) return take(NttRoute::Rows32, 1);  // (a grid-stride walk: one launch whatever the batch)
-    }
+        (log_n == 5 || (s.batch << log_n) * size_t(s.L) >= 4096))
+        return take(NttRoute::Rows32, 1);  // (a grid-stride walk: one launch whatever the batch)
     if (log_n <= 4) return take(NttRoute::Tiny, 1);
     // (the latency-shaped kernel also takes the coset scalings of fast_coset_evaluate / fast_coset_interpolate: a 2^10-point coset
     //  evaluation is one launch of 8-element threads, 8 us, instead of one 32-element-thread workgroup, 19 us)
@@ -286,14 +182,12 @@ static NttPlan plan_call(const NttShape& s, bool large) {
     }
     if (log_n <= 10) return take(NttRoute::Row, (s.batch + (size_t(1) << 24) - 1) >> 24);  // 2^31 columns per launch
     {
-        static const bool no_block = ab_env("TF_NTT_NO_BLOCK") != nullptr;  // A/B switch
         const bool product_inverse = s.in2 && s.inverse && !load_work && !s.post_scale;
-        // XFieldElement slices take the same kernel as three limb transforms per slice with element stride 3 (round 2;
-        // TF_NTT_NO_XFE_BLOCK restores the two-pass plan for an A/B run): one HBM pass instead of two
-        static const bool no_xfe_block = ab_env("TF_NTT_NO_XFE_BLOCK") != nullptr;
+        // XFieldElement slices take the same kernel as three limb transforms per slice with element stride 3 (round 2):
+        // one HBM pass instead of two
         // (2^11 and 2^12 only: 1.09 vs 1.46 and 1.33 vs 1.42 ms per 3 * 2^26 words; at 2^13 / 2^14 the limbs of a slice sit in
         // different workgroups and the 24-byte element stride costs more than the second pass saves: 1.52 vs 1.42, 1.78 vs 1.33)
-        if (!no_block && log_n <= (s.L == 1 ? 14 : 12) && (s.L == 1 || (s.L == 3 && !no_xfe_block)) && s.cosets == 1 && min_passes == 0 &&
+        if (log_n <= (s.L == 1 ? 14 : 12) && (s.L == 1 || s.L == 3) && s.cosets == 1 && min_passes == 0 &&
             s.batch < (size_t(1) << 29)) {
             // the inverse transform of a BFieldElement product (second operand on load) is the one shape that truncates its store
             const bool product = product_inverse && s.L == 1;
@@ -312,11 +206,7 @@ static NttPlan plan_call(const NttShape& s, bool large) {
     choose_split(log_n, p.P, s.L, p.a);
     // 2^21 and 2^22 points in TWO passes: a 2048-point pass runs as pairs of 1024-point workgroups that share their input
     // (ntt_kernels.h, PRE2; a[i] = 11 below)
-    if (pre4_plan_ok(s, log_n, p)) {
-        p.P = 2;
-        p.a[0] = 10, p.a[1] = 12, p.a[2] = p.a[3] = 0;
-        p.pre4_last = true;
-    } else if (pre2_plan_ok(s, log_n, p)) {
+    if (pre2_plan_ok(s, log_n, p)) {
         p.P = 2;
         // (a scaling first pass on the one-workgroup kernel needs the offset itself, for the inter-pass table with offset^b folded in)
         p.c8 = c8_first_pass(log_n, s.pre_scale) && (!s.pre_scale || s.coset_offset);
@@ -338,12 +228,11 @@ static NttPlan plan_call(const NttShape& s, bool large) {
     if (pipe <= 0) pipe = (P == 2 && log_n >= 21) ? 2 : 1;
     p.K = (P < 4) ? (int)std::min<size_t>((size_t)pipe, p.ntiles) : 1;
     if (P < 4) {
-        p.plain1024 = (last == 10 || p.pre2[P - 1] || p.pre4_last) && last1024_enabled(p.narrow) &&
-                      (!s.post_scale || (s.inverse && scaled_last1024_enabled() && log_n <= 28));
+        // (the narrow tiles take the generic last pass; the kernel's variant that multiplies on store serves fast_coset_interpolate)
+        p.plain1024 = (last == 10 || p.pre2[P - 1]) && !p.narrow && (!s.post_scale || (s.inverse && log_n <= 28));
         // XFieldElement rows through the R = 1024 kernel: word-granular tiles (whole 128-byte lines on the output side)
-        static const bool no_words16 = ab_env("TF_NTT_NO_WORDS16") != nullptr;  // A/B switch
         // (the other last-pass kernels too: all their thread slots as word-columns, e.g. 32 words = 256 bytes for R = 512)
-        if (s.L == 3 && !no_words16) {
+        if (s.L == 3) {
             if (p.plain1024) {
                 p.words = 16;
             } else {  // share the N_1 * L words of a row evenly among the fewest tiles, in whole lines
@@ -355,7 +244,7 @@ static NttPlan plan_call(const NttShape& s, bool large) {
     }
     // the LAST1024 kernel (two or three passes, last radix 1024) is the one that truncates, and it addresses its stores through a
     // buffer resource: 1024 * (n L / 1024) * 8 bytes must fit 32 bits (fits_buffer_offsets)
-    p.truncates = P <= 3 && last == 10 && last1024_enabled(p.narrow) && (unsigned long long)s.n * s.L * 8 + (1ull << 20) < (1ull << 32);
+    p.truncates = P <= 3 && last == 10 && !p.narrow && (unsigned long long)s.n * s.L * 8 + (1ull << 20) < (1ull << 32);
     // (the last pass of a four-pass plan is launched per polynomial)
     return take(NttRoute::Passes, P == 4 ? p.ntiles * 3 + s.batch : p.ntiles * P);
 }
@@ -385,23 +274,15 @@ bool can_truncate(size_t n, int L) {
 size_t coset_split(size_t n_coeffs, size_t order, size_t batch, int L) {
     size_t len = 1;
     while (len < n_coeffs) len <<= 1;
-    static const bool no_split = ab_env("TF_COSET_EVAL_NO_SPLIT") != nullptr;  // A/B switch
     // ADVICE r3 asked whether the comparison should use the EFFECTIVE pass count of the plain plan (orders 2^21 / 2^22 run in two
     // passes under PRE2, so the split then saves no pass).  Built and measured (profiles/r04_lde_split_rule.txt, 2^28 words per
     // call): the split still wins where it matters -- BFE 2^20 -> 2^22 2.05 vs 2.48 ms, 2^19 -> 2^22 2.03 vs 2.40, 2^20 -> 2^21
     // 2.07 vs 2.17; XFE 2^20 -> 2^22 1.01 vs 1.13 -- because its first pass reads n_coeffs rows instead of `order` and none of its
     // passes pays the PRE2 pair's second read and second scaling; only XFE 2^18 / 2^19 -> 2^21 is 3 % faster on the plain plan.
-    // The round-3 rule (nominal pass counts) therefore stays; the other one is a laboratory switch.
-    static const bool effective_rule = ab_env("TF_COSET_EVAL_EFFECTIVE_PASSES") != nullptr;
-    int plain_passes = pass_count(ilog2(order));
-    if (effective_rule) {  // the passes the plain evaluation of this very call is planned with
-        NttShape s;
-        s.n = order, s.batch = batch, s.L = L, s.n_coeffs = (long long)n_coeffs, s.pre_scale = s.coset_offset = true, s.packed = false;
-        const NttPlan plain = plan_ntt(s);
-        if (plain.route == NttRoute::Passes) plain_passes = plain.P;
-    }
+    // The round-3 rule (nominal pass counts) therefore stays.
+    const int plain_passes = pass_count(ilog2(order));
     // (at most kMaxCosetSplit cosets: one scale table of n_coeffs words per coset is built and, while it fits the budget, cached)
-    const bool split = !no_split && len > 1024 && len < order && order / len <= kMaxCosetSplit && order <= (size_t(1) << 30) &&
+    const bool split = len > 1024 && len < order && order / len <= kMaxCosetSplit && order <= (size_t(1) << 30) &&
                        pass_count(ilog2(len)) < plain_passes;
     return split ? order / len : 1;
 }

@@ -84,9 +84,8 @@ int poly_mul_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out, siz
     DevTemp work(s);
     TRY(work.alloc(2 * half, "poly_mul"));
     u64* const tmp = work.p;
-    static const bool no_fuse = ab_env("TF_POLY_MUL_NO_FUSE") != nullptr;  // A/B switch
     bool copied = false;
-    if (order > 16 && !no_fuse) {
+    if (order > 16) {
         // zero padding happens in the first pass of each forward transform (rows beyond the coefficients read as zero);
         // over BFieldElement the pointwise product rides on the inverse transform's first load
         TRY(run_ntt(ctx, a, tmp, a_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s));
@@ -164,9 +163,8 @@ int poly_square_dev(const u64* a, size_t na, u64* out, size_t batch, int L, void
     DevTemp work(s);
     TRY(work.alloc(batch * order * size_t(L), "poly_square"));
     u64* const tmp = work.p;
-    static const bool no_fuse = ab_env("TF_POLY_MUL_NO_FUSE") != nullptr;  // A/B switch
     bool copied = false;
-    if (order > 16 && !no_fuse) {
+    if (order > 16) {
         TRY(run_ntt(ctx, a, tmp, (long long)na * L, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s));
         const bool trunc = can_truncate(order, L);
         u64* dst = trunc ? out : tmp;
@@ -220,41 +218,21 @@ int lde_dev(const u64* values, size_t n, u64 offset_in, u64* out, size_t m, u64 
 // work expensive).  With the levels in the transform domain (10 launches per level to build, 7 to walk) a level costs less than
 // the O(leaf^2) work of a bigger leaf on the few workgroups a small tree has: n = m = 2^16 BFE 2.56 ms with 1024-point leaves,
 // 2.30 with 512, 2.33 with 256, 2.46 with 128; 2^20 x 2^20 6.7 / 5.7 / 5.4 / 5.5; XFE 2^20 x 2^20 24.1 / 17.0 / 14.0 / 13.6
-// (tools/leaf_ab.sh, profiles/r02_leaf_ab.txt).
-inline int tree_leaf_log(int L) {  // TF_TREE_LEAF_LOG = 6..10 overrides both fields (A/B: tools/batch_eval_sweep.py)
-    static const int forced = [] {
-        const char* e = ab_env("TF_TREE_LEAF_LOG");
-        const int v = e ? atoi(e) : 0;
-        return (v >= 6 && v <= 10) ? v : 0;
-    }();
-    return forced ? forced : (L == 1 ? 8 : 7);
-}
+// (profiles/r02_leaf_ab.txt).
+inline int tree_leaf_log(int L) { return L == 1 ? 8 : 7; }
 inline int tree_leaf(int L) { return 1 << tree_leaf_log(L); }
 // Trees that are also walked UPWARDS (interpolation; the padded trees behind zerofier / interpolate / the ZerofierTree handle) are
 // built down to 64-point leaves: the interpolant of a leaf is d sequential steps of ~0.4 us each (leaf_interpolant_kernel), 102 us
 // for 256 points, while a level costs ~15 us since the latency-shaped transform -- prepared-tree interpolation of 2^12 points
 // 176 -> 122 us, 2^16 434 -> 383, XFieldElement 2^12 358 -> 234 (tools/tree_latency.py, profiles/r03_tree_latency_leaf.txt).
 // Evaluations on such a tree stop their walk at the level whose nodes have tree_leaf(L) points (Horner is parallel over the
-// points: the bigger leaf is the faster one there).  TF_TREE_INTERP_LEAF_LOG = 6..10 overrides.
-inline int tree_interp_leaf(int L) {
-    static const int forced = [] {
-        const char* e = ab_env("TF_TREE_INTERP_LEAF_LOG");
-        const int v = e ? atoi(e) : 0;
-        return (v >= 6 && v <= 10) ? v : 0;
-    }();
-    return 1 << std::min(forced ? forced : 6, tree_leaf_log(L));
-}
+// points: the bigger leaf is the faster one there).
+inline int tree_interp_leaf(int L) { return 1 << std::min(6, tree_leaf_log(L)); }
 
-// widest walk (points in flight) that takes the four-threads-per-point leaf kernels (TF_TREE_LEAF_SPLIT_MAX: sweep hook).  Measured,
+// widest walk (points in flight) that takes the four-threads-per-point leaf kernels.  Measured,
 // tools/tree_latency.py with the limit lifted: 2^16 points evaluate 726 -> 681 us (XFE), interpolate 265 -> 253 (BFE) but 450 -> 487
 // (XFE: 109 KB of LDS per leaf), level at 2^18, XFE interpolation 1.5 x slower at 2^20 -- hence 2^16 / 2^16 / 2^15.
-inline long long leaf_split_max() {
-    static const long long v = [] {
-        const char* e = ab_env("TF_TREE_LEAF_SPLIT_MAX");
-        return e ? atoll(e) : (1ll << 15);
-    }();
-    return v;
-}
+inline long long leaf_split_max() { return 1ll << 15; }
 
 struct ZerofierTree {
     int leaf = 0;              // points per leaf (tree_leaf(L) for a tree that is only evaluated on, tree_interp_leaf(L) otherwise)
@@ -304,10 +282,6 @@ int zerofier_tree_build(DeviceCtx* ctx, const u64* points, long long n_points, Z
     }
     if (h == 0) return TF_OK;
     const int kTreeLeaf = T->leaf;
-    if (3 * kTreeLeaf * L * sizeof(u64) > 48 * 1024) {  // (only with a leaf size forced through TF_TREE_LEAF_LOG, laboratory build)
-        static std::atomic<unsigned long long> done_mask{0};
-        if (int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::leaf_zerofier_kernel<L>), 160 * 1024, done_mask)) return rc_attr;
-    }
     hipLaunchKernelGGL(tfk::leaf_zerofier_kernel<L>, dim3((unsigned)(M / kTreeLeaf)), dim3(kTreeLeaf), 3 * kTreeLeaf * L * sizeof(u64), s, points,
                        n_points, kTreeLeaf, T->tails[0], T->inv[0]);
     HIPCHK(hipGetLastError());
@@ -359,10 +333,9 @@ int inverse_of_cached_product(DeviceCtx* ctx, const u64* a_hat, const u64* b_hat
 
 // The elementwise steps of a walk (reverse, remainder, the interpolation's pointwise combination) ride on the load / store of the
 // latency-shaped transform next to them whenever that kernel serves the level (round 3): a level of the walk down is 4 launches
-// instead of 7, of the walk up 2 instead of 3.  TF_TREE_NO_FUSE keeps them as kernels of their own (A/B, tests).
+// instead of 7, of the walk up 2 instead of 3.
 bool tree_fuse(long long order, long long lines, int L) {
-    static const bool off = ab_env("TF_TREE_NO_FUSE") != nullptr;
-    if (off || order > 4096 || order < 64 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;
+    if (order > 4096 || order < 64 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;
     if (lines >= (1ll << 22)) return false;
     return lat_wanted(ilog2((size_t)order), (size_t)lines, L);
 }
@@ -439,10 +412,9 @@ int zerofier_tree_evaluate(DeviceCtx* ctx, const ZerofierTree& T, const u64* F, 
         cur = nxt;
     }
     // few leaves: four threads per point (the chip is idle anyway; a thread's eval_leaf products in a row were 16 of the 116 us of
-    // a 2^12-point walk).  TF_TREE_NO_LEAF_SPLIT: A/B switch.
-    static const bool no_split = ab_env("TF_TREE_NO_LEAF_SPLIT") != nullptr;
+    // a 2^12-point walk).
     constexpr int kSplit = 4;
-    if (!no_split && UM <= 2 * leaf_split_max() && eval_leaf * kSplit <= 1024 && eval_leaf >= 16 * kSplit) {
+    if (UM <= 2 * leaf_split_max() && eval_leaf * kSplit <= 1024 && eval_leaf >= 16 * kSplit) {
         hipLaunchKernelGGL((tfk::leaf_evaluate_split_kernel<L, kSplit>), dim3((unsigned)(UM / eval_leaf)), dim3(eval_leaf * kSplit),
                            (size_t)(1 + kSplit) * eval_leaf * L * sizeof(u64), s, cur, points, n_points, eval_leaf, vals, M / eval_leaf);
     } else {
@@ -453,16 +425,11 @@ int zerofier_tree_evaluate(DeviceCtx* ctx, const ZerofierTree& T, const u64* F, 
     return TF_OK;
 }
 
-// When the tree pays (measured, tools/batch_eval_sweep.py): many points AND a long polynomial.  TF_BATCH_EVAL = horner | tree
-// forces a route (A/B, tests).
-std::atomic<int> g_batch_eval_route{-1};  // tf_set_batch_eval_route: 0 automatic, 1 Horner, 2 zerofier tree (-1: read TF_BATCH_EVAL)
+// When the tree pays (measured, tools/batch_eval_sweep.py): many points AND a long polynomial.  tf_set_batch_eval_route forces a
+// route (tests).
+std::atomic<int> g_batch_eval_route{0};  // tf_set_batch_eval_route: 0 automatic, 1 Horner, 2 zerofier tree
 bool tree_route(size_t n_coeffs, size_t n_points, size_t batch, int L) {
-    int route = g_batch_eval_route.load(std::memory_order_relaxed);
-    if (route < 0) {
-        const char* e = ab_env("TF_BATCH_EVAL");
-        route = !e ? 0 : (!strcmp(e, "horner") ? 1 : (!strcmp(e, "tree") ? 2 : 0));
-        g_batch_eval_route.store(route, std::memory_order_relaxed);
-    }
+    const int route = g_batch_eval_route.load(std::memory_order_relaxed);
     const char* force = route == 1 ? "horner" : (route == 2 ? "tree" : nullptr);
     if (force && !strcmp(force, "horner")) return false;
     const size_t kTreeLeaf = (size_t)tree_leaf(L);
@@ -509,8 +476,8 @@ int tree_batch_evaluate(DeviceCtx* ctx, const ZerofierTree& T, const u64* points
     const long long M = T.M;
     const size_t chunks = std::max<size_t>(1, (n_coeffs + (size_t)M - 1) / (size_t)M);
     const size_t units = batch * chunks, ML = (size_t)M * L;
-    // units per walk: 2^25 elements of work per array (TF_TREE_UNIT_SLAB = elements: the A/B and test knob for the slab boundary)
-    static const size_t slab_elems = [] { const char* e = ab_env("TF_TREE_UNIT_SLAB"); const long long v = e ? atoll(e) : 0; return v > 0 ? (size_t)v : (size_t(1) << 25); }();
+    // units per walk: 2^25 elements of work per array
+    constexpr size_t slab_elems = size_t(1) << 25;
     const size_t slab = std::max<size_t>(1, std::min<size_t>(units, slab_elems / (size_t)M));
     // padded coefficients (units M) + values (units M) + walk work (8 slab M)
     DevTemp tmp(s);
@@ -662,10 +629,6 @@ int padded_tree_build(const u64* points, size_t n_points, size_t extra_words, Pa
     u64* leaf_inv = pt->root_tail + (size_t)M * L;
     pt->extra = leaf_inv + (size_t)M * L;
     if (h == 0) {  // one leaf: it is the root
-        if (3 * kTreeLeaf * L * sizeof(u64) > 48 * 1024) {
-            static std::atomic<unsigned long long> done_mask{0};
-            if (int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::leaf_zerofier_kernel<L>), 160 * 1024, done_mask)) return rc_attr;
-        }
         hipLaunchKernelGGL(tfk::leaf_zerofier_kernel<L>, dim3(1), dim3(kTreeLeaf), 3 * kTreeLeaf * L * sizeof(u64), s, points, (long long)n_points,
                            kTreeLeaf, pt->root_tail, leaf_inv);
         HIPCHK(hipGetLastError());
@@ -764,21 +727,16 @@ int tree_interpolate_rows(DeviceCtx* ctx, const PaddedTree& pt, const u64* domai
     for (size_t r0 = 0; r0 < rows && !rc; r0 += slab) {
         const size_t nr = std::min(slab, rows - r0);
         // few leaves: the quotient form on the leaf zerofiers the tree holds (no barrier per point; four threads per coefficient in
-        // its second phase).  TF_TREE_NO_LEAF_SPLIT: A/B switch
-        static const bool no_split = ab_env("TF_TREE_NO_LEAF_SPLIT") != nullptr;
+        // its second phase)
         constexpr int kSplit = 4;
         const size_t div_lds = ((size_t)2 * kTreeLeaf + (size_t)kTreeLeaf * (kTreeLeaf + 1) + (size_t)kSplit * kTreeLeaf) * L * sizeof(u64);
-        if (!no_split && (long long)nr * M <= (L == 1 ? 2 : 1) * leaf_split_max() && kTreeLeaf * kSplit <= 1024 && kTreeLeaf >= 4 * kSplit && div_lds <= 144 * 1024) {
+        if ((long long)nr * M <= (L == 1 ? 2 : 1) * leaf_split_max() && kTreeLeaf * kSplit <= 1024 && kTreeLeaf >= 4 * kSplit && div_lds <= 144 * 1024) {
             static std::atomic<unsigned long long> done_mask{0};
             if (div_lds > 48 * 1024) rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::leaf_interpolant_div_kernel<L, kSplit>), 144 * 1024, done_mask);
             if (!rc)
                 hipLaunchKernelGGL((tfk::leaf_interpolant_div_kernel<L, kSplit>), dim3((unsigned)(M / kTreeLeaf), (unsigned)nr), dim3(kTreeLeaf * kSplit),
                                    div_lds, s, domain, values + r0 * n * L, winv, (const u64*)(h > 0 ? pt.T.tails[0] : pt.root_tail) /* a single leaf is the root */, (long long)n, kTreeLeaf, M, na);
         } else {
-            if (6 * kTreeLeaf * L * sizeof(u64) > 48 * 1024) {  // only with a leaf size forced through TF_TREE_LEAF_LOG
-                static std::atomic<unsigned long long> done_mask{0};
-                if (!rc) rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&tfk::leaf_interpolant_kernel<L>), 160 * 1024, done_mask);
-            }
             hipLaunchKernelGGL(tfk::leaf_interpolant_kernel<L>, dim3((unsigned)(M / kTreeLeaf), (unsigned)nr), dim3(kTreeLeaf),
                                6 * kTreeLeaf * L * sizeof(u64), s, domain, values + r0 * n * L, winv, (long long)n, kTreeLeaf, M, na);
         }
@@ -802,24 +760,17 @@ int tree_interpolate_rows(DeviceCtx* ctx, const PaddedTree& pt, const u64* domai
                 continue;
             }
             rc = run_ntt(ctx, cur, Nh, d * L, 2 * d * L, (size_t)(2 * d), (size_t)(children * (long long)nr), L, false, nullptr, d, s);
-            // (measured, tools/tree_latency.py on one box: prepared-tree interpolation of 2^12 points 129.0 us with the pointwise
-            //  kernel, 135.8 us with it fused -- four strided loads and two products per element in front of the transform's first
-            //  stage cost more than the 1.5 us a pipelined elementwise launch really adds; off unless TF_TREE_FUSE_INTERP is set)
-            static const bool fuse_interp = ab_env("TF_TREE_FUSE_INTERP") != nullptr;
-            if (!rc && L == 1 && fuse_interp && tree_fuse(2 * d, parents * (long long)nr, 1)) {
-                // the pointwise combination rides on the load of the inverse transform (ntt_lat_kernel, load_mode 2)
-                tfk::NttLatArgs m{};
-                m.load_mode = 2, m.th = pt.T.That[l], m.parents = parents;
-                rc = launch_lat(ctx, Nh, nxt, 2 * d, 2 * d, ilog2((size_t)(2 * d)), (size_t)(parents * (long long)nr), 1, true, -1, nullptr, s, &m);
-            } else {
-                if (!rc) rc = launch_1d<L>(tfk::interpolant_pointwise_kernel<L>, (long long)nr * parents * 2 * d, s, (const u64*)Nh,
-                                           (const u64*)pt.T.That[l], nxt, d, parents, (long long)nr);
-                // the root level of an unpadded domain (n = M) transforms straight into the caller's rows: no copy-out launch
-                const bool direct = l == h - 1 && (long long)n == M;
-                u64* dst = direct ? out + r0 * n * L : nxt;
-                wrote_direct = direct;
-                if (!rc) rc = run_ntt(ctx, nxt, dst, 2 * d * L, 2 * d * L, (size_t)(2 * d), (size_t)(parents * (long long)nr), L, true, nullptr, -1, s);
-            }
+            // (the pointwise combination stays a kernel of its own.  Measured, tools/tree_latency.py on one box: prepared-tree
+            //  interpolation of 2^12 points 129.0 us with the pointwise kernel, 135.8 us with it fused into the inverse transform's load
+            //  -- four strided loads and two products per element in front of the transform's first stage cost more than the 1.5 us a
+            //  pipelined elementwise launch really adds)
+            if (!rc) rc = launch_1d<L>(tfk::interpolant_pointwise_kernel<L>, (long long)nr * parents * 2 * d, s, (const u64*)Nh,
+                                       (const u64*)pt.T.That[l], nxt, d, parents, (long long)nr);
+            // the root level of an unpadded domain (n = M) transforms straight into the caller's rows: no copy-out launch
+            const bool direct = l == h - 1 && (long long)n == M;
+            u64* dst = direct ? out + r0 * n * L : nxt;
+            wrote_direct = direct;
+            if (!rc) rc = run_ntt(ctx, nxt, dst, 2 * d * L, 2 * d * L, (size_t)(2 * d), (size_t)(parents * (long long)nr), L, true, nullptr, -1, s);
             std::swap(cur, nxt);
         }
         if (!rc && !wrote_direct) {
@@ -1106,8 +1057,7 @@ int barycentric_dev(const u64* codewords, size_t n, size_t batch, int cw_width, 
     hipLaunchKernelGGL(tfk::barycentric_weights_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, (long long)n, log_n, omega, gl::mont_pow(omega, 256),
                        x[0], x[1], x[2], w);
     {
-        static const int rows_env = [] { const char* e = ab_env("TF_BARY_ROWS"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= tfk::kBaryRows) ? v : 0; }();
-        const int rpb = rows_env ? rows_env : 2;  // rows per block (A/B: tools/barycentric_bench.py; 1 / 2 / 4 within 3 % of each other)
+        constexpr int rpb = 2;  // rows per block (tools/barycentric_bench.py: 1 / 2 / 4 within 3 % of each other)
         const long long row_groups = ((long long)batch + 1 + rpb - 1) / rpb;  // the denominator is row `batch`
         if (row_groups > 65535) return TF_ERR_LEN_TOO_LARGE;  // more than 65 535 rpb - 1 = 131 069 codewords in one call
         if (cw_width == 1)

@@ -51,13 +51,12 @@ int ensure_tip5(DeviceCtx* ctx) {
 // ------------------------------------------------------------------------------------ Tip5 / Merkle
 // Two kernel families (tip5_kernels.h).  Launches of at most kCoopMaxCount permutation chains are latency-bound (fewer chains
 // than the chip has SIMD slots): 16 lanes per permutation, ~2.5 us per permutation of a chain.  Everything larger runs in the
-// matrix-pipe form (4 lanes per permutation, MDS on v_mfma_i32_16x16x64_i8 since round 6): crossover measured at 2^13 chains with the f64 form
+// matrix-pipe form (4 lanes per permutation, MDS on v_mfma_i32_16x16x64_i8 since round 6): crossover measured at 2^13 chains with round 5's f64 form
 // (profiles/r05_tip5_small_times.txt: hash_varlen of 33 words, 2^13 rows 24.4 vs 25.6 us, 2^14 rows 34.6 vs 26.3 us).
 // (kCoopMaxCount, coop_two_rows and mx_blocks: tf_internal.h -- tf_sponge.hip plans with the same rules)
 // ... and the subtree launches use a row pair per hash_pair at the levels that have the rows to spare, when every workgroup has a CU of its own
 inline int subtree_two_rows(long long workgroups) {
-    static const bool off = ab_env("TF_TIP5_NO_COOP2") != nullptr;  // A/B switch
-    return (!off && workgroups <= (long long)device_cus()) ? 1 : 0;
+    return workgroups <= (long long)device_cus() ? 1 : 0;
 }
 
 // per_tree = 2^shift, or -1
@@ -68,7 +67,7 @@ void launch_permute_mx(u64* d_states, u64* d_trace, long long count, hipStream_t
 }
 
 // tf_debug_field_op_dev: ONE primitive of gl64.h or one fold tail of tip5_kernels.h over count operand pairs, called as the kernels call
-// it (so TF_MONT4 / TF_MONT_CC / TF_TIP5_I8 pick the form here as they do there).  A thread runs one block of the primitive on W
+// it (so TF_MONT4 / TF_MONT_CC pick the form here as they do there).  A thread runs one block of the primitive on W
 // consecutive elements: element index mod W is the position in the block, i.e. which carry chain (vcc or an SGPR pair) the pair rides.
 // Loads and stores are guarded by count, missing operands are 0, out1 is written by the two-output ops only.  The fold tails take
 // t = a[i] = (th : tl) and h0 = the low half of b[i].

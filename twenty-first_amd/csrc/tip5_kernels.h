@@ -6,16 +6,16 @@
 //   hash_10 :559-569; hash_pair :577-586; hash_varlen :617-623 + util_types/sponge.rs:41-55.
 // Merkle: twenty-first/src/util_types/merkle_tree.rs:149-222 (nodes[i] = hash_pair(nodes[2i], nodes[2i+1])).
 //
-// Three formulations of the same round, all producing the reference's words:
+// Two formulations of the same round, both producing the reference's words:
 //   * matrix-pipe form (throughput; every launch of more than 2^13 permutation chains): FOUR lanes per permutation, the MDS --
 //     the one dense contraction on this path, out = M * state with the constant circulant M (tip5/naive.rs:54-68, mod.rs:154-157)
-//     -- on the matrix pipe: v_mfma_i32_16x16x64_i8 on byte planes since round 6 (round 5: v_mfma_f64_16x16x4_f64, kept as -DTF_TIP5_I8=0)
+//     -- on the matrix pipe: v_mfma_i32_16x16x64_i8 on byte planes
 //   * cooperative form (latency; small launches and the top of a tree): 16 lanes of a DPP row per permutation, the circulant as
 //     16 row rotations + v_mad_u64_u32; where half the rows would idle anyway, a row PAIR per permutation (the rotation terms split
 //     over the two rows, v_permlane16_swap_b32 joins them: tip5_permutation_coop2)
-//   * lane-per-permutation form (tip5_round below): the whole state in one lane's registers, 512 v_mad_u64_u32 per MDS.  It was
-//     the throughput kernel through round 4; the library no longer launches it -- tools/microbench_mds.hip keeps it as the
-//     yardstick the matrix-pipe form is measured against (profiles/r05_microbench_mds_mfma.txt).
+// (The lane-per-permutation round -- the whole state in one lane's registers, 512 v_mad_u64_u32 per MDS, the throughput kernel through
+// round 4 -- lives in tools/microbench_mds.hip as the yardstick the matrix-pipe form is measured against,
+// profiles/r05_microbench_mds_mfma.txt.)
 // In every form a half-sum is reduced with 2^64 = 2^32 - 1 and made canonical explicitly after adding the round constant (the
 // reference gets there through a quirk of Add, mod.rs:222-242 / :1098-1142; the canonical result is the same word).
 #pragma once
@@ -47,61 +47,6 @@ __device__ __forceinline__ u32 lookup4(u32 w, const unsigned char* lut) {
     return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
 }
 
-__device__ __forceinline__ void tip5_round(u64 (&s)[16], int round, const unsigned char* lut) {
-    // S-box layer (mod.rs:184-194)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        u32 lo = lookup4((u32)s[i], lut), hi = lookup4((u32)(s[i] >> 32), lut);
-        s[i] = ((u64)hi << 32) | lo;  // may be >= p, exactly like the reference
-    }
-#pragma unroll
-    for (int i = 4; i < 16; i += 2) {  // x^7 = x * (x^2 * x^4), two elements per hand-scheduled product pair
-        u64 sq0, sq1, qu0, qu1, t0, t1;
-        gl::mont_mul2(s[i], s[i], s[i + 1], s[i + 1], sq0, sq1);
-        gl::mont_mul2(sq0, sq0, sq1, sq1, qu0, qu1);
-        gl::mont_mul2(sq0, qu0, sq1, qu1, t0, t1);
-        gl::mont_mul2(s[i], t0, s[i + 1], t1, s[i], s[i + 1]);
-    }
-    // MDS on 32-bit halves + round constant
-    u32 lo[16], hi[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        lo[i] = (u32)s[i];
-        hi[i] = (u32)(s[i] >> 32);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        u64 alo = 0, ahi = 0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            const u32 m = mds_entry(16 + r - c);
-            alo += (u64)m * lo[c];
-            ahi += (u64)m * hi[c];
-        }
-        // value + round constant = alo + ahi * 2^32 + rc  (< 2^85)  as three 32-bit carry-chain words (t2 : t1 : t0), then one
-        // fold of t2 * 2^64 == t2 * (2^32 - 1) and one conditional subtraction: the canonical word of the reference's
-        // reduce-then-add (mod.rs:244-252, :178-180), because every step is exact
-        const u64 rc = g_tip5.rc[round * 16 + r];
-        unsigned c0, c1, c2, c3, c4;
-        const u32 w1 = __builtin_addc((u32)(alo >> 32), (u32)ahi, 0u, &c0);
-        const u32 w2 = __builtin_addc((u32)(ahi >> 32), 0u, c0, &c1);
-        const u32 t0 = __builtin_addc((u32)alo, (u32)rc, 0u, &c2);
-        const u32 t1 = __builtin_addc(w1, (u32)(rc >> 32), c2, &c3);
-        const u32 t2 = __builtin_addc(w2, 0u, c3, &c4);  // < 2^22
-        const u64 l64 = ((u64)t1 << 32) | t0;
-        const u64 t = (u64)t2 * 0xffffffffu + l64;  // true value < 2^64 + 2^54
-        const bool ca = t < l64;
-        const u64 u = t + gl::EPS;  // t - p (mod 2^64)
-        const bool cb = u < t;
-        s[r] = (ca | cb) ? u : t;
-    }
-}
-
-__device__ __forceinline__ void tip5_permutation(u64 (&s)[16], const unsigned char* lut) {
-#pragma unroll 1
-    for (int r = 0; r < 5; ++r) tip5_round(s, r, lut);
-}
-
 __device__ __forceinline__ void stage_lut(unsigned char* lut_lds) {
     // LOOKUP_TABLE (mod.rs:50-64) into LDS, once per workgroup, from its definition L(x) = ((x + 1)^3 mod 257) - 1
     // (mod.rs:1022-1026; the reference's lookup_table_is_correct test :1035-1053 pins the literal table to it): a dozen integer
@@ -125,31 +70,18 @@ __device__ __forceinline__ u64 table_word(const u64* table, long long i, long lo
     return table[j * col_stride + i * width + k];
 }
 
-// ---- matrix-pipe form: FOUR lanes hold one permutation, the MDS runs on v_mfma_f64_16x16x4_f64 ---------------------------------
+// ---- matrix-pipe form: FOUR lanes hold one permutation, the MDS runs on the matrix pipe ------------------------------------------
 // The MDS layer is the one dense contraction on this path: a constant 16 x 16 matrix times the state (tip5/naive.rs:54-68,
 // mod.rs:210-253).  A wave is a 16-column x 4-quarter grid: lane l = (column j = l & 15, quarter q = l >> 4) holds the words
 // 4 i + q (i = 0..3) of the permutation in column j, so register 0 of every lane is a split_and_lookup word and registers 1..3 are
-// x^7 words -- no divergence in the S-box layer.  For the MDS each 32-bit half of a word becomes an f64 (v_cvt_f64_u32) and is the
-// B operand of K-block i (B[k][j]: lane (j, k) -- exactly where the word lives); A is the circulant itself, A_i[r][k] =
-// M[(r - 4 i - k) mod 16], one constant per lane and K-block; D[r][j] comes back in lane (j, r & 3) register r >> 2 -- again exactly
-// the strided layout (MI355X f64 C/D map: row = (lane >> 4) + 4 * reg).  Products are < 2^48 and a sum of 16 is < 2^51.01, so the
-// f64 arithmetic is exact; the accumulator starts at 2^52 + (half of the round constant, adjusted), which makes the raw bits of
-// the result  0x433 << 52 | integer sum.  The recombination works on those raw bits: with B = 0x433 << 52,
-//     rawlo + 2^32 rawhi = (lo-sum + 2^32 hi-sum + x) + B (1 + 2^32),     x = (rc - B (1 + 2^32)) mod p  split into the two starts,
-// so   h1 * (2^32 - 1) + rawlo  (one v_mad_u64_u32; < 2^64: no carry)  + h0 * 2^32  (one add with carry k)  is congruent to
-// MDS(state)[r] + rc[r], and one conditional "+ (2^32 - 1)" (carry, or >= p) makes it the canonical word -- the word the
-// lane-per-permutation round above produces.  8 MFMA per 16 permutations and round; measured (tools/microbench_mds.hip,
-// profiles/r05_microbench_mds_mfma.txt) the f64 matrix pipe does NOT overlap with the vector ALU on gfx950 (it runs at the vector
-// f64 rate and blocks VALU issue), so the gain is what the layout saves -- 8 MFMA (512 cycles) replace 128 v_mad_u64_u32 (~600
-// cycles) per 16 permutations, the round constant and the 85-bit recombination shrink to 6 instructions per word -- not a second pipe.
-#ifndef TF_TIP5_I8
-#define TF_TIP5_I8 1  // 1: the MDS on v_mfma_i32_16x16x64_i8 (round 6); 0: on v_mfma_f64_16x16x4_f64 (round 5; the yardstick of tools/microbench_mds.hip)
-#endif
-typedef double d4 __attribute__((ext_vector_type(4)));
+// x^7 words -- no divergence in the S-box layer.  The result of a layer is congruent to MDS(state)[r] + rc[r], and one conditional
+// "+ (2^32 - 1)" (carry, or >= p) makes it the canonical word -- the word the lane-per-permutation round produces.
+// (Round 5 ran the layer on v_mfma_f64_16x16x4_f64, the 32-bit halves of every word as exact f64: measured, tools/microbench_mds.hip,
+// profiles/r05_microbench_mds_mfma.txt, the f64 matrix pipe does NOT overlap with the vector ALU on gfx950 -- it runs at the vector
+// f64 rate and blocks VALU issue -- so its gain was only what the layout saves.)
 typedef int v4i __attribute__((ext_vector_type(4)));
-#if TF_TIP5_I8
 // ---- round 6: the MDS on the i8 matrix pipe --------------------------------------------------------------------------------------
-// Same lane layout.  The state goes in byte by byte, the matrix entries as three SIGNED base-256 digits (M = m0 + 256 m1 + 65536 m2,
+// The state goes in byte by byte, the matrix entries as three SIGNED base-256 digits (M = m0 + 256 m1 + 65536 m2,
 // |m| <= 128), and output plane p = a + b (0..9) collects
 //     P_p[r][j] = sum_c sum_{a <= 2} m_a[(r - c) mod 16] * d_{p - a}[c][j],   d_b = (byte b of word c) - 128 = the byte XOR 0x80 as an i8,
 // on v_mfma_i32_16x16x64_i8 with K = (c, b) (16 words x 4 bytes), at most 48 non-zero products per plane, |P_p| < 2^20, so
@@ -168,7 +100,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 //     non-negative (< 2^22) and the round constant costs nothing.
 // Recombination per word: L0 = Q0 + 2^8 Q1 + 2^16 Q2 + 2^24 Q3 (one v_lshl_add_u32, two v_mad_u64_u32), L1 from Q4..Q7, L2 = Q8 + 2^8 Q9;
 //   value = L0 + 2^32 L1 + 2^64 L2 = L0 + 2^32 lo(L1) + (2^32 - 1) (hi(L1) + L2) (mod p): one add, one v_mad_u64_u32 (< 2^64), then the same
-//   "add to the high word, fold the carry" tail as the f64 form (mx_fold4_tail).  Ten MFMA of 16 cycles instead of eight of 64, and unlike
+//   "add to the high word, fold the carry" tail the f64 form had (mx_fold4_tail).  Ten MFMA of 16 cycles instead of eight of 64, and unlike
 //   the f64 pipe the i8 pipe runs BESIDE the vector ALU (profiles/r05_mfma_valu_mix.txt).  Measured (tools/microbench_mds.hip,
 //   profiles/r06_microbench_mds_i8.txt): MDS layer alone 49.6 -> 73.8 G layers/s, whole permutations 5.57 -> 6.42 G/s (+15 %), every word
 //   that of 128-bit arithmetic / of the lane-per-permutation round.
@@ -249,67 +181,6 @@ __device__ __forceinline__ void mx_a_operands(const Tip5MxLds*, MxA& a) {
 #pragma unroll
     for (int p = 0; p < 6; ++p) a.p[p] = *reinterpret_cast<const v4i*>(&g_tip5_mx.a[p][threadIdx.x & 63][0]);
 }
-#else  // ---- the f64 form of round 5 ------------------------------------------------------------------------------------------------
-
-struct Tip5MxConsts {
-    double c[5][4][8];  // accumulator starts [round][quarter q][lo-half reg 0..3 | hi-half reg 0..3] for state word 4 reg + q
-    double a[16];       // MDS_MATRIX_FIRST_COLUMN as f64
-    double cf[4][8];    // round 0 of a FIXED-LENGTH hash (hash_10 / hash_pair): c[0] plus the MDS contribution of words 12..15, which
-                        // are the constant 1 there (Tip5::new(Domain::FixedLength), mod.rs:511-526, and 1^7 = 1)
-};
-__constant__ Tip5MxConsts g_tip5_mx;
-
-// host side of the table above; rc_mont = Montgomery form of ROUND_CONSTANTS (the g_tip5.rc words)
-inline void fill_tip5_mx(Tip5MxConsts& t, const u64* rc_mont) {
-    constexpr u32 col[16] = {61402, 1108, 28750, 33823, 7454, 43244, 53865, 12034, 56951, 27521, 41351, 40901, 12021, 59689, 26798, 17845};
-    const u64 B = 0x4330000000000000ULL;
-    const u64 Bp = B % gl::P;
-    const u64 K = (u64)(((unsigned __int128)Bp * ((1ull << 32) + 1)) % gl::P);
-    for (int i = 0; i < 16; ++i) t.a[i] = (double)col[i];
-    for (int round = 0; round < 5; ++round)
-        for (int q = 0; q < 4; ++q)
-            for (int v = 0; v < 4; ++v) {
-                const u64 rc = rc_mont[round * 16 + 4 * v + q];
-                const u64 x = rc >= K ? rc - K : rc + (gl::P - K);
-                t.c[round][q][v] = 4503599627370496.0 + (double)(u32)x;
-                t.c[round][q][4 + v] = 4503599627370496.0 + (double)(u32)(x >> 32);
-            }
-    // words 12..15 = ONE = 0x00000000ffffffff (Montgomery form of 1): low half 2^32 - 1, high half 0
-    for (int q = 0; q < 4; ++q)
-        for (int v = 0; v < 4; ++v) {
-            const int r = 4 * v + q;
-            u64 m = 0;
-            for (int c = 12; c < 16; ++c) m += col[(r - c) & 15];
-            t.cf[q][v] = t.c[0][q][v] + (double)(m * 0xffffffffULL);  // < 2^50: exact, and the half-sum bound is that of the full product
-            t.cf[q][4 + v] = t.c[0][q][4 + v];
-        }
-}
-
-struct Tip5MxLds {
-    Tip5MxConsts t;
-    unsigned char lut[256];
-};
-
-__device__ __forceinline__ void stage_mx(Tip5MxLds* l) {
-    const double* src = reinterpret_cast<const double*>(&g_tip5_mx);
-    double* dst = reinterpret_cast<double*>(&l->t);
-    for (int i = threadIdx.x; i < (int)(sizeof(Tip5MxConsts) / 8); i += blockDim.x) dst[i] = src[i];
-    stage_lut(l->lut);  // ends in __syncthreads()
-}
-
-// per-lane A operands: K-block i, lane (r = l & 15, k = l >> 4) holds M[(r - 4 i - k) mod 16]
-struct MxA {
-    double v[4];
-    __device__ __forceinline__ double operator[](int i) const { return v[i]; }
-};
-__device__ __forceinline__ void mx_a_operands(const Tip5MxLds* l, MxA& aa) {
-    double (&a)[4] = aa.v;
-    const int lane = threadIdx.x & 63, r = lane & 15, k = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = l->t.a[(r - 4 * i - k) & 15];
-}
-
-#endif  // TF_TIP5_I8
 
 // four accumulator registers of the lo-half and hi-half products -> the four state words of this lane.  Word 0 (register 0: the
 // next round's split_and_lookup input, whose bytes must be those of the canonical word) is always made canonical; words 1..3
@@ -317,23 +188,6 @@ __device__ __forceinline__ void mx_a_operands(const Tip5MxLds* l, MxA& aa) {
 // arbitrary 64-bit words is a correct, possibly non-canonical, 64-bit representative: montyred's subtrahend is < p, so at most one
 // "+ p" is ever needed), and the MDS is linear in the integer value of a word, so a representative that is p too large changes a
 // sum by a multiple of p.  The last round of a permutation runs with CANON: everything that leaves the registers is canonical.
-template <bool CANON>
-__device__ __forceinline__ void mx_fold4_tail(u32 (&tl)[4], u32 (&th)[4], const u32 (&h0)[4], u64* out);
-#if !TF_TIP5_I8
-template <bool CANON>
-__device__ __forceinline__ void mx_fold4(const d4 dlo, const d4 dhi, u64* out) {
-    u32 tl[4], th[4], h0[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const u64 rawlo = (u64)__double_as_longlong(dlo[v]), rawhi = (u64)__double_as_longlong(dhi[v]);
-        const u64 t1 = (u64)(u32)(rawhi >> 32) * 0xffffffffu + rawlo;  // < 2^63.1: rawlo < 2^62.1, (rawhi >> 32) < 2^30.1
-        tl[v] = (u32)t1;
-        th[v] = (u32)(t1 >> 32);
-        h0[v] = (u32)rawhi;
-    }
-    mx_fold4_tail<CANON>(tl, th, h0, out);
-}
-#endif
 // value = (th : tl) + h0 * 2^32, th : tl < 2^63.1 + 2^47: add h0 to the high word (carry k: the value is t + k 2^64 = t + k (2^32 - 1)),
 // fold the carry; word 0 canonical always, words 1..3 when CANON
 template <bool CANON>
@@ -406,21 +260,6 @@ __device__ __forceinline__ void mx_fold4_tail(u32 (&tl)[4], u32 (&th)[4], const 
 // One round on NS permutations per lane quartet: s[4 n + i] = word 4 i + q of the permutation in column j of column block n.
 // the canonical recombination of words 0 and 1 only: the last round of hash_10 / hash_pair, whose digest is state words 0..4
 // (registers 0 of the four quarters and register 1 of quarter 0)
-__device__ __forceinline__ void mx_fold2_tail(u32 (&tl)[2], u32 (&th)[2], const u32 (&h0)[2], u64* out);
-#if !TF_TIP5_I8
-__device__ __forceinline__ void mx_fold2_canon(const d4 dlo, const d4 dhi, u64* out) {
-    u32 tl[2], th[2], h0[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const u64 rawlo = (u64)__double_as_longlong(dlo[v]), rawhi = (u64)__double_as_longlong(dhi[v]);
-        const u64 t1 = (u64)(u32)(rawhi >> 32) * 0xffffffffu + rawlo;
-        tl[v] = (u32)t1;
-        th[v] = (u32)(t1 >> 32);
-        h0[v] = (u32)rawhi;
-    }
-    mx_fold2_tail(tl, th, h0, out);
-}
-#endif
 __device__ __forceinline__ void mx_fold2_tail(u32 (&tl)[2], u32 (&th)[2], const u32 (&h0)[2], u64* out) {
     u32 rl[2], rh[2];
     u64 ka, kb, ea, eb, na, nb;
@@ -477,7 +316,6 @@ __device__ __forceinline__ void tip5_round_mx(u64 (&s)[4 * NS], int round, const
             s[4 * n + 1] = x[0], s[4 * n + 2] = x[1], s[4 * n + 3] = x[2];
         }
     }
-#if TF_TIP5_I8
     // ---- the MDS on the i8 matrix pipe (see Tip5MxConsts): ten planes, twelve MFMA
     const int* cp = FIXED0 == 1 ? &l->cf[0][q][0] : (FIXED0 == 2 ? &l->cz[0][q][0] : &l->c[round][0][q][0]);  // [plane][q][t]: 16 ints per plane
     constexpr int NW = FIXED0 ? 3 : 4;  // registers that go into B (FIXED0: register 3 -- words 12..15 -- is a constant, folded into the starts)
@@ -529,25 +367,6 @@ __device__ __forceinline__ void tip5_round_mx(u64 (&s)[4 * NS], int round, const
         if constexpr (DIGEST) mx_fold2_tail(tl, th, h0, &s[4 * n]);
         else mx_fold4_tail<LAST>(tl, th, h0, &s[4 * n]);
     }
-#else
-    const d4* cp = reinterpret_cast<const d4*>(FIXED0 == 1 ? &l->t.cf[q][0] : &l->t.c[round][q][0]);
-    const d4 c_lo = cp[0], c_hi = cp[1];
-    d4 dlo[NS], dhi[NS];
-#pragma unroll
-    for (int n = 0; n < NS; ++n) dlo[n] = c_lo, dhi[n] = c_hi;
-#pragma unroll
-    for (int i = 0; i < (FIXED0 ? 3 : 4); ++i)
-#pragma unroll
-        for (int n = 0; n < NS; ++n) {
-            dlo[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], (double)(u32)s[4 * n + i], dlo[n], 0, 0, 0);
-            dhi[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], (double)(u32)(s[4 * n + i] >> 32), dhi[n], 0, 0, 0);
-        }
-#pragma unroll
-    for (int n = 0; n < NS; ++n) {
-        if constexpr (DIGEST) mx_fold2_canon(dlo[n], dhi[n], &s[4 * n]);  // (words 8..15 of the final state are not part of a digest)
-        else mx_fold4<LAST>(dlo[n], dhi[n], &s[4 * n]);
-    }
-#endif
 }
 
 template <int NS>
@@ -794,7 +613,7 @@ __global__ void __launch_bounds__(256) tip5_permute_mx_kernel(u64* states, u64* 
 }
 
 // ---- cooperative form: the 16 lanes of a DPP row hold the 16 state words of ONE permutation ------------------
-// The lane-per-permutation kernels above are throughput-optimal but one permutation is a dependent chain of ~8 200
+// With the whole state in one lane's registers one permutation is a dependent chain of ~8 200
 // instructions (~19 us), which is what every level of a Merkle tree with fewer nodes than the GPU has lanes costs.
 // Here lane j of a row owns state[j]: the S-box is one lookup or one x^7 per lane, and because the MDS matrix is
 // circulant, out[r] = sum_k M[k] * state[(r - k) mod 16] is 16 row rotations (v_mov_b32 row_ror:k) each followed by one
@@ -841,7 +660,7 @@ __device__ __forceinline__ void tip5_permutation_coop(u64& s, int j, const unsig
         mds_coop_terms<1>(lo, hi, alo, ahi);
         asm("" : "+v"(alo[1]), "+v"(ahi[1]));  // (keeps the compiler from folding the odd chains back into the even ones)
         const u64 slo = alo[0] + alo[1], shi = ahi[0] + ahi[1];  // < 2^52 each
-        // same single-fold reduction as tip5_round
+        // single-fold reduction, as in the lane-per-permutation round
         const u64 rc = rcs[round];
         unsigned c0, c1, c2, c3, c4;
         const u32 w1 = __builtin_addc((u32)(slo >> 32), (u32)shi, 0u, &c0);
