@@ -34,6 +34,8 @@ BARY_ROWS_PER_BLOCK = 2        # rpb
 BARY_MAX_BATCH = GRID_Y * BARY_ROWS_PER_BLOCK - 1   # the denominator is one more row: 131 069
 DIVIDE_MAX_BATCH = 65535       # kMaxDivideBatch
 CLEAN_DIVIDE_MAX_BATCH = 65535
+TREE_LEVEL_WORDS = 1 << 22     # words of a walk's level up to which it is ONE launch (tree_level_wanted) ...
+TREE_FUSE_LINES = 1 << 22      # ... and lines below which its steps ride on the latency-shaped transform (tree_fuse), 64 .. 4096 points a line
 
 # (file under twenty-first_amd/csrc, text, occurrences) -- the literal at its site
 SITES = [
@@ -60,6 +62,13 @@ SITES = [
     ("tf_poly.hip", "((long long)batch + 1 + rpb - 1) / rpb;", 1),
     ("tf_poly.hip", f"if (row_groups > {GRID_Y}) return TF_ERR_LEN_TOO_LARGE;", 1),
     ("tf_poly.hip", f"if (batch > {CLEAN_DIVIDE_MAX_BATCH}) return TF_ERR_LEN_TOO_LARGE;", 1),        # clean_divide_dev
+    ("tf_lat.hip", "constexpr long long limit = 1ll << 22;", 2),                                        # tree_level_wanted, tree_build_level_wanted
+    ("tf_lat.hip", "return lines * order * L <= limit;", 1),                                            # tree_level_wanted
+    ("tf_lat.hip", "if (order < 64 || order > 4096 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;", 1),
+    ("tf_poly.hip", "if (order > 4096 || order < 64 || g_min_passes.load(std::memory_order_relaxed) != 0) return false;", 1),   # tree_fuse
+    ("tf_poly.hip", "if (lines >= (1ll << 22)) return false;", 1),                                      # tree_fuse
+    ("tf_poly.hip", "if (tree_level_wanted(2 * d, all, L, false)) {", 1),                               # the walk down: one launch first, fused next
+    ("tf_poly.hip", "if (tree_fuse(2 * d, all, L)) {", 1),
     ("tf_divide.hip", f"constexpr size_t kMaxDivideBatch = {DIVIDE_MAX_BATCH};", 1),
     ("tf_divide.hip", "if (batch > kMaxDivideBatch ||", 1),
     ("tf_algebra.hip", f"unsigned rows_dim(size_t rows) {{ return (unsigned)std::min<size_t>(rows, {GRID_Y}); }}", 1),

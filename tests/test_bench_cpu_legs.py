@@ -96,4 +96,4 @@ def test_stored_counter_records_belong_to_this_build(tf):
     want = tf.lib().tf_source_hash().decode().replace("-ab", "")
     for name in ("hbm_traffic_ntt.json", "valu_counts.json", "pipeline_counters.json"):
         rec = json.load(open(os.path.join(ROOT, "profiles", name)))
-        assert rec["library"]["source_hash"] == want, f"profiles/{name} was recorded on build {rec['library']['source_hash']}, the sources are {want}: re-run tools/r06_final_session.sh a"
+        assert rec["library"]["source_hash"] == want, f"profiles/{name} was recorded on build {rec['library']['source_hash']}, the sources are {want}: re-take the three records: the passes of tools/prof_r02.sh over tools/prof_target.py, once more with --ntt 0 --merkle 0 --coset 0 --pipeline N, then tools/make_profile_records.py and tools/make_pipeline_record.py"

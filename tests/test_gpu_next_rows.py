@@ -1444,3 +1444,110 @@ def test_two_pass_plan_over_several_batch_tiles(tf, oracle):
             assert np.array_equal(y, x)
     finally:
         lib.tf_set_ntt_tile_bytes(keep)
+
+
+def test_fast_square_truncating_inverse_over_the_extension_field_in_a_batch(tf, oracle):
+    """fast_square at the first order whose inverse transform truncates over XFieldElement (2^15: the last radix is 1024 there and
+    at 2^20 only): the square of 8193 coefficients has 16 385, a batch of 2 stores them 3 * 16 385 words apart straight from the last
+    pass.  Word for word the oracle's product."""
+    import ctypes as C
+
+    na, width, batch = 8193, 3, 2
+    # can_truncate(order, 3): a plan of at most three passes whose last radix is 1024 -- at 2^15, at no XFieldElement order below
+    radix, last = (C.c_int * 4)(), {}
+    for k in range(11, 16):
+        passes = tf.lib().tf_ntt_plan(1 << k, width, radix)
+        last[k] = radix[passes - 1]
+    assert last[15] == 10 and all(last[k] != 10 for k in range(11, 15)), last
+    assert 1 << 14 < 2 * na - 1 <= 1 << 15
+    a = oracle.fill_random(na * width * batch, 0x5A15)
+    got = tf.fast_square(a, width=width, batch=batch).reshape(batch, -1)
+    for k in range(batch):
+        ak = a[k * na * width:(k + 1) * na * width]
+        assert np.array_equal(got[k], oracle.poly_mul(ak, ak, width=width)), k
+
+
+class _latency_kernel_forced:
+    """tf_set_ntt_latency_kernel(1) around a call, automatic again afterwards"""
+
+    def __init__(self, tf):
+        self.lib = tf.lib()
+
+    def __enter__(self):
+        self.lib.tf_set_ntt_latency_kernel(1)
+
+    def __exit__(self, *exc):
+        self.lib.tf_set_ntt_latency_kernel(-1)
+
+
+def _fused_levels(m, units, stop_leaf=256):
+    """the levels (points per line 2d, lines) of a BFieldElement walk down a tree of m padded points by `units` units that take the
+    fused launch_lat calls while the latency-shaped transform is forced (lat_wanted then holds for every line of 64 .. 4096 points):
+    more words than one launch per level takes (tree_level_wanted), fewer lines than the fused launches' limit (tree_fuse).  The
+    two rules' literals and the order in which the walk asks them are pinned at their sites by tests/slab_ref.py."""
+    from tests import slab_ref as S
+
+    out = []
+    d = stop_leaf
+    while d < m:
+        order, lines = 2 * d, units * (m // d)
+        if 64 <= order <= 4096 and lines * order > S.TREE_LEVEL_WORDS and lines < S.TREE_FUSE_LINES:
+            out.append((order, lines))
+        d *= 2
+    return out
+
+
+def test_fused_walk_levels_of_many_base_field_units(tf, oracle):
+    """The walk down with the reversals and the remainder riding on the latency-shaped transform's load and store (the four
+    launch_lat calls of zerofier_tree_evaluate).  Over BFieldElement the automatic plan takes the one-launch-per-level kernel
+    wherever that transform applies, so these calls run only with the transform forced on a level of more than 2^22 words: 2049
+    polynomials of 700 coefficients on a tree of 513 points (M = 1024: levels of 2 x 2049 lines of 1024 and 4 x 2049 of 512).
+    The rows are a rank-2 family (tests/slab_ref.py); expected a_r E0 + b_r E1 from the oracle's Horner values of the two base rows."""
+    import torch
+
+    from tests import slab_ref as S
+
+    n_points, n_coeffs, batch = 513, 700, 2049
+    m = S.padded_points(n_points, S.INTERP_LEAF)
+    assert m == 1024 and n_coeffs <= m
+    pts = oracle.fill_random(n_points, 0xF05E)
+    f0, f1 = oracle.fill_random(n_coeffs, 0xF05F), oracle.fill_random(n_coeffs, 0xF060)
+    a, b = S.scalars(oracle, batch, 0xF061)
+    rows = S.family(oracle, f0, f1, a, b)
+    out = torch.empty(batch * n_points, dtype=torch.int64, device="cuda")
+    with tf.device.ZerofierTree(_to_dev(pts)) as tree:
+        with _latency_kernel_forced(tf):
+            assert _fused_levels(m, batch) == [(512, 4 * batch), (1024, 2 * batch)]     # every level of this walk
+            assert _fused_levels(m, batch - 1) == []                                     # (one unit fewer: one launch per level)
+            tree.batch_evaluate(_to_dev(rows.reshape(-1)), n_coeffs, out, batch=batch)
+        torch.cuda.synchronize()
+    bad = S.family_mismatch(oracle, _to_host(out), S.horner(oracle, f0, pts, 1), S.horner(oracle, f1, pts, 1), a, b)
+    assert bad is None, f"row {bad[0]} word {bad[1]}: got {bad[2]:#x}, expected {bad[3]:#x}"
+
+
+def test_fused_walk_levels_of_one_base_field_polynomial(tf, oracle):
+    """The same levels for ONE polynomial, where the product with the level's cached transform rides on the inverse transform's
+    load (in2): a level of one unit has more than 2^22 words from 2^22 points on, which no O(n^2) oracle reaches as a whole.  So
+    this is NOT a word-for-word comparison of every value with the oracle: the values of 2^22 coefficients at 2^22 points, taken
+    with the transform forced, interpolate back to the coefficients on the automatic plan (interpolation is a bijection: one wrong
+    value changes the coefficients), and sixteen of them, spread over the leaves, are the oracle's Horner values.  0.3 s on an MI355X
+    (tree, both walks and the sixteen Horner sums of 2^22 terms on the host)."""
+    import torch
+
+    n = 1 << 22
+    dom = torch.empty(n, dtype=torch.int64, device="cuda")
+    f = torch.empty(n, dtype=torch.int64, device="cuda")
+    tf.device.fill_random(dom, 0xF062)
+    tf.device.fill_random(f, 0xF063)
+    vals, back = torch.empty_like(f), torch.empty_like(f)
+    with tf.device.ZerofierTree(dom) as tree:
+        with _latency_kernel_forced(tf):
+            assert _fused_levels(n, 1) == [(512, n // 256), (1024, n // 512), (2048, n // 1024), (4096, n // 2048)]
+            assert _fused_levels(n // 2, 1) == []                                        # (half the points: one launch per level)
+            tree.batch_evaluate(f, n, vals)
+        tree.interpolate(vals, back)
+        torch.cuda.synchronize()
+    assert torch.equal(back, f)
+    c, p, v = _to_host(f), _to_host(dom), _to_host(vals)
+    for i in [0, 1, 255, 256, 54321, n // 2 - 1, n // 2, n - 1] + [(k * 0x9E3779B1) % n for k in range(1, 9)]:
+        assert int(v[i]) == int(oracle.poly_eval(c, int(p[i]))[0]), i

@@ -1359,7 +1359,7 @@ __global__ void __launch_bounds__(256) build_split_powers_kernel(u64* tab, u64 b
 }
 
 // out[c * n + j] = base_c^j by square-and-multiply in every thread (at most 2 log2 n products per word): the TEMPORARY power tables of
-// get_pow_table, which must not leave the caller's stream (the split-table builder above uploads host-built tables and waits for them)
+// PowTable::acquire, which must not leave the caller's stream (the split-table builder above uploads host-built tables and waits for them)
 struct PowBases {
     u64 base[64];  // kMaxCosetSplit
 };

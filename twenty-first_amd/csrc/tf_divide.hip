@@ -54,7 +54,9 @@ int bcast_mul(u64* A, const u64* B, long long period, long long total, hipStream
 int xform(DeviceCtx* ctx, const u64* in, long long in_bs, long long n_coeffs, u64* out, long long out_bs, size_t n, size_t batch, int L,
           bool inverse, hipStream_t s) {
     if (n == 1) return copy_pad(in, in_bs, (n_coeffs < 0 ? 1 : std::min<long long>(n_coeffs, 1)) * L, out, out_bs, L, (long long)batch, s);
-    return run_ntt(ctx, in, out, in_bs, out_bs, n, batch, L, inverse, nullptr, n_coeffs < (long long)n ? n_coeffs : -1, s);
+    NttCall c(in, out, n, batch, L, inverse);
+    c.in_bs = in_bs, c.out_bs = out_bs, c.n_coeffs = n_coeffs < (long long)n ? n_coeffs : -1;
+    return run_ntt(ctx, c, s);
 }
 
 // dst (batch x N elements) = the rows of src (len elements each, src_bs words apart) folded modulo x^N - 1; long rows fold in steps

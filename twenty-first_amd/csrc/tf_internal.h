@@ -1,7 +1,7 @@
 // tf_internal.h -- what the translation units of libtf_hip.so share on the host side (nothing here is part of the ABI: the
 // library is built with -fvisibility=hidden and only the tf_* functions of include/tf_hip.h are exported).
 //   tf_plan.hip   the NTT planner (ntt_plan.h): route, passes, radices, tiles and streams of a call -- host logic only, no kernel
-//   tf_ntt.hip    device context, table caches, run_ntt (plan, then execute) and every launcher of ntt_kernels.h
+//   tf_ntt.hip    device context, table caches, run_ntt(ctx, NttCall, stream) (plan, then execute) and every launcher of ntt_kernels.h
 //   tf_lat.hip    the latency-shaped transforms and the one-launch-per-level kernels of the tree walks (lat_kernels.h)
 //   tf_tip5.hip   Tip5 / Merkle launchers (tip5_kernels.h), authentication structures
 //   tf_poly.hip   the callers on either side of the path, SURVEY 8(f) (poly_kernels.h)
@@ -89,7 +89,6 @@ struct DeviceCtx {
     size_t scratch_bytes = 0;                // bytes held by blocks in scratch_free
     size_t cached_post_bytes = 0;          // inter-pass twiddle tables kept for the life of the process (guarded by mu)
     size_t cached_pow_bytes = 0;           // coset power tables kept for the life of the process (guarded by mu)
-    std::map<const u64*, ScratchBlock> temp_pow;  // temporary power tables in flight: scratch blocks, given back by release_pow_table (guarded by mu)
 };
 
 constexpr int kMaxDevices = 64;
@@ -126,8 +125,30 @@ int temp_guard_report(uint64_t* ledger, uint64_t* label_blocks, uint64_t* label_
 const char* temp_guard_label(size_t id);
 int temp_guard_selftest(int defect, size_t n_words, uint64_t* out_word);
 int ensure_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done_mask);
-int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, const u64** out, bool* temp, size_t cosets = 1, int log_order = 0);
-void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t stream);  // after the launches that read a table get_pow_table returned
+// offset^j tables of the coset transforms, owned for the scope of the call that reads them (in the style of DevTemp, tf_temp.h).
+// cosets = 1: table[j] = offset^j, j < n.  cosets = C > 1 (the blown-up coset evaluation, NttCall::cosets; C <= kMaxCosetSplit): C
+// tables back to back, table[c * n + j] = (offset * w^c)^j with w the root of unity of order 2^log_order.  At most 16 tables /
+// kPowCacheBudget bytes (tf_ntt.hip) per device stay cached for the life of the process; a table beyond that is a block of the scratch cache, private to this
+// owner, which release() -- or the destructor, on any early return -- hands back on the stream behind the launches enqueued so far.
+class PowTable {
+   public:
+    PowTable(DeviceCtx* ctx, hipStream_t stream) : ctx_(ctx), s_(stream) {}
+    PowTable(const PowTable&) = delete;
+    PowTable& operator=(const PowTable&) = delete;
+    ~PowTable() { release(); }
+    int acquire(u64 offset_raw, size_t n, size_t cosets = 1, int log_order = 0);
+    const u64* get() const { return table_; }
+    void release() {  // (a cached table holds no block: nothing goes back)
+        scratch_release(ctx_, blk_, s_);
+        blk_ = DeviceCtx::ScratchBlock{}, table_ = nullptr;
+    }
+
+   private:
+    DeviceCtx* ctx_;
+    hipStream_t s_;
+    const u64* table_ = nullptr;
+    DeviceCtx::ScratchBlock blk_;  // the temporary's block; empty for a cached table
+};
 
 // keys of DeviceCtx::tables
 enum : u64 { TAG_INNER = 1, TAG_POST = 2, TAG_TINY = 3, TAG_BLOCK1 = 4, TAG_BLOCK2 = 5, TAG_LAT = 6 };
@@ -138,18 +159,50 @@ class DevTemp;  // tf_temp.h
 int get_post_table(DeviceCtx* ctx, int log_m, int a, bool inverse, hipStream_t stream, const u64** out, DevTemp* own);
 
 int check_len(size_t n);
-int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, size_t n, size_t batch, int L, bool inverse,
-            const u64* pre_scale, long long n_coeffs, hipStream_t stream, const u64* post_scale = nullptr, size_t cosets = 1,
-            const u64* in2 = nullptr, long long n_out = -1, const u64* coset_offset = nullptr);
+// One transform call: the operands and the shape, and nothing about where or how it runs.  The constructor takes what every call
+// has; the optional operands are set by name.
+struct NttCall {
+    const u64* in;  // device pointers; in == out for ntt / intt, distinct for a coset evaluation
+    u64* out;
+    size_t n, batch;  // points per transform, transforms
+    int L;            // words per element (1 BFieldElement, 3 XFieldElement)
+    bool inverse;
+    long long in_bs = 0, out_bs = 0;  // words between the polynomials of the batch; 0: packed, n * L words (with_strides)
+    long long n_coeffs = -1;          // >= 0: rows >= n_coeffs of the input read as zero (the zero padding of a forward transform)
+    // >= 0 (only with can_truncate(n, L)): the last pass stores output elements j < n_out only and out_bs may be n_out * L -- the
+    // truncation of fast_multiply without a copy; `in` is then used as work space and CLOBBERED
+    long long n_out = -1;
+    const u64* pre_scale = nullptr;   // coefficient j is multiplied by pre_scale[j] on load (coset evaluation: a PowTable)
+    const u64* post_scale = nullptr;  // output j is multiplied by post_scale[j] on store (coset interpolation; inverse only)
+    const u64* in2 = nullptr;         // the pointwise product in[j] * in2[j] is what is transformed (batch stride in_bs as well)
+    const u64* coset_offset = nullptr;  // host pointer to the offset behind pre_scale, for the table with offset^b folded in (c8)
+    // C > 1 (forward coset evaluation only, n > 1024): the output has C * n points per polynomial, out[j * C + c] = (transform of
+    // the coefficients scaled by pre_scale[c * n_coeffs + .])[j] -- the evaluation on the coset of order C * n done as C transforms
+    // of length n whose outputs interleave (w_{Cn}^(jC + c) = w_{Cn}^c * w_n^j).  The first pass reads the coefficients once per c
+    // and writes rows (k_1, c); from there on it is the ordinary plan with N_1 * C rows.
+    size_t cosets = 1;
+    NttCall(const u64* in_, u64* out_, size_t n_, size_t batch_, int L_, bool inverse_) : in(in_), out(out_), n(n_), batch(batch_), L(L_), inverse(inverse_) {}
+};
+// the forward transform of `n_coeffs` coefficients per polynomial (packed) zero padded to n points
+inline NttCall ntt_of_coeffs(const u64* in, size_t n_coeffs, u64* out, size_t n, size_t batch, int L) {
+    NttCall c(in, out, n, batch, L, false);
+    c.in_bs = (long long)n_coeffs * L, c.n_coeffs = (long long)n_coeffs;
+    return c;
+}
+// the ONE reading of "0 means packed": run_ntt, shape_of and the launchers called directly (tf_lat.hip) take their strides through it
+inline NttCall with_strides(NttCall c) {
+    if (!c.in_bs) c.in_bs = (long long)c.n * c.L;
+    if (!c.out_bs) c.out_bs = (long long)c.n * c.L;
+    return c;
+}
+NttShape shape_of(const NttCall& c);  // what the planner sees of a call
+int run_ntt(DeviceCtx* ctx, const NttCall& c, hipStream_t stream);
 int ntt_dev(u64* d_x, size_t n, size_t batch, int L, int inverse, void* stream);
 int coset_eval_dev(const u64* d_coeffs, size_t n_coeffs, u64 offset_raw, u64* d_out, size_t order, size_t batch, int L, void* stream);
 // ------------------------------------------------------------------------------------ tf_lat.hip
-// latency-shaped transforms and the one-launch-per-level kernels of the zerofier-tree walks
-int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
-                long long n_coeffs, const u64* in2, hipStream_t stream, const u64* pre_scale = nullptr, const u64* post_scale = nullptr);
-int launch_lat(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
-               long long n_coeffs, const u64* in2, hipStream_t stream, const tfk::NttLatArgs* mods = nullptr, const u64* pre_scale = nullptr,
-               const u64* post_scale = nullptr);
+// latency-shaped transforms (mods: the tree walks' load / store modifiers) and the one-launch-per-level kernels of the tree walks
+int launch_lat2(DeviceCtx* ctx, const NttCall& c, hipStream_t stream);
+int launch_lat(DeviceCtx* ctx, const NttCall& c, hipStream_t stream, const tfk::NttLatArgs* mods = nullptr);
 int get_lat_table(DeviceCtx* ctx, int log_n, bool inverse, const u64** out, int scale_log);  // (scale_log < 0: log_n)
 bool tree_level_wanted(long long order, long long lines, int L = 1, bool up = false);
 template <bool UP>

@@ -65,30 +65,31 @@ int launch_lat_dir(int log_n, const tfk::NttLatArgs& a, hipStream_t s) {
 }
 // (when: lat_wanted, tf_plan.hip)
 // mods (tree walks only): the load / store modifier fields of NttLatArgs; such calls are one launch (batch < 2^22)
-int launch_lat(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
-               long long n_coeffs, const u64* in2, hipStream_t stream, const tfk::NttLatArgs* mods, const u64* pre_scale, const u64* post_scale) {
+int launch_lat(DeviceCtx* ctx, const NttCall& unresolved, hipStream_t stream, const tfk::NttLatArgs* mods) {
+    const NttCall c = with_strides(unresolved);
+    const int log_n = ilog2(c.n);
     const u64* tw = nullptr;
-    int rc = get_lat_table(ctx, log_n, inverse, &tw);
+    int rc = get_lat_table(ctx, log_n, c.inverse, &tw);
     if (rc) return rc;
     const size_t max_batch = size_t(1) << 22;  // 2^31 threads per launch at most
-    if (mods && batch > max_batch) return TF_ERR_HIP;
-    for (size_t b0 = 0; b0 < batch && !rc; b0 += max_batch) {
-        const size_t nb = std::min(max_batch, batch - b0);
+    if (mods && c.batch > max_batch) return TF_ERR_HIP;
+    for (size_t b0 = 0; b0 < c.batch && !rc; b0 += max_batch) {
+        const size_t nb = std::min(max_batch, c.batch - b0);
         tfk::NttLatArgs a{};
         if (mods) a = *mods;
-        a.in = in + (long long)b0 * in_bs;
-        a.out = out + (long long)b0 * out_bs;
-        a.in2 = in2 ? in2 + (long long)b0 * in_bs : nullptr;
-        a.pre_scale = pre_scale;
-        a.post_scale = post_scale;
+        a.in = c.in + (long long)b0 * c.in_bs;
+        a.out = c.out + (long long)b0 * c.out_bs;
+        a.in2 = c.in2 ? c.in2 + (long long)b0 * c.in_bs : nullptr;
+        a.pre_scale = c.pre_scale;
+        a.post_scale = c.post_scale;
         a.tw = tw;
-        a.n_coeffs = n_coeffs;
-        a.in_bs = in_bs;
-        a.out_bs = out_bs;
-        a.total = (long long)nb * L;
-        a.ninv = inverse ? gl::mont_inverse(gl::to_mont(u64(1) << log_n)) : 0;
-        a.L = L;
-        rc = inverse ? launch_lat_dir<true>(log_n, a, stream) : launch_lat_dir<false>(log_n, a, stream);
+        a.n_coeffs = c.n_coeffs;
+        a.in_bs = c.in_bs;
+        a.out_bs = c.out_bs;
+        a.total = (long long)nb * c.L;
+        a.ninv = c.inverse ? gl::mont_inverse(gl::to_mont(u64(1) << log_n)) : 0;
+        a.L = c.L;
+        rc = c.inverse ? launch_lat_dir<true>(log_n, a, stream) : launch_lat_dir<false>(log_n, a, stream);
     }
     return rc;
 }
@@ -213,8 +214,10 @@ int launch_lat2_dir(int log_n, const tfk::NttLat2Args& a, size_t batch, hipStrea
     return TF_ERR_HIP;
 }
 // (when: lat2_wanted, tf_plan.hip)
-int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, int L, bool inverse,
-                long long n_coeffs, const u64* in2, hipStream_t stream, const u64* pre_scale, const u64* post_scale) {
+int launch_lat2(DeviceCtx* ctx, const NttCall& unresolved, hipStream_t stream) {
+    const NttCall call = with_strides(unresolved);
+    const int log_n = ilog2(call.n), L = call.L;
+    const bool inverse = call.inverse;
     const int a1 = (log_n + 1) / 2, a2 = log_n - a1;
     const long long N1 = 1ll << a1, N2 = 1ll << a2, n = 1ll << log_n;
     const u64 *tw1 = nullptr, *tw2 = nullptr, *post = nullptr;
@@ -223,45 +226,45 @@ int launch_lat2(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long l
     TRY(get_lat_table(ctx, a2, inverse, &tw2, inverse ? log_n : 0));
     TRY(get_post_table(ctx, log_n, a1, inverse, stream, &post, &post_own));
     DeviceCtx::ScratchBlock sblk;
-    TRY(scratch_acquire(ctx, batch * (size_t)n * L * sizeof(u64), stream, &sblk, "lat2 inter-pass scratch"));
+    TRY(scratch_acquire(ctx, call.batch * (size_t)n * L * sizeof(u64), stream, &sblk, "lat2 inter-pass scratch"));
     tfk::NttLat2Args c{};  // column pass: the caller's input -> scratch
-    c.in = in;
+    c.in = call.in;
     c.out = sblk.p;
-    c.in2 = in2;
+    c.in2 = call.in2;
     c.tw = tw1;
     c.post_tw = post;
-    c.n_coeffs = n_coeffs;
+    c.n_coeffs = call.n_coeffs;
     c.nc_es = N2;
-    c.in_bs = in_bs;
+    c.in_bs = call.in_bs;
     c.out_bs = n * L;
     c.lines = N2 * L;
     c.in_es = c.out_es = N2 * L;
     c.in_lhi = c.out_lhi = L;
     c.tw_rs = N2;
-    c.scale_tab = pre_scale;
+    c.scale_tab = call.pre_scale;
     c.scale_es = N2;
     c.L = L;
     c.cfast = 1;
-    int rc = inverse ? launch_lat2_dir<true, false>(a1, c, batch, stream) : launch_lat2_dir<false, false>(a1, c, batch, stream);
+    int rc = inverse ? launch_lat2_dir<true, false>(a1, c, call.batch, stream) : launch_lat2_dir<false, false>(a1, c, call.batch, stream);
     if (!rc) {
         tfk::NttLat2Args r{};  // last pass: rows of the scratch -> natural order in the caller's output
         r.in = sblk.p;
-        r.out = out;
+        r.out = call.out;
         r.tw = tw2;
         r.n_coeffs = -1;
         r.in_bs = n * L;
-        r.out_bs = out_bs;
+        r.out_bs = call.out_bs;
         r.lines = N1 * L;
         r.in_es = L;
         r.in_lhi = N2 * L;
         r.out_es = N1 * L;
         r.out_lhi = L;
         r.scale = inverse ? gl::mont_inverse(gl::to_mont(u64(1) << log_n)) : 0;
-        r.scale_tab = post_scale;
+        r.scale_tab = call.post_scale;
         r.scale_es = N1;
         r.L = L;
         r.cfast = 0;
-        rc = inverse ? launch_lat2_dir<true, true>(a2, r, batch, stream) : launch_lat2_dir<false, true>(a2, r, batch, stream);
+        rc = inverse ? launch_lat2_dir<true, true>(a2, r, call.batch, stream) : launch_lat2_dir<false, true>(a2, r, call.batch, stream);
     }
     scratch_release(ctx, sblk, stream);
     return rc;

@@ -535,10 +535,7 @@ int get_tiny_table(DeviceCtx* ctx, int log_n, bool inverse, const u64** out) {
     return TF_OK;
 }
 
-// offset^j, j < n  (the power chain of Polynomial::scale, polynomial.rs:766-771).
-// Up to 16 tables per device are cached for the life of the process; beyond that a table is built into a
-// stream-ordered temporary (*temp = true) that the caller releases with release_pow_table after its launches, so no
-// table another thread may still be using is ever freed.
+// offset^j, j < n  (the power chain of Polynomial::scale, polynomial.rs:766-771): the builder of the CACHED tables (PowTable::acquire)
 int build_pow_tables(u64 offset_raw, u64 w, size_t cosets, size_t n, u64* d, hipStream_t s) {
     // table c (c < cosets) = powers of base_c = offset * w^c: out[c * n + j] = base_c^j = HI_c[j >> h] * LO_c[j & (2^h - 1)].
     // The split tables of ALL cosets go up in one allocation and ONE kernel fills every table (grid.y = coset).
@@ -571,33 +568,30 @@ int build_pow_tables(u64 offset_raw, u64 w, size_t cosets, size_t n, u64* d, hip
     return TF_OK;
 }
 
-// cosets = 1: out[j] = offset^j, j < n.  cosets = C > 1 (blown-up coset evaluation, see run_ntt; C <= kMaxCosetSplit): C tables
-// back to back, out[c * n + j] = (offset * w_{C * len}^c)^j with len the power-of-two transform length the n coefficients are
-// padded to.  At most 16 tables / kPowCacheBudget bytes stay cached; anything beyond is a stream-ordered temporary (*temp).
-int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, const u64** out, bool* temp, size_t cosets,
-                  int log_order) {
-    *temp = false;
-    std::unique_lock<std::mutex> lk(ctx->mu);
+// (class PowTable: tf_internal.h)  A cached table is never freed while another thread may use it; a temporary is private to its owner.
+int PowTable::acquire(u64 offset_raw, size_t n, size_t cosets, int log_order) {
+    release();
+    std::unique_lock<std::mutex> lk(ctx_->mu);
     auto key = std::make_pair(offset_raw, u64(n) | (u64(cosets) << 40) | (u64(log_order) << 56));
-    auto it = ctx->pow_tables.find(key);
-    if (it != ctx->pow_tables.end()) {
-        *out = it->second;
+    auto it = ctx_->pow_tables.find(key);
+    if (it != ctx_->pow_tables.end()) {
+        table_ = it->second;
         return TF_OK;
     }
     const size_t words = std::max<size_t>(n * cosets, 1);
-    const bool cacheable = ctx->pow_tables.size() < 16 && ctx->cached_pow_bytes + words * sizeof(u64) <= kPowCacheBudget;
+    const bool cacheable = ctx_->pow_tables.size() < 16 && ctx_->cached_pow_bytes + words * sizeof(u64) <= kPowCacheBudget;
     const u64 w = cosets > 1 ? root_of_unity_mont(log_order) : gl::ONE;
-    u64* d = nullptr;
     if (cacheable) {
+        u64* d = nullptr;
         HIPCHK(hipMalloc(&d, words * sizeof(u64)));
         int rc = build_pow_tables(offset_raw, w, cosets, n, d, 0);
         if (rc) {
             (void)hipFree(d);
             return rc;
         }
-        ctx->pow_tables[key] = d;
-        ctx->cached_pow_bytes += words * sizeof(u64);
-        *out = d;
+        ctx_->pow_tables[key] = d;
+        ctx_->cached_pow_bytes += words * sizeof(u64);
+        table_ = d;
         return TF_OK;
     }
     lk.unlock();  // a temporary is private to this call: build it without holding the device context
@@ -606,43 +600,25 @@ int get_pow_table(DeviceCtx* ctx, u64 offset_raw, size_t n, hipStream_t stream, 
     // built by one kernel instead, every word by square-and-multiply; (2) hipFreeAsync of a pool block behind the launches blocked the
     // host for the depth of the queue (0.8-1.0 ms per call, measured around that one call) when several streams share the pool -- the
     // temporary therefore lives in a block of the scratch cache (hipMalloc'ed blocks handed on with event fences, no stream-ordered free).
-    DeviceCtx::ScratchBlock blk;
-    int rc = scratch_acquire(ctx, words * sizeof(u64), stream, &blk, "temporary power table");
-    if (rc) return rc;
-    d = blk.p;
-    {
-        tfk::PowBases pb{};
-        u64 base = offset_raw;
-        for (size_t c = 0; c < cosets && c < 64; ++c) {
-            pb.base[c] = base;
-            base = gl::mont_mul(base, w);
-        }
-        if (n) hipLaunchKernelGGL(tfk::build_pow_tables_direct_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)cosets), dim3(256), 0, stream, d, pb, (long long)n);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            scratch_release(ctx, blk, stream);
-            return hip_fail(e, "build_pow_tables_direct_kernel", __FILE__, __LINE__);
-        }
+    int rc = scratch_acquire(ctx_, words * sizeof(u64), s_, &blk_, "temporary power table");
+    if (rc) {
+        blk_ = DeviceCtx::ScratchBlock{};  // (nothing of ours to give back)
+        return rc;
     }
-    {
-        std::lock_guard<std::mutex> lk2(ctx->mu);
-        ctx->temp_pow[d] = blk;
+    tfk::PowBases pb{};
+    u64 base = offset_raw;
+    for (size_t c = 0; c < cosets && c < 64; ++c) {
+        pb.base[c] = base;
+        base = gl::mont_mul(base, w);
     }
-    *temp = true;
-    *out = d;
+    if (n) hipLaunchKernelGGL(tfk::build_pow_tables_direct_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)cosets), dim3(256), 0, s_, blk_.p, pb, (long long)n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        release();
+        return hip_fail(e, "build_pow_tables_direct_kernel", __FILE__, __LINE__);
+    }
+    table_ = blk_.p;
     return TF_OK;
-}
-void release_pow_table(DeviceCtx* ctx, const u64* table, bool temp, hipStream_t stream) {
-    if (!temp || !table) return;
-    DeviceCtx::ScratchBlock blk;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        auto it = ctx->temp_pow.find(table);
-        if (it == ctx->temp_pow.end()) return;
-        blk = it->second;
-        ctx->temp_pow.erase(it);
-    }
-    scratch_release(ctx, blk, stream);
 }
 
 // The inter-pass table of a forward first pass with the COLUMN part of a coset evaluation's scaling folded in: T'[k B + b] =
@@ -665,9 +641,8 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
     const u64* T = nullptr;
     DevTemp t_own(stream);  // (given back behind the build below)
     TRY(get_post_table(ctx, log_m, a, false, stream, &T, &t_own));
-    const u64* S = nullptr;
-    bool s_temp = false;
-    TRY(get_pow_table(ctx, offset_raw, (size_t)B, stream, &S, &s_temp));
+    PowTable S(ctx, stream);  // (given back behind the build below)
+    TRY(S.acquire(offset_raw, (size_t)B));
     bool cache;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
@@ -677,11 +652,11 @@ int get_scaled_post_table(DeviceCtx* ctx, int log_m, int a, u64 offset_raw, hipS
     hipError_t e = cache ? hipMalloc(&d, size_t(M) * sizeof(u64))
                          : pool_malloc_async(reinterpret_cast<void**>(&d), size_t(M) * sizeof(u64), stream, "temporary scaled twiddle table");
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(tfk::scale_post_tw_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, d, T, S, B, M);
+        hipLaunchKernelGGL(tfk::scale_post_tw_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, d, T, S.get(), B, M);
         e = hipGetLastError();
         if (e == hipSuccess && cache) e = hipStreamSynchronize(stream);  // other streams may use the cached table from now on
     }
-    release_pow_table(ctx, S, s_temp, stream);
+    S.release();
     if (e != hipSuccess) {
         if (d) { if (cache) (void)hipFree(d); else (void)pool_free_async(d, stream); }
         return hip_fail(e, "scale_post_tw_kernel", __FILE__, __LINE__);
@@ -1094,19 +1069,19 @@ int launch_rows32w_n(const tfk::NttRows32Args& a, unsigned grid, int log_n, hipS
 }
 
 // batch contiguous transforms of n = 2^log_n <= 32 points (BFieldElement: <= 64)
-int launch_rows32(const u64* in, u64* out, size_t batch, int L, int log_n, bool inverse, hipStream_t stream) {
-    const int cus = device_cus();
+int launch_rows32(const NttCall& c, hipStream_t stream) {
+    const int cus = device_cus(), log_n = ilog2(c.n), L = c.L;
     tfk::NttRows32Args a{};
-    a.in = in;
-    a.out = out;
-    a.total_transforms = (long long)batch;
-    a.scale = inverse ? gl::mont_inverse(gl::to_mont(u64(1) << log_n)) : 0;
+    a.in = c.in;
+    a.out = c.out;
+    a.total_transforms = (long long)c.batch;
+    a.scale = c.inverse ? gl::mont_inverse(gl::to_mont(u64(1) << log_n)) : 0;
     a.L = L;
-    const size_t words = (batch << log_n) * size_t(L), per_tile = L == 1 ? 2048 : 2016;  // words per wave and tile
+    const size_t words = c.batch * c.n * size_t(L), per_tile = L == 1 ? 2048 : 2016;  // words per wave and tile
     const size_t tiles = (words + per_tile - 1) / per_tile, wgs = (tiles + 3) / 4;
     const unsigned grid = (unsigned)std::min(wgs, size_t(cus) * 2);  // two workgroups are resident per CU (LDS); they walk the tiles
-    if (L == 1) return inverse ? launch_rows32w_n<true, 1>(a, grid, log_n, stream) : launch_rows32w_n<false, 1>(a, grid, log_n, stream);
-    return inverse ? launch_rows32w_n<true, 3>(a, grid, log_n, stream) : launch_rows32w_n<false, 3>(a, grid, log_n, stream);
+    if (L == 1) return c.inverse ? launch_rows32w_n<true, 1>(a, grid, log_n, stream) : launch_rows32w_n<false, 1>(a, grid, log_n, stream);
+    return c.inverse ? launch_rows32w_n<true, 3>(a, grid, log_n, stream) : launch_rows32w_n<false, 3>(a, grid, log_n, stream);
 }
 
 // 2^11 <= n <= 2^14, contiguous BFieldElement transforms: whole transform per workgroup (ntt_block_kernel)
@@ -1121,27 +1096,26 @@ int launch_block_t(const tfk::NttBlockArgs& a, unsigned grid, hipStream_t stream
     return TF_OK;
 }
 
-int launch_block(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, int log_n, size_t batch, bool inverse,
-                 const u64* pre_scale, long long n_coeffs, const u64* post_scale, hipStream_t stream, const u64* in2 = nullptr,
-                 long long n_out = -1, int L = 1) {
+int launch_block(DeviceCtx* ctx, const NttCall& c, hipStream_t stream) {
+    const int log_n = ilog2(c.n);
     tfk::NttBlockArgs a{};
-    int rc = get_block_tables(ctx, log_n, inverse, &a.tw1, &a.tw2);
+    int rc = get_block_tables(ctx, log_n, c.inverse, &a.tw1, &a.tw2);
     if (rc) return rc;
-    a.in = in;
-    a.out = out;
-    a.pre_scale = pre_scale;
-    a.post_scale = post_scale;
-    a.n_coeffs = n_coeffs;
-    a.in_bs = in_bs;
-    a.out_bs = out_bs;
-    a.total_transforms = (long long)batch * L;  // limb transforms (ntt_kernels.h)
-    a.in2 = in2;
-    a.n_out = n_out;
-    a.L = L;
+    a.in = c.in;
+    a.out = c.out;
+    a.pre_scale = c.pre_scale;
+    a.post_scale = c.post_scale;
+    a.n_coeffs = c.n_coeffs;
+    a.in_bs = c.in_bs;
+    a.out_bs = c.out_bs;
+    a.total_transforms = (long long)c.batch * c.L;  // limb transforms (ntt_kernels.h)
+    a.in2 = c.in2;
+    a.n_out = c.n_out;
+    a.L = c.L;
     const int lp3 = log_n - 10, T = 16 >> lp3;
-    const unsigned grid = (unsigned)((batch * (size_t)L + T - 1) / T);
-    const bool scaled_load = pre_scale || n_coeffs >= 0, scaled_store = post_scale != nullptr;
-    if (in2) {  // the inverse transform of a product: second operand on load, truncated store
+    const unsigned grid = (unsigned)((c.batch * (size_t)c.L + T - 1) / T);
+    const bool scaled_load = c.pre_scale || c.n_coeffs >= 0, scaled_store = c.post_scale != nullptr;
+    if (c.in2) {  // the inverse transform of a product: second operand on load, truncated store
         switch (lp3) {
             case 1: return launch_block_t<1, true, 3>(a, grid, stream);
             case 2: return launch_block_t<2, true, 3>(a, grid, stream);
@@ -1149,7 +1123,7 @@ int launch_block(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long 
             default: return launch_block_t<4, true, 3>(a, grid, stream);
         }
     }
-    switch (lp3 * 2 + (inverse ? 1 : 0)) {
+    switch (lp3 * 2 + (c.inverse ? 1 : 0)) {
         case 2: return scaled_load ? launch_block_t<1, false, 1>(a, grid, stream) : launch_block_t<1, false, 0>(a, grid, stream);
         case 3: return scaled_store ? launch_block_t<1, true, 2>(a, grid, stream) : launch_block_t<1, true, 0>(a, grid, stream);
         case 4: return scaled_load ? launch_block_t<2, false, 1>(a, grid, stream) : launch_block_t<2, false, 0>(a, grid, stream);
@@ -1164,30 +1138,21 @@ int launch_block(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long 
 // (launchers of the latency-shaped kernels: tf_lat.hip)
 
 // ------------------------------------------------------------------------------------ run_ntt: plan, then execute
-// One transform call as run_ntt received it: what the route executors below share.
-struct NttCall {
-    DeviceCtx* ctx;
-    const u64* in;
-    u64* out;
-    long long in_bs, out_bs;
-    size_t n, batch;
-    int L;
-    bool inverse;
-    const u64* pre_scale;
-    long long n_coeffs;
-    hipStream_t stream;
-    const u64* post_scale;
-    size_t cosets;
-    const u64* in2;
-    long long n_out;
-    const u64* coset_offset;
-    int log_n;
-};
+// (NttCall, the one description of a transform call: tf_internal.h.  The executors of this unit take a call that went through with_strides.)
+NttShape shape_of(const NttCall& call) {
+    const NttCall c = with_strides(call);
+    NttShape s;
+    s.n = c.n, s.batch = c.batch, s.L = c.L, s.inverse = c.inverse, s.cosets = c.cosets, s.n_coeffs = c.n_coeffs, s.n_out = c.n_out;
+    s.pre_scale = c.pre_scale != nullptr, s.post_scale = c.post_scale != nullptr, s.in2 = c.in2 != nullptr, s.coset_offset = c.coset_offset != nullptr;
+    s.packed = c.in_bs == (long long)c.n * c.L && c.out_bs == (long long)c.n * c.L;
+    return s;
+}
 
 // n <= 16: one thread per transform
-int run_tiny(const NttCall& c) {
+int run_tiny(DeviceCtx* ctx, const NttCall& c, hipStream_t stream) {
+    const int log_n = ilog2(c.n);
     const u64* tw = nullptr;
-    TRY(get_tiny_table(c.ctx, c.log_n, c.inverse, &tw));
+    TRY(get_tiny_table(ctx, log_n, c.inverse, &tw));
     tfk::NttTinyArgs A{};
     A.in = c.in;
     A.out = c.out;
@@ -1198,30 +1163,31 @@ int run_tiny(const NttCall& c) {
     A.in_bs = c.in_bs;
     A.out_bs = c.out_bs;
     A.count = (long long)c.batch * c.L;
-    A.scale = (c.inverse && c.log_n > 0) ? gl::mont_inverse(gl::to_mont(u64(c.n))) : 0;
-    A.log_n = c.log_n;
+    A.scale = (c.inverse && log_n > 0) ? gl::mont_inverse(gl::to_mont(u64(c.n))) : 0;
+    A.log_n = log_n;
     A.L = c.L;
     const long long blocks = (A.count + 255) / 256;
-    hipLaunchKernelGGL(tfk::ntt_tiny_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream, A);
+    hipLaunchKernelGGL(tfk::ntt_tiny_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, A);
     HIPCHK(hipGetLastError());
     return TF_OK;
 }
 
 // n <= 1024 in one pass: a tile is whole transforms
-int run_row(const NttCall& c, const NttPlan& plan) {
+int run_row(DeviceCtx* ctx, const NttCall& c, const NttPlan& plan, hipStream_t stream) {
+    const int log_n = ilog2(c.n);
     const u64* inner = nullptr;
-    TRY(get_inner_table(c.ctx, c.log_n, c.inverse, c.inverse ? c.log_n : 0, &inner));
+    TRY(get_inner_table(ctx, log_n, c.inverse, c.inverse ? log_n : 0, &inner));
     // 2^31 columns limit per launch: split huge batches
     const size_t max_batch = size_t(1) << 24;
     for (size_t b0 = 0; b0 < c.batch; b0 += max_batch) {
         const size_t nb = std::min(max_batch, c.batch - b0);
-        Launch l = plan_row_pass(plan, c.in + b0 * c.in_bs, c.out + b0 * c.out_bs, c.in_bs, c.out_bs, nb, c.log_n, c.L);
+        Launch l = plan_row_pass(plan, c.in + b0 * c.in_bs, c.out + b0 * c.out_bs, c.in_bs, c.out_bs, nb, log_n, c.L);
         l.a.inner_tw = inner;
         l.a.pre_scale = c.pre_scale;
         l.a.post_scale = c.post_scale;
         l.a.n_coeffs = c.n_coeffs;
         l.a.in2 = c.in2 ? c.in2 + b0 * c.in_bs : nullptr;
-        TRY(launch_pass(l, c.inverse, c.stream));
+        TRY(launch_pass(l, c.inverse, stream));
     }
     return TF_OK;
 }
@@ -1296,28 +1262,25 @@ private:
 // inter-pass twiddle, same position in and out); the last pass transforms the contiguous rows of N_P elements and
 // scatters output digit k_P to  k_1 + N_1 k_2 + ... + N_1..N_{P-1} k_P  (natural order).  Everything that was decided -- passes,
 // radices, pairs, tiles, streams -- is read from the plan.
-int run_passes(const NttCall& c, const NttPlan& plan) {
-    DeviceCtx* const ctx = c.ctx;
-    const int P = plan.P, L = c.L, log_n = c.log_n;
+int run_passes(DeviceCtx* ctx, const NttCall& c, const NttPlan& plan, hipStream_t stream) {
+    const int P = plan.P, L = c.L, log_n = ilog2(c.n);
     const int (&a)[4] = plan.a;
     const bool (&pre2)[4] = plan.pre2;
-    const bool inverse = c.inverse, c8 = plan.c8;
+    const bool inverse = c.inverse, scaled_c8 = plan.c8 && c.pre_scale;  // the first pass's table has offset^b folded in (ntt_col2048_kernel)
     const size_t n = c.n, cosets = c.cosets;
-    const long long n_coeffs = c.n_coeffs, n_out = c.n_out;
-    const u64 *const pre_scale = c.pre_scale, *const post_scale = c.post_scale;
     const u64* inner[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < P; ++i)
         TRY(get_inner_table(ctx, pre2[i] ? 10 : a[i], inverse, (i == P - 1 && inverse) ? log_n : 0, &inner[i], pre2[i] ? 2 : 1));  // n^-1 rides on the last pass
     const u64* post[3] = {nullptr, nullptr, nullptr};
     // tables too large to cache: given back on the caller's stream when the call returns, behind the join of the tile streams
-    DevTemp post_own[3] = {DevTemp(c.stream), DevTemp(c.stream), DevTemp(c.stream)};
+    DevTemp post_own[3] = {DevTemp(stream), DevTemp(stream), DevTemp(stream)};
     {
         int rest = log_n;
         for (int i = 0; i + 1 < P; ++i) {
-            if (i == 0 && c8 && pre_scale) {  // the table with offset^b folded in (ntt_col2048_kernel)
-                TRY(get_scaled_post_table(ctx, rest, a[i], *c.coset_offset, c.stream, &post[i], &post_own[i]));
+            if (i == 0 && scaled_c8) {
+                TRY(get_scaled_post_table(ctx, rest, a[i], *c.coset_offset, stream, &post[i], &post_own[i]));
             } else {
-                TRY(get_post_table(ctx, rest, a[i], inverse, c.stream, &post[i], &post_own[i]));
+                TRY(get_post_table(ctx, rest, a[i], inverse, stream, &post[i], &post_own[i]));
             }
             rest -= a[i];
         }
@@ -1339,7 +1302,7 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
             side[i] = ctx->side[i];
         }
     }
-    TileScope tiles(ctx, c.stream);  // (declared after the tables: it joins and releases before they are given back)
+    TileScope tiles(ctx, stream);  // (declared after the tables: it joins and releases before they are given back)
     TRY(tiles.acquire(size_t(K) * tb * poly_bytes));
     if (K > 1) TRY(tiles.fork(K, side));
     const long long sbs = (long long)(n * cosets) * L;  // scratch batch stride
@@ -1349,7 +1312,7 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
     size_t tile_no = 0;
     for (size_t b0 = 0; b0 < c.batch && rc == TF_OK; b0 += tb, ++tile_no) {
         const size_t nb = std::min(tb, c.batch - b0);
-        hipStream_t const stream = K > 1 ? side[tile_no % K] : c.stream;
+        hipStream_t const ts = K > 1 ? side[tile_no % K] : stream;
         u64* const scratch = K > 1 ? tiles.scratch() + (tile_no % K) * tb * (size_t)sbs : tiles.scratch();
         const u64* tin = c.in + (long long)b0 * c.in_bs;
         u64* tout = c.out + (long long)b0 * c.out_bs;
@@ -1363,29 +1326,29 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
             const bool to_scratch = i == P - 2;
             // a truncated output (n_out >= 0) is smaller than the transform: the middle passes then work in place on the
             // INPUT, which the caller gives up (fast_multiply's temporary)
-            u64* dst = to_scratch ? scratch : (n_out >= 0 ? const_cast<u64*>(tin) : tout);
-            const long long dst_bs = to_scratch ? sbs : (n_out >= 0 ? c.in_bs : c.out_bs);
+            u64* dst = to_scratch ? scratch : (c.n_out >= 0 ? const_cast<u64*>(tin) : tout);
+            const long long dst_bs = to_scratch ? sbs : (c.n_out >= 0 ? c.in_bs : c.out_bs);
             Launch p = plan_column_pass(plan, src, dst, src_bs, dst_bs, nb, (i == 0) ? (long long)cosets : outer, a[i], B, L, pre2[i]);
             p.a.inner_tw = inner[i];
             p.a.post_tw = post[i];
             if (pre2[i]) {
                 // partner coefficients are n / 2 apart: offset^(n/2) is word n / 2 of the scale table when the polynomial is that long
-                p.a.pre2_cp = pre_scale ? pre_scale + ((long long)(n / 2) < n_coeffs ? (long long)(n / 2) : 0) : nullptr;
+                p.a.pre2_cp = c.pre_scale ? c.pre_scale + ((long long)(n / 2) < c.n_coeffs ? (long long)(n / 2) : 0) : nullptr;
             }
             if (i == 0) {
-                p.a.pre_scale = pre_scale;
-                if (c8 && pre_scale) p.a.ps_col = 0;  // the column part offset^b of the scaling comes with the inter-pass table
-                p.a.n_coeffs = n_coeffs;
+                p.a.pre_scale = c.pre_scale;
+                if (scaled_c8) p.a.ps_col = 0;  // the column part offset^b of the scaling comes with the inter-pass table
+                p.a.n_coeffs = c.n_coeffs;
                 p.a.in2 = c.in2 ? c.in2 + (long long)b0 * c.in_bs : nullptr;
                 if (cosets > 1) {  // "outer" index = coset c: same input for every c, output row (k_1, c), scale table c
                     p.a.ib1 = 0;
                     p.a.ob1 = B * L;
                     p.a.out_rs = (long long)cosets * B * L;
-                    p.a.ps_i1 = n_coeffs;
+                    p.a.ps_i1 = c.n_coeffs;
                 }
                 outer = (long long)cosets;
             }
-            rc = launch_pass(p, inverse, stream);
+            rc = launch_pass(p, inverse, ts);
             src = dst;
             src_bs = dst_bs;
             outer <<= a[i];
@@ -1396,8 +1359,8 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
             Launch pl = plan_transpose_pass(plan, scratch, tout, sbs, c.out_bs, nb, a[P - 1], N[0] * (long long)cosets, P == 3 ? N[1] : 1, L, 0,
                                             plan.words, pre2[P - 1] ? 2 : 1);
             pl.a.inner_tw = inner[P - 1];
-            pl.a.post_scale = post_scale;
-            pl.a.n_out = n_out;
+            pl.a.post_scale = c.post_scale;
+            pl.a.n_out = c.n_out;
             if (plan.plain1024 && pl.a.nc == 16 && (unsigned long long)n * L * sizeof(u64) < (1ull << 32)) {
                 // The R = 1024 last pass stores 128-byte segments of 16 adjacent output words.  When the output of batch entry
                 // b does not start on a cache line (a truncated product: stride n_out = na + nb - 1 words, or a caller's
@@ -1410,14 +1373,14 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
                 pl.a.col_shift_i0 = (int)(c.out_bs & 15);
                 pl.a.col_wrap = pl.a.col_limit;
             }
-            rc = launch_pass(pl, inverse, stream);
+            rc = launch_pass(pl, inverse, ts);
         } else {
             for (size_t b = 0; b < nb && rc == TF_OK; ++b) {
                 Launch pl = plan_transpose_pass(plan, scratch + (long long)b * sbs, tout + (long long)b * c.out_bs, sbs, c.out_bs, 1, a[3], N[0],
                                                 N[1] * N[2], L, N[1]);
                 pl.a.inner_tw = inner[3];
-                pl.a.post_scale = post_scale;
-                rc = launch_pass(pl, inverse, stream);
+                pl.a.post_scale = c.post_scale;
+                rc = launch_pass(pl, inverse, ts);
             }
         }
     }
@@ -1425,33 +1388,21 @@ int run_passes(const NttCall& c, const NttPlan& plan) {
     return jrc ? jrc : rc;
 }
 
-// The transform proper.  in/out are device pointers; in == out for ntt/intt, distinct for coset evaluation
-// (then pre_scale != null and rows >= n_coeffs read as zero).  in_bs/out_bs: words per polynomial.
-// cosets = C > 1 (forward coset evaluation only, n > 1024): the output has C * n points per polynomial,
-// out[j * C + c] = (transform of the coefficients scaled by pre_scale[c * n_coeffs + .])[j] -- the evaluation on the coset of
-// order C * n done as C transforms of length n whose outputs interleave (w_{Cn}^(jC + c) = w_{Cn}^c * w_n^j).  The first pass
-// reads the coefficients once per c and writes rows (k_1, c); from there on it is the ordinary plan with N_1 * C rows.
-// n_out >= 0 (only with can_truncate(n, L)): the last pass stores output elements j < n_out only and out_bs may be
-// n_out * L -- the truncation of fast_multiply without a copy; `in` is then used as work space and clobbered
-int run_ntt(DeviceCtx* ctx, const u64* in, u64* out, long long in_bs, long long out_bs, size_t n, size_t batch, int L,
-            bool inverse, const u64* pre_scale, long long n_coeffs, hipStream_t stream, const u64* post_scale,
-            size_t cosets, const u64* in2, long long n_out, const u64* coset_offset) {
-    if (n == 0 || batch == 0) return TF_OK;
-    NttShape s;
-    s.n = n, s.batch = batch, s.L = L, s.inverse = inverse, s.cosets = cosets, s.n_coeffs = n_coeffs, s.n_out = n_out;
-    s.pre_scale = pre_scale != nullptr, s.post_scale = post_scale != nullptr, s.in2 = in2 != nullptr, s.coset_offset = coset_offset != nullptr;
-    s.packed = in_bs == (long long)n * L && out_bs == (long long)n * L;
-    const NttPlan plan = plan_ntt(s);
-    const NttCall c{ctx, in, out, in_bs, out_bs, n, batch, L, inverse, pre_scale, n_coeffs, stream, post_scale, cosets, in2, n_out, coset_offset, ilog2(n)};
+// The transform proper: the call (NttCall, tf_internal.h, has the contract of every operand) is planned once and handed to the
+// executor of its route.
+int run_ntt(DeviceCtx* ctx, const NttCall& call, hipStream_t stream) {
+    if (call.n == 0 || call.batch == 0) return TF_OK;
+    const NttCall c = with_strides(call);
+    const NttPlan plan = plan_ntt(shape_of(c));
     switch (plan.route) {
-        case NttRoute::Rows32: return launch_rows32(in, out, batch, L, c.log_n, inverse, stream);
-        case NttRoute::Tiny: return run_tiny(c);
-        case NttRoute::Lat: return launch_lat(ctx, in, out, in_bs, out_bs, c.log_n, batch, L, inverse, n_coeffs, in2, stream, nullptr, pre_scale, post_scale);
-        case NttRoute::Lat2: return launch_lat2(ctx, in, out, in_bs, out_bs, c.log_n, batch, L, inverse, n_coeffs, in2, stream, pre_scale, post_scale);
-        case NttRoute::Row: return run_row(c, plan);
+        case NttRoute::Rows32: return launch_rows32(c, stream);
+        case NttRoute::Tiny: return run_tiny(ctx, c, stream);
+        case NttRoute::Lat: return launch_lat(ctx, c, stream);
+        case NttRoute::Lat2: return launch_lat2(ctx, c, stream);
+        case NttRoute::Row: return run_row(ctx, c, plan, stream);
         // (a product's inverse carries in2 and n_out and nothing else; every other shape on this route carries neither)
-        case NttRoute::Block: return launch_block(ctx, in, out, in_bs, out_bs, c.log_n, batch, inverse, pre_scale, n_coeffs, post_scale, stream, in2, n_out, L);
-        case NttRoute::Passes: return run_passes(c, plan);
+        case NttRoute::Block: return launch_block(ctx, c, stream);
+        case NttRoute::Passes: return run_passes(ctx, c, plan, stream);
     }
     return TF_ERR_HIP;
 }
@@ -1464,8 +1415,7 @@ int ntt_dev(u64* d_x, size_t n, size_t batch, int L, int inverse, void* stream) 
     DeviceCtx* ctx = nullptr;
     rc = current_ctx(&ctx);
     if (rc) return rc;
-    return run_ntt(ctx, d_x, d_x, (long long)n * L, (long long)n * L, n, batch, L, inverse != 0, nullptr, -1,
-                   static_cast<hipStream_t>(stream));
+    return run_ntt(ctx, NttCall(d_x, d_x, n, batch, L, inverse != 0), static_cast<hipStream_t>(stream));
 }
 
 int coset_eval_dev(const u64* d_coeffs, size_t n_coeffs, u64 offset_raw, u64* d_out, size_t order, size_t batch, int L,
@@ -1483,23 +1433,20 @@ int coset_eval_dev(const u64* d_coeffs, size_t n_coeffs, u64 offset_raw, u64* d_
         HIPCHK(hipMemsetAsync(d_out, 0, order * batch * size_t(L) * sizeof(u64), s));
         return TF_OK;
     }
-    const u64* pw = nullptr;
-    bool temp = false;
     // the blown-up evaluation on order / len cosets of the padded coefficient length where it saves a global pass (coset_split, tf_plan.hip)
     const size_t cosets = coset_split(n_coeffs, order, batch, L);
+    PowTable pw(ctx, s);  // (given back behind the transform's launches when the call returns)
+    NttCall c = ntt_of_coeffs(d_coeffs, n_coeffs, d_out, order / cosets, batch, L);
+    c.out_bs = (long long)order * L;
     if (cosets > 1) {
-        rc = get_pow_table(ctx, offset_raw, n_coeffs, s, &pw, &temp, cosets, ilog2(order));
-        if (rc) return rc;
-        rc = run_ntt(ctx, d_coeffs, d_out, (long long)n_coeffs * L, (long long)order * L, order / cosets, batch, L, false, pw,
-                     (long long)n_coeffs, s, nullptr, cosets);
+        TRY(pw.acquire(offset_raw, n_coeffs, cosets, ilog2(order)));
+        c.cosets = cosets;
     } else {
-        rc = get_pow_table(ctx, offset_raw, n_coeffs, s, &pw, &temp);
-        if (rc) return rc;
-        rc = run_ntt(ctx, d_coeffs, d_out, (long long)n_coeffs * L, (long long)order * L, order, batch, L, false, pw,
-                     (long long)n_coeffs, s, nullptr, 1, nullptr, -1, &offset_raw);
+        TRY(pw.acquire(offset_raw, n_coeffs));
+        c.coset_offset = &offset_raw;
     }
-    release_pow_table(ctx, pw, temp, s);
-    return rc;
+    c.pre_scale = pw.get();
+    return run_ntt(ctx, c, s);
 }
 
 

@@ -16,14 +16,12 @@ int coset_interp_dev(const u64* d_values, size_t n, u64 offset_raw, u64* d_out, 
     DeviceCtx* ctx = nullptr;
     rc = current_ctx(&ctx);
     if (rc) return rc;
-    const u64* pw = nullptr;
-    bool temp = false;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = get_pow_table(ctx, gl::mont_inverse(offset_raw), n, s, &pw, &temp);
-    if (rc) return rc;
-    rc = run_ntt(ctx, d_values, d_out, (long long)n * L, (long long)n * L, n, batch, L, true, nullptr, -1, s, pw);
-    release_pow_table(ctx, pw, temp, s);
-    return rc;
+    PowTable pw(ctx, s);  // (given back behind the transform's launches when the call returns)
+    TRY(pw.acquire(gl::mont_inverse(offset_raw), n));
+    NttCall c(d_values, d_out, n, batch, L, true);
+    c.post_scale = pw.get();
+    return run_ntt(ctx, c, s);
 }
 
 int hadamard_dev(const u64* a, const u64* b, u64* out, size_t count, int L, void* stream) {
@@ -88,26 +86,22 @@ int poly_mul_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out, siz
     if (order > 16) {
         // zero padding happens in the first pass of each forward transform (rows beyond the coefficients read as zero);
         // over BFieldElement the pointwise product rides on the inverse transform's first load
-        TRY(run_ntt(ctx, a, tmp, a_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s));
-        TRY(run_ntt(ctx, b, tmp + half, b_bs, (long long)order * L, order, batch, L, false, nullptr, (long long)nb, s));
-        const bool trunc = can_truncate(order, L);  // the inverse's last pass writes the n_out coefficients straight to `out`
-        u64* dst = trunc ? out : tmp;
-        const long long dst_bs = trunc ? (long long)n_out * L : (long long)order * L;
-        if (L == 1) {
-            TRY(run_ntt(ctx, tmp, dst, (long long)order, dst_bs, order, batch, 1, true, nullptr, -1, s, nullptr, 1, tmp + half,
-                        trunc ? (long long)n_out : -1));
-        } else {
-            TRY(hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s));
-            TRY(run_ntt(ctx, tmp, dst, (long long)order * L, dst_bs, order, batch, L, true, nullptr, -1, s, nullptr, 1, nullptr,
-                        trunc ? (long long)n_out : -1));
-        }
-        copied = trunc;
+        NttCall fa = ntt_of_coeffs(a, na, tmp, order, batch, L), fb = ntt_of_coeffs(b, nb, tmp + half, order, batch, L);
+        fa.in_bs = a_bs, fb.in_bs = b_bs;
+        TRY(run_ntt(ctx, fa, s));
+        TRY(run_ntt(ctx, fb, s));
+        copied = can_truncate(order, L);  // the inverse's last pass writes the n_out coefficients straight to `out`
+        NttCall inv(tmp, copied ? out : tmp, order, batch, L, true);
+        if (copied) inv.n_out = (long long)n_out, inv.out_bs = (long long)n_out * L;
+        if (L == 1) inv.in2 = tmp + half;
+        else TRY(hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s));
+        TRY(run_ntt(ctx, inv, s));
     } else {
         TRY(pad_copy(a, tmp, (long long)na * L, (long long)order * L, (long long)batch, s, a_bs));
         TRY(pad_copy(b, tmp + half, (long long)nb * L, (long long)order * L, (long long)batch, s, b_bs));
-        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, 2 * batch, L, false, nullptr, -1, s));
+        TRY(run_ntt(ctx, NttCall(tmp, tmp, order, 2 * batch, L, false), s));
         TRY(hadamard_dev(tmp, tmp + half, tmp, batch * order, L, s));
-        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s));
+        TRY(run_ntt(ctx, NttCall(tmp, tmp, order, batch, L, true), s));
     }
     if (!copied) TRY(pad_copy(tmp, out, (long long)order * L, (long long)n_out * L, (long long)batch, s));
     return work.release();
@@ -136,13 +130,13 @@ int poly_mul_shared_dev(const u64* a, size_t na, size_t batch, const u64* b, siz
     TRY(work.alloc((batch + 1) * row, "poly_mul_shared"));
     u64* const tmp = work.p;
     u64* bh = tmp + batch * row;
-    TRY(run_ntt(ctx, a, tmp, (long long)na * L, (long long)row, order, batch, L, false, nullptr, (long long)na, s));
-    TRY(run_ntt(ctx, b, bh, (long long)nb * L, (long long)row, order, 1, L, false, nullptr, (long long)nb, s));
+    TRY(run_ntt(ctx, ntt_of_coeffs(a, na, tmp, order, batch, L), s));
+    TRY(run_ntt(ctx, ntt_of_coeffs(b, nb, bh, order, 1, L), s));
     TRY(L == 1 ? launch_1d<1>(tfk::product_bcast_kernel<1>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)bh, tmp, (long long)order,
                               (long long)(batch * order))
                : launch_1d<3>(tfk::product_bcast_kernel<3>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)bh, tmp, (long long)order,
                               (long long)(batch * order)));
-    TRY(run_ntt(ctx, tmp, tmp, (long long)row, (long long)row, order, batch, L, true, nullptr, -1, s));
+    TRY(run_ntt(ctx, NttCall(tmp, tmp, order, batch, L, true), s));
     TRY(pad_copy(tmp, out, (long long)row, (long long)(n_out * L), (long long)batch, s));
     return work.release();
 }
@@ -165,24 +159,18 @@ int poly_square_dev(const u64* a, size_t na, u64* out, size_t batch, int L, void
     u64* const tmp = work.p;
     bool copied = false;
     if (order > 16) {
-        TRY(run_ntt(ctx, a, tmp, (long long)na * L, (long long)order * L, order, batch, L, false, nullptr, (long long)na, s));
-        const bool trunc = can_truncate(order, L);
-        u64* dst = trunc ? out : tmp;
-        const long long dst_bs = trunc ? (long long)n_out * L : (long long)order * L;
-        if (L == 1) {
-            TRY(run_ntt(ctx, tmp, dst, (long long)order, dst_bs, order, batch, 1, true, nullptr, -1, s, nullptr, 1, tmp,
-                        trunc ? (long long)n_out : -1));
-        } else {
-            TRY(hadamard_dev(tmp, tmp, tmp, batch * order, L, s));
-            TRY(run_ntt(ctx, tmp, dst, (long long)order * L, dst_bs, order, batch, L, true, nullptr, -1, s, nullptr, 1, nullptr,
-                        trunc ? (long long)n_out : -1));
-        }
-        copied = trunc;
+        TRY(run_ntt(ctx, ntt_of_coeffs(a, na, tmp, order, batch, L), s));
+        copied = can_truncate(order, L);
+        NttCall inv(tmp, copied ? out : tmp, order, batch, L, true);
+        if (copied) inv.n_out = (long long)n_out, inv.out_bs = (long long)n_out * L;
+        if (L == 1) inv.in2 = tmp;
+        else TRY(hadamard_dev(tmp, tmp, tmp, batch * order, L, s));
+        TRY(run_ntt(ctx, inv, s));
     } else {
         TRY(pad_copy(a, tmp, (long long)na * L, (long long)order * L, (long long)batch, s));
-        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, false, nullptr, -1, s));
+        TRY(run_ntt(ctx, NttCall(tmp, tmp, order, batch, L, false), s));
         TRY(hadamard_dev(tmp, tmp, tmp, batch * order, L, s));
-        TRY(run_ntt(ctx, tmp, tmp, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s));
+        TRY(run_ntt(ctx, NttCall(tmp, tmp, order, batch, L, true), s));
     }
     if (!copied) TRY(pad_copy(tmp, out, (long long)order * L, (long long)n_out * L, (long long)batch, s));
     return work.release();
@@ -252,7 +240,9 @@ template <int L>
 int inverse_of_product(DeviceCtx* ctx, const u64* a_hat, const u64* b_hat, long long in_bs, u64* out, size_t order, size_t batch, bool pairs,
                        hipStream_t s) {
     if constexpr (L == 1) {
-        return run_ntt(ctx, a_hat, out, in_bs, (long long)order, order, batch, 1, true, nullptr, -1, s, nullptr, 1, b_hat, -1);
+        NttCall c(a_hat, out, order, batch, 1, true);
+        c.in_bs = in_bs, c.in2 = b_hat;
+        return run_ntt(ctx, c, s);
     } else {
         int rc;
         if (pairs)  // a_hat / b_hat are the even / odd rows of one array
@@ -260,7 +250,7 @@ int inverse_of_product(DeviceCtx* ctx, const u64* a_hat, const u64* b_hat, long 
         else
             rc = hadamard_dev(a_hat, b_hat, out, batch * order, L, s);
         if (rc) return rc;
-        return run_ntt(ctx, out, out, (long long)order * L, (long long)order * L, order, batch, L, true, nullptr, -1, s);
+        return run_ntt(ctx, NttCall(out, out, order, batch, L, true), s);
     }
 }
 
@@ -299,7 +289,7 @@ int zerofier_tree_build(DeviceCtx* ctx, const u64* points, long long n_points, Z
         // transforms of order 2d of this level's tails and inverses: kept for the walks, and the parents are built from them
         // (ONE call: the level's tails and inverses are neighbours in the arena, and so are their transforms)
         static_assert(kTreeLevelArrays == 6, "tails | inv | That (2) | Ghat (2)");
-        int rc = run_ntt(ctx, T->tails[l], T->That[l], d * L, 2 * d * L, (size_t)(2 * d), (size_t)(2 * children), L, false, nullptr, d, s);
+        int rc = run_ntt(ctx, ntt_of_coeffs(T->tails[l], (size_t)d, T->That[l], (size_t)(2 * d), (size_t)(2 * children), L), s);
         if (rc) return rc;
         if (l + 1 == h) break;
         u64* S1 = work;              // parents x 2d    g_left g_right (its low half is G)
@@ -307,13 +297,13 @@ int zerofier_tree_build(DeviceCtx* ctx, const u64* points, long long n_points, Z
         u64* C = work + 3 * M * L;   // 2 parents x 4d  their transforms; the G rows become g (2 - h g)
         // tails of the parents: (A^ + s)(B^ + s) - 1 pointwise, one inverse transform straight into the level array
         rc = launch_1d<L>(tfk::zerofier_pointwise_kernel<L>, parents * 2 * d, s, (const u64*)T->That[l], T->tails[l + 1], d, parents);
-        if (!rc) rc = run_ntt(ctx, T->tails[l + 1], T->tails[l + 1], 2 * d * L, 2 * d * L, (size_t)(2 * d), (size_t)parents, L, true, nullptr, -1, s);
+        if (!rc) rc = run_ntt(ctx, NttCall(T->tails[l + 1], T->tails[l + 1], (size_t)(2 * d), (size_t)parents, L, true), s);
         // inverses of the parents: G = g_left g_right mod x^d, then one Newton step g <- G (2 - rev(Z) G) mod x^2d at order 4d
         if (!rc) rc = inverse_of_product<L>(ctx, T->Ghat[l], T->Ghat[l] + 2 * d * L, 4 * d * L, S1, (size_t)(2 * d), (size_t)parents, true, s);
         if (!rc) rc = launch_1d<L>(tfk::newton_inputs_kernel<L>, parents * 2 * d, s, (const u64*)S1, (const u64*)T->tails[l + 1], B, d, parents);
-        if (!rc) rc = run_ntt(ctx, B, C, 2 * d * L, 4 * d * L, (size_t)(4 * d), (size_t)(2 * parents), L, false, nullptr, 2 * d, s);
+        if (!rc) rc = run_ntt(ctx, ntt_of_coeffs(B, (size_t)(2 * d), C, (size_t)(4 * d), (size_t)(2 * parents), L), s);
         if (!rc) rc = launch_1d<L>(tfk::newton_pointwise_kernel<L>, parents * 4 * d, s, C, 4 * d, parents);
-        if (!rc) rc = run_ntt(ctx, C, C, 4 * d * L, 4 * d * L, (size_t)(4 * d), (size_t)parents, L, true, nullptr, -1, s);
+        if (!rc) rc = run_ntt(ctx, NttCall(C, C, (size_t)(4 * d), (size_t)parents, L, true), s);
         if (!rc) rc = launch_1d<L>(tfk::poly_truncate_kernel<L>, parents * 2 * d, s, (const u64*)C, 4 * d, T->inv[l + 1], 2 * d, parents);
         if (rc) return rc;
     }
@@ -328,7 +318,7 @@ int inverse_of_cached_product(DeviceCtx* ctx, const u64* a_hat, const u64* b_hat
     const long long period = (long long)(batch * order), total = period * U;
     int rc = launch_1d<L>(tfk::product_bcast_kernel<L>, total, s, a_hat, b_hat, out, period, total);
     if (rc) return rc;
-    return run_ntt(ctx, out, out, (long long)order * L, (long long)order * L, order, batch * (size_t)U, L, true, nullptr, -1, s);
+    return run_ntt(ctx, NttCall(out, out, order, batch * (size_t)U, L, true), s);
 }
 
 // The elementwise steps of a walk (reverse, remainder, the interpolation's pointwise combination) ride on the load / store of the
@@ -374,23 +364,27 @@ int zerofier_tree_evaluate(DeviceCtx* ctx, const ZerofierTree& T, const u64* F, 
         }
         if (tree_fuse(2 * d, all, L)) {
             // the same steps with the reversals read on load and the remainder formed on store (ntt_lat_kernel's modifiers)
-            const int lg = ilog2((size_t)(2 * d));
             tfk::NttLatArgs m{};
             m.load_mode = 1, m.src_shift = 1, m.rev_top = 2 * d - 1;  // line `child` <- reversed upper half of its parent's remainder
-            rc = launch_lat(ctx, cur, Fh, 2 * d * L, 2 * d * L, lg, (size_t)all, L, false, d, nullptr, s, &m);
+            NttCall fwd(cur, Fh, (size_t)(2 * d), (size_t)all, L, false);
+            fwd.n_coeffs = d;  // (lines of 2d elements in and out, packed)
+            rc = launch_lat(ctx, fwd, s, &m);
             if (!rc) rc = inverse_of_cached_product<L>(ctx, Fh, T.Ghat[l], prod, (size_t)(2 * d), (size_t)children, U, s);
             m.src_shift = 0, m.rev_top = d - 1;                        // q = the reversed low half of that product
-            if (!rc) rc = launch_lat(ctx, prod, Fh, 2 * d * L, 2 * d * L, lg, (size_t)all, L, false, d, nullptr, s, &m);
+            fwd.in = prod;
+            if (!rc) rc = launch_lat(ctx, fwd, s, &m);
             // r = f_low - (q tail)_low: the product's inverse transform stores f_low - value for the low d outputs only
             tfk::NttLatArgs st{};
             st.store_mode = 1, st.sub_src = cur, st.sub_bs = 2 * d * L, st.keep = d;
+            NttCall rem(prod, nxt, (size_t)(2 * d), (size_t)all, L, true);
+            rem.out_bs = d * L;
             if (!rc && U == 1 && L == 1) {
-                rc = launch_lat(ctx, Fh, nxt, 2 * d, d, lg, (size_t)all, 1, true, -1, T.That[l], s, &st);
+                rem.in = Fh, rem.in2 = T.That[l];
             } else if (!rc) {
                 if (U == 1) rc = hadamard_dev(Fh, T.That[l], prod, (size_t)(all * 2 * d), L, s);
                 else rc = launch_1d<L>(tfk::product_bcast_kernel<L>, all * 2 * d, s, (const u64*)Fh, (const u64*)T.That[l], prod, children * 2 * d, all * 2 * d);
-                if (!rc) rc = launch_lat(ctx, prod, nxt, 2 * d * L, d * L, lg, (size_t)all, L, true, -1, nullptr, s, &st);
             }
+            if (!rc) rc = launch_lat(ctx, rem, s, &st);
             if (rc) return rc;
             cur = nxt;
             continue;
@@ -400,11 +394,11 @@ int zerofier_tree_evaluate(DeviceCtx* ctx, const ZerofierTree& T, const u64* F, 
             rc = launch_1d<L>(tfk::remainder_rev_high_kernel<L>, all * d, s, cur, fr, d, all);
             fr_in = fr;
         }
-        if (!rc) rc = run_ntt(ctx, fr_in, Fh, d * L, 2 * d * L, (size_t)(2 * d), (size_t)all, L, false, nullptr, d, s);
+        if (!rc) rc = run_ntt(ctx, ntt_of_coeffs(fr_in, (size_t)d, Fh, (size_t)(2 * d), (size_t)all, L), s);
         if (!rc) rc = inverse_of_cached_product<L>(ctx, Fh, T.Ghat[l], prod, (size_t)(2 * d), (size_t)children, U, s);
         if (!rc) rc = launch_1d<L>(tfk::poly_reverse_kernel<L>, all * d, s, (const u64*)prod, 2 * d, fr, d, all);
         // r = f_low - (q tail)_low
-        if (!rc) rc = run_ntt(ctx, fr, Fh, d * L, 2 * d * L, (size_t)(2 * d), (size_t)all, L, false, nullptr, d, s);
+        if (!rc) rc = run_ntt(ctx, ntt_of_coeffs(fr, (size_t)d, Fh, (size_t)(2 * d), (size_t)all, L), s);
         if (!rc) rc = inverse_of_cached_product<L>(ctx, Fh, T.That[l], prod, (size_t)(2 * d), (size_t)children, U, s);
         if (rc) return rc;
         rc = launch_1d<L>(tfk::remainder_finish_kernel<L>, all * d, s, cur, (const u64*)prod, 2 * d, nxt, d, all, l > l_stop ? frq : (u64*)nullptr);
@@ -642,7 +636,7 @@ int padded_tree_build(const u64* points, size_t n_points, size_t extra_words, Pa
     // the root from the transforms of the two nodes of level h - 1 (d = M / 2, order M)
     const long long d = M / 2;
     TRY(launch_1d<L>(tfk::zerofier_pointwise_kernel<L>, 2 * d, s, (const u64*)pt->T.That[h - 1], pt->root_tail, d, (long long)1));
-    TRY(run_ntt(ctx, pt->root_tail, pt->root_tail, 2 * d * L, 2 * d * L, (size_t)(2 * d), 1, L, true, nullptr, -1, s));
+    TRY(run_ntt(ctx, NttCall(pt->root_tail, pt->root_tail, (size_t)(2 * d), 1, L, true), s));
     return work.release();
 }
 
@@ -759,7 +753,7 @@ int tree_interpolate_rows(DeviceCtx* ctx, const PaddedTree& pt, const u64* domai
                 std::swap(cur, nxt);
                 continue;
             }
-            rc = run_ntt(ctx, cur, Nh, d * L, 2 * d * L, (size_t)(2 * d), (size_t)(children * (long long)nr), L, false, nullptr, d, s);
+            rc = run_ntt(ctx, ntt_of_coeffs(cur, (size_t)d, Nh, (size_t)(2 * d), (size_t)(children * (long long)nr), L), s);
             // (the pointwise combination stays a kernel of its own.  Measured, tools/tree_latency.py on one box: prepared-tree
             //  interpolation of 2^12 points 129.0 us with the pointwise kernel, 135.8 us with it fused into the inverse transform's load
             //  -- four strided loads and two products per element in front of the transform's first stage cost more than the 1.5 us a
@@ -770,7 +764,7 @@ int tree_interpolate_rows(DeviceCtx* ctx, const PaddedTree& pt, const u64* domai
             const bool direct = l == h - 1 && (long long)n == M;
             u64* dst = direct ? out + r0 * n * L : nxt;
             wrote_direct = direct;
-            if (!rc) rc = run_ntt(ctx, nxt, dst, 2 * d * L, 2 * d * L, (size_t)(2 * d), (size_t)(parents * (long long)nr), L, true, nullptr, -1, s);
+            if (!rc) rc = run_ntt(ctx, NttCall(nxt, dst, (size_t)(2 * d), (size_t)(parents * (long long)nr), L, true), s);
             std::swap(cur, nxt);
         }
         if (!rc && !wrote_direct) {
@@ -1003,7 +997,7 @@ int coset_eval_xoffset_dev(const u64* d_coeffs, size_t n_coeffs, const u64 offse
                            (long long)n_coeffs * 3, d_out + b0 * order * 3, (long long)order, nb, offset[0], offset[1], offset[2]);
         HIPCHK(hipGetLastError());
     }
-    return run_ntt(ctx, d_out, d_out, (long long)order * 3, (long long)order * 3, order, batch, 3, false, nullptr, -1, s);
+    return run_ntt(ctx, NttCall(d_out, d_out, order, batch, 3, false), s);
 }
 
 int coset_interp_xoffset_dev(const u64* d_values, size_t n, const u64 offset[3], u64* d_out, size_t batch, void* stream) {
@@ -1018,7 +1012,7 @@ int coset_interp_xoffset_dev(const u64* d_values, size_t n, const u64 offset[3],
     rc = current_ctx(&ctx);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = run_ntt(ctx, d_values, d_out, (long long)n * 3, (long long)n * 3, n, batch, 3, true, nullptr, -1, s);
+    rc = run_ntt(ctx, NttCall(d_values, d_out, n, batch, 3, true), s);
     if (rc) return rc;
     const size_t slab = std::max<size_t>(1, (size_t(1) << 30) / n);
     for (size_t b0 = 0; b0 < batch; b0 += slab) {
@@ -1120,14 +1114,14 @@ int clean_divide_dev(const u64* a, size_t na, const u64* b, size_t nb, u64* out,
         hipLaunchKernelGGL(tfk::lift_scale_kernel, dim3(blocks, 1), dim3(256), 0, s, b, (long long)nb, (long long)order, div, X[0], X[1], X[2]);
         if (hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
     }
-    if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)half, (long long)half, order, batch + 1, 3, false, nullptr, -1, s);
+    if (!rc) rc = run_ntt(ctx, NttCall(tmp, tmp, order, batch + 1, 3, false), s);
     if (!rc) {
         hipLaunchKernelGGL(tfk::xfe_invert_inplace_kernel, dim3(blocks), dim3(256), 0, s, div, (long long)order, flag);
         if (hipGetLastError() != hipSuccess) rc = TF_ERR_HIP;
     }
     if (!rc) rc = launch_1d<3>(tfk::product_bcast_kernel<3>, (long long)(batch * order), s, (const u64*)tmp, (const u64*)div, tmp, (long long)order,
                                (long long)(batch * order));
-    if (!rc) rc = run_ntt(ctx, tmp, tmp, (long long)half, (long long)half, order, batch, 3, true, nullptr, -1, s);
+    if (!rc) rc = run_ntt(ctx, NttCall(tmp, tmp, order, batch, 3, true), s);
     if (!rc) {
         hipLaunchKernelGGL(tfk::unscale_unlift_kernel, dim3(blocks, (unsigned)batch), dim3(256), 0, s, (const u64*)tmp, (long long)order,
                            (long long)(na - nb + 1), out, Xinv[0], Xinv[1], Xinv[2], flag);
