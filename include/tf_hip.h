@@ -957,6 +957,70 @@ size_t tf_scan_workspace(int mode, size_t n, size_t batch, int width_out);
 int tf_scan_plan(int mode, size_t n, size_t batch, int width_out, int *info, int capacity);
 
 /* ---------------------------------------------------------------------------------------------
+ * DEEP quotients: the codeword FRI is run on, from the extended tables and the out-of-domain values, and the same value at sampled
+ * rows for the verifier.  replaces the composition, per point, of tf_poly_linear_combination_dev, tf_powers_dev, a broadcast
+ * subtraction, tf_batch_inversion_xfe_dev and two Hadamard passes:
+ *     out[i] = sum_{p < n_points} ( sum_c w[p][c] * (T_c[i] - v[p][c]) ) / (x_i - z_p),    x_i = offset * w_n^i
+ * T_c are the columns of two column-major tables: k1 BFieldElement columns (`main`, column c = n words at d_main + c * stride_main)
+ * followed by k3 XFieldElement columns (`aux`, column c = 3 n words at d_aux + c * stride_aux); a BFieldElement stands for its lift.
+ * z_p are the out-of-domain points (in practice z and w z), v the claimed values there, w the sampled weights.  Every result is the
+ * canonical raw Montgomery word of the field element the formula defines, whatever the grouping of the operations: there is no
+ * tolerance anywhere.
+ *   domain           w_n is the reference's primitive_root_of_unity(n), natural order: the domain of tf_fri_fold_dev and
+ *                    tf_coset_eval_*.  offset_raw is a non-zero BFieldElement.
+ *   operands         all in device memory.  d_points: n_points XFieldElements.  d_weights, d_values: n_points * (k1 + k3)
+ *                    XFieldElements each, point-major, the main columns first: element (p, c) at ((p * (k1 + k3)) + c) * 3 -- where
+ *                    tf_tip5_sponge_sample_scalars_dev and tf_barycentric_evaluate_*_dev leave them.  d_out: n XFieldElements.
+ *                    Words between the end of a column and its stride are never read.
+ *   limits           1 <= n_points <= 4; k1 + k3 <= 65 535, the counter bound of the carry-deferred accumulators
+ *                    (csrc/algebra_kernels.h); n a power of two, at most 2^32.
+ *   empty tables     either table may be empty: k1 == 0 allows d_main == NULL, k3 == 0 allows d_aux == NULL, and the stride of an
+ *                    empty table is not looked at.  k1 + k3 == 0 writes zeros (the empty sum), needs no d_weights, d_values or work
+ *                    space and leaves the status alone.
+ *   empty calls      n == 0 (rows form: n_rows == 0): TF_OK, nothing touched, NULL pointers allowed.
+ *   zero denominator x_i == z_p (z_p the lift of a point of the domain) writes TF_ERR_INVERSE_OF_ZERO to *d_status, one int of device
+ *                    memory in which the first non-zero code stays and which is never cleared (the contract of the _async calls).
+ *                    That element of d_out is unspecified; every other element, those of the same wave included, is correct.
+ *   rows form        tf_deep_quotient_rows_dev computes out[r] = the value above at i = d_indices[r], r < n_rows, from row-major rows:
+ *                    row r of d_main_rows = k1 words at r * row_stride_main, row r of d_aux_rows = 3 k3 words at r * row_stride_aux
+ *                    -- what tf_table_gather_rows_dev wrote for the same index list.  Repeated indices are allowed.  An index >= n
+ *                    writes TF_ERR_INVALID_ARGUMENT to *d_status, the code tf_table_gather_rows_dev stores for it; that row of
+ *                    d_out is unspecified, every other row is correct.  No work space.
+ *   work space       the caller's: d_work, work_bytes.  tf_deep_quotient_workspace returns the bytes a codeword call needs: one
+ *                    XFieldElement per point (C_p = sum_c w[p][c] v[p][c], formed once per call by a small launch ahead of the
+ *                    passes); 0 for k1 + k3 == 0, for an empty and for a rejected call.  d_work may be NULL when that is 0; it is
+ *                    8-byte aligned; a smaller work_bytes is TF_ERR_INVALID_ARGUMENT.  The library allocates nothing and has no
+ *                    host-pointer form of these calls.
+ *   passes           one pass of the codeword kernel serves up to two points and reads every word of both tables once; n_points = 3
+ *                    and 4 run a second pass over the tables, which adds its points' terms into d_out (a one-pass form of four
+ *                    points does not fit the register file without scratch).  No codeword-sized intermediate is written.
+ *   plan             tf_deep_quotient_plan writes (at most `capacity` entries; fields may be NULL) fields[0] elements per wave and step
+ *                    (the chunk C), [1] elements per lane, [2] points per pass, [3] passes, [4] launches (the constants and the
+ *                    passes; 1 for k1 + k3 == 0, 0 for n == 0), [5] the grid cap in chunks: above that many chunks a wave takes
+ *                    further chunks in a grid-stride loop.  It returns the launches, or minus the status the call would return for
+ *                    (n, k1, k3, n_points).  Host arithmetic, as tf_deep_quotient_workspace: no device needed.
+ *   aliasing         d_out, d_work and d_status must not overlap an input or each other.
+ *   forms            only _dev forms: device pointers, enqueued on `stream`; nothing is synchronised or copied back.
+ *   errors           returned before any HIP call, in this order: TF_ERR_NULL_POINTER (a pointer the call would use: d_points, d_out
+ *                    and d_status always, a table with columns, d_weights and d_values with k1 + k3 > 0, d_indices, d_work where an
+ *                    otherwise valid call needs it); TF_ERR_INVALID_ARGUMENT (n_points outside 1..4, the stride of a table with
+ *                    columns below its line: n or 3 n words, k1 or 3 k3 words in the rows form; a short work space);
+ *                    TF_ERR_LEN_NOT_POWER_OF_TWO (n; in the rows form n == 0 too); TF_ERR_LEN_TOO_LARGE (n above 2^32, k1 + k3 above
+ *                    65 535, n_rows above 2^30, a table whose lines at its stride span more than 2^40 words);
+ *                    TF_ERR_INVERSE_OF_ZERO (offset_raw == 0); then TF_ERR_NO_DEVICE on a machine without a GPU.
+ * Lanes run along i: a wave owns C consecutive elements, inverts all their denominators with one inversion (Montgomery's trick over
+ * the wave, as tf_batch_inversion_*) and accumulates the weighted sums unreduced (csrc/deep_kernels.h). */
+int tf_deep_quotient_dev(const uint64_t *d_main, size_t k1, size_t stride_main, const uint64_t *d_aux, size_t k3, size_t stride_aux, size_t n,
+                         uint64_t offset_raw, const uint64_t *d_points, size_t n_points, const uint64_t *d_weights, const uint64_t *d_values,
+                         uint64_t *d_out, void *d_work, size_t work_bytes, void *stream, int *d_status);
+size_t tf_deep_quotient_workspace(size_t n, size_t k1, size_t k3, size_t n_points);
+int tf_deep_quotient_plan(size_t n, size_t k1, size_t k3, size_t n_points, int *fields, int capacity);
+int tf_deep_quotient_rows_dev(const uint64_t *d_main_rows, size_t k1, size_t row_stride_main, const uint64_t *d_aux_rows, size_t k3,
+                              size_t row_stride_aux, size_t n, uint64_t offset_raw, const uint32_t *d_indices, size_t n_rows,
+                              const uint64_t *d_points, size_t n_points, const uint64_t *d_weights, const uint64_t *d_values,
+                              uint64_t *d_out, void *stream, int *d_status);
+
+/* ---------------------------------------------------------------------------------------------
  * Tables: moving a table between the two layouts the library itself uses, and opening its rows.  replaces
  *   Array2 .t() / reversed_axes, a prover's own transposes           table_transpose     dst line i, element o = src line o, element i
  *   table.row(i) / select(Axis(0), indices)                          table_gather_rows   out row q = row indices[q]

@@ -27,7 +27,7 @@ from . import _lib
 
 __all__ = [
     "P", "BFieldElement", "ntt", "intt", "batch_inversion", "inverse_or_zero", "linear_combination", "get_colinear_y", "are_colinear", "mod_pow", "powers", "fri_fold", "Polynomial", "ZerofierTree", "barycentric_evaluate", "fast_coset_evaluate", "fast_coset_interpolate", "fast_multiply", "fast_square", "Tip5", "Tip5Sponge", "Digest", "MerkleTree", "Table",
-    "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "table", "merkle_sampled", "fri", "scan", "set_device", "get_device", "shard_range",
+    "MerkleTreeInclusionProof", "MerkleTreeError", "TwentyFirstError", "NttPanic", "lib", "device", "table", "merkle_sampled", "fri", "scan", "deep", "set_device", "get_device", "shard_range",
 ]
 
 P = 0xFFFFFFFF00000001  # BFieldElement::P, math/b_field_element.rs:225
@@ -1459,5 +1459,6 @@ from . import table  # noqa: E402  (tables on the device: transposes, row openin
 from . import merkle_sampled  # noqa: E402  (Merkle openings at leaf indices that are device data)
 from . import fri  # noqa: E402  (the FRI split-and-fold of whole codewords)
 from . import scan  # noqa: E402  (prefix scans along columns: running sums, products, the affine recurrence)
+from . import deep  # noqa: E402  (DEEP quotients of the extended tables: whole codewords and sampled rows)
 
 fri_fold = fri.fold_host  # the numpy form, next to get_colinear_y and powers

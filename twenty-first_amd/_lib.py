@@ -148,6 +148,10 @@ SIGNATURES = {
     "tf_scan_affine_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, C.c_int, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "tf_scan_workspace": (_sz, [C.c_int, _sz, _sz, C.c_int]),
     "tf_scan_plan": (C.c_int, [C.c_int, _sz, _sz, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "tf_deep_quotient_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _sz, _sz, C.c_uint64, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tf_deep_quotient_workspace": (_sz, [_sz, _sz, _sz, _sz]),
+    "tf_deep_quotient_plan": (C.c_int, [_sz, _sz, _sz, _sz, C.POINTER(C.c_int), C.c_int]),
+    "tf_deep_quotient_rows_dev": (C.c_int, [_vp, _sz, _sz, _vp, _sz, _sz, _sz, C.c_uint64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "tf_table_transpose": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz]),
     "tf_table_transpose_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _sz, _vp, _sz, _sz, _vp]),
     "tf_table_gather_rows": (C.c_int, [_vp, C.c_int, _sz, _sz, C.c_int, _sz, _vp, _sz, _vp, _sz, _sz]),

@@ -999,6 +999,29 @@ size_t tf_scan_workspace(int mode, size_t n, size_t batch, int width_out) try {
 int tf_scan_plan(int mode, size_t n, size_t batch, int width_out, int* info, int capacity) try {
     return scan_plan(mode, n, batch, width_out, info, capacity);
 } TF_ABI_CATCH
+// the DEEP quotient: whole codewords and sampled rows (tf_deep.hip)
+int tf_deep_quotient_dev(const uint64_t* d_main, size_t k1, size_t stride_main, const uint64_t* d_aux, size_t k3, size_t stride_aux, size_t n,
+                         uint64_t offset_raw, const uint64_t* d_points, size_t n_points, const uint64_t* d_weights, const uint64_t* d_values,
+                         uint64_t* d_out, void* d_work, size_t work_bytes, void* stream, int* d_status) try {
+    return deep_quotient_dev(d_main, k1, stride_main, d_aux, k3, stride_aux, n, offset_raw, d_points, n_points, d_weights, d_values, d_out, d_work,
+                             work_bytes, stream, d_status);
+} TF_ABI_CATCH
+size_t tf_deep_quotient_workspace(size_t n, size_t k1, size_t k3, size_t n_points) try {
+    return deep_quotient_workspace(n, k1, k3, n_points);
+} catch (...) {
+    ::tfi::abi_caught("C++ exception in tf_deep_quotient_workspace", TF_ERR_INTERNAL);
+    return 0;
+}
+int tf_deep_quotient_plan(size_t n, size_t k1, size_t k3, size_t n_points, int* fields, int capacity) try {
+    return deep_quotient_plan(n, k1, k3, n_points, fields, capacity);
+} TF_ABI_CATCH
+int tf_deep_quotient_rows_dev(const uint64_t* d_main_rows, size_t k1, size_t row_stride_main, const uint64_t* d_aux_rows, size_t k3,
+                              size_t row_stride_aux, size_t n, uint64_t offset_raw, const uint32_t* d_indices, size_t n_rows,
+                              const uint64_t* d_points, size_t n_points, const uint64_t* d_weights, const uint64_t* d_values, uint64_t* d_out,
+                              void* stream, int* d_status) try {
+    return deep_quotient_rows_dev(d_main_rows, k1, row_stride_main, d_aux_rows, k3, row_stride_aux, n, offset_raw, d_indices, n_rows, d_points, n_points,
+                                  d_weights, d_values, d_out, stream, d_status);
+} TF_ABI_CATCH
 // tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (tf_table.hip)
 int tf_table_transpose(const uint64_t* src, size_t n_outer, size_t n_inner, int width, size_t src_stride, uint64_t* dst, size_t dst_stride,
                        size_t batch) try {

@@ -15,6 +15,7 @@
 //   tf_points.hip get_colinear_y / are_colinear, element-wise mod_pow, geometric sequences and index gathers (points_kernels.h)
 //   tf_fri.hip    the FRI split-and-fold of codewords on an evaluation domain, one to many levels per call (fri_kernels.h)
 //   tf_scan.hip   prefix scans along the columns of a table: running sums, products and the affine recurrence (scan_kernels.h)
+//   tf_deep.hip   the DEEP quotient of the extended tables: whole codewords and sampled rows (deep_kernels.h)
 //   tf_table.hip  tables between the column-major and the row-major layout: transpose, row gather, row-major LDE (table_kernels.h)
 //   tf_merkle_open.hip authentication structures and roots straight from the leafs: the root-only sweep with the wanted nodes copied out
 //   tf_temp_guard.hip the guard mode for all of the above's device temporaries (tf_debug_temp_guard): guards, poison, ledger, self-test
@@ -405,6 +406,18 @@ int scan_dev(int mode, const u64* a, size_t a_len, size_t a_sets, int wa, size_t
              const u64* init, size_t n_init, u64* out, size_t stride_out, void* d_work, size_t work_bytes, void* stream);
 size_t scan_workspace(int mode, size_t n, size_t batch, int w);
 int scan_plan(int mode, size_t n, size_t batch, int w, int* info, int capacity);
+
+// ------------------------------------------------------------------------------------ tf_deep.hip
+// the DEEP quotients of include/tf_hip.h ("DEEP quotients"): device pointers, only enqueues on `stream`, the work space is the caller's;
+// the work-space rule and the plan are pure host arithmetic (the plan: launches, or minus a status)
+int deep_quotient_dev(const u64* d_main, size_t k1, size_t stride_main, const u64* d_aux, size_t k3, size_t stride_aux, size_t n, u64 offset_raw,
+                      const u64* d_points, size_t n_points, const u64* d_weights, const u64* d_values, u64* d_out, void* d_work, size_t work_bytes,
+                      void* stream, int* d_status);
+size_t deep_quotient_workspace(size_t n, size_t k1, size_t k3, size_t n_points);
+int deep_quotient_plan(size_t n, size_t k1, size_t k3, size_t n_points, int* fields, int capacity);
+int deep_quotient_rows_dev(const u64* d_main_rows, size_t k1, size_t row_stride_main, const u64* d_aux_rows, size_t k3, size_t row_stride_aux, size_t n,
+                           u64 offset_raw, const uint32_t* d_indices, size_t n_rows, const u64* d_points, size_t n_points, const u64* d_weights,
+                           const u64* d_values, u64* d_out, void* stream, int* d_status);
 
 // ------------------------------------------------------------------------------------ tf_table.hip
 // the table calls of include/tf_hip.h ("Tables"): host = false takes device pointers and only enqueues on `stream`, host = true
